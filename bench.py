@@ -25,6 +25,8 @@ north-star exchange -- RCCL all-gather of x + RCCL all-reduce of the dots -- is 
 always reported (`value_rccl_allgather`); cheaper exchanges are then validated against its product
 and timed, and `value` is the best validated configuration (never below the baseline).
 
+--dump-outputs DIR writes what the last timed solve returned (a seeded sample of the iterate, the info) as float64 .npy files.
+
 Rank 0 prints ONE JSON line; see DESIGN.md "Measurement" for every field.
 """
 import argparse
@@ -214,6 +216,10 @@ def main():
                     help="REHEARSAL, not a measurement: all N ranks on GPU 0, torch side on gloo, the library's collectives from tests/fake_rccl "
                          "(the real RCCL refuses two ranks on one device) -- launch_ranks, run_sharded, votes, budget, fallbacks and the line's "
                          "fields run end to end with N > 1 before an N-GPU node has to")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed solve returned in its last repetition to DIR/*.npy (float64): "
+                         "x.npy (the iterate at a fixed, seeded sample of at most 2^21 rows, all rows when there are fewer), x_rows.npy "
+                         "(those rows) and info.npy (return code, iterations, residual) -- for comparing two builds output for output")
     ap.add_argument("--dry-launch", action="store_true",
                     help="rehearse the launch only: every rank reports its RANK / LOCAL_RANK / WORLD_SIZE over gloo, no GPU is touched")
     args = ap.parse_args()
@@ -414,6 +420,7 @@ def main():
                 barrier()               # ... everybody's are; the MAX over ranks is the job's time (the closing barrier's own
                 el = allmax(mine)       # collective is not one of the K steps)
                 runs.append((el, lib.lcg_hip_last_ax_mean_us(), lib.lcg_hip_last_ax_calls()))
+                self.last_info = info
                 lib.lcg_hip_set_profiling(0)
                 if info.iterations != steps:
                     raise RuntimeError(f"timed solve ran {info.iterations} iterations, expected {steps} (ret={info.ret})")
@@ -474,6 +481,8 @@ def main():
         else:
             times, ax_us, ax_calls, check, exchange, comm_probe, p2p = run_sharded(args, S, lib, api, partition, dist, torch, n, rank,
                                                                                   barrier, allmax, allsum, out, tdev)
+        if args.dump_outputs:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, S, r0, rank, dist, np, torch, tdev)
     except Exception as exc:        # every rank still leaves a JSON line behind (rank 0 prints it)
         out.update({"value": 0.0, "ms_per_step": None, "error": f"{type(exc).__name__}: {exc}",
                     "config": {"workload": workload_name(args.pattern, args.band, args.npairs, args.solver)}})
@@ -605,6 +614,34 @@ def main():
         lib.lcg_hip_p2p_disconnect()
         lib.lcg_hip_comm_destroy()
         dist.destroy_process_group()
+
+
+DUMP_ROWS = 1 << 21        # rows of the iterate --dump-outputs writes (x.npy + x_rows.npy: 32 MiB in float64)
+
+
+def dump_outputs(where, S, r0, rank, dist, np, torch, tdev):
+    """--dump-outputs: what the last timed solve handed its caller -- the iterate m and the info (ret, iterations, residual) -- as
+    float64 .npy files.  Above DUMP_ROWS rows the iterate is sampled at rows drawn once from a fixed seed (sorted), the same rows in
+    every run with the same --rows; sharded runs gather the sample to rank 0, which writes the files."""
+    n = S.n
+    rows = np.arange(n, dtype=np.int64) if n <= DUMP_ROWS else np.sort(np.random.default_rng(20240917).choice(n, DUMP_ROWS, replace=False))
+    mine = (rows >= r0) & (rows < r0 + S.nloc)
+    x = torch.zeros(len(rows), dtype=torch.float64, device="cuda")
+    sel = torch.from_numpy(np.nonzero(mine)[0]).cuda()
+    x[sel] = S.m[torch.from_numpy(rows[mine] - r0).cuda()]
+    if dist is not None:        # every sampled row lies in exactly one rank's shard: the sum is the gather
+        x = x.to(tdev)
+        dist.all_reduce(x)
+    torch.cuda.synchronize()
+    info = S.last_info
+    files = {"x": x.cpu().numpy(), "x_rows": rows.astype(np.float64),
+             "info": np.array([info.ret, info.iterations, info.residual], np.float64)}
+    if rank == 0:
+        os.makedirs(where, exist_ok=True)
+        for name, a in files.items():
+            np.save(os.path.join(where, f"{name}.npy"), a)
+    return {"dir": where, "files": {f"{name}.npy": list(a.shape) for name, a in files.items()},
+            "rows_sampled": len(rows) < n}
 
 
 def variants(args, System, S, lib, api, n, spmv_bytes, iteration_bytes):
