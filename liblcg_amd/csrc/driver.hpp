@@ -22,6 +22,21 @@
 
 namespace lcgh {
 
+#define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+inline uintptr_t al(const void *p) { return (uintptr_t)p; }
+double global_rows_of(Ctx &c, int n, const void *afp, const void *inst);   // comm.hip: n summed over ranks (n itself when single)
+
+// One k_vec pass over n elements; returns its grid.  Complex vectors are naturally 16-byte elements; reals use the 2-wide path
+// when every pointer is 16-byte aligned (align_or: the pointers OR-ed together).
+template <class Op> int launch_vec(const Op &op, long n, bool cplx, uintptr_t align_or, double *partials, hipStream_t s)
+{
+    const bool v2 = !cplx && (align_or & 15) == 0;
+    const int g = grid_for(v2 ? (n + 1) / 2 : n);
+    if (v2) hipLaunchKernelGGL((k_vec<Op, true>), dim3(g), dim3(VB), 0, s, op, n, partials);
+    else hipLaunchKernelGGL((k_vec<Op, false>), dim3(g), dim3(VB), 0, s, op, n, partials);
+    return g;
+}
+
 struct Driver {
     Ctx &c;
     long n;            // local vector length (reals: elements, complex: complex elements)
@@ -34,8 +49,7 @@ struct Driver {
     bool user_cb = false;
 
     Driver(Ctx &c_, long n_, bool cplx_, int max_it_, double eps_, int abs_diff_)
-        : c(c_), n(n_), cplx(cplx_), max_it(max_it_), abs_diff(abs_diff_), eps(eps_)
-    { c.in_solve = true; c.ax_rc = 0; c.cnt_vec = c.cnt_scal = c.cnt_allreduce = c.cnt_ax = 0; }
+        : c(c_), n(n_), cplx(cplx_), max_it(max_it_), abs_diff(abs_diff_), eps(eps_) {}
     ~Driver() { c.in_solve = false; }
     Driver(const Driver &) = delete;
 
@@ -58,20 +72,9 @@ struct Driver {
     // same pass over a vector of another length (e.g. the per-block partials of a fused A.x)
     template <class Op> int vec_n(Op op, long n, uintptr_t align_or)
     {
-        // complex vectors are naturally 16-byte elements; reals use the 2-wide path when
-        // every pointer is 16-byte aligned
-        const bool v2 = cplx || ((align_or & 15) == 0);
-        const long items = cplx ? n : (v2 ? (n + 1) / 2 : n);
-        const int g = grid_for(items);
         c.cnt_vec++;
         op.st = c.state;        // the state of THIS launch (vecf below moves it between the buffers of a pair)
-        if (cplx) {
-            hipLaunchKernelGGL((k_vec<Op, false>), dim3(g), dim3(VB), 0, c.stream, op, n, c.partials);
-        } else if (v2) {
-            hipLaunchKernelGGL((k_vec<Op, true>), dim3(g), dim3(VB), 0, c.stream, op, n, c.partials);
-        } else {
-            hipLaunchKernelGGL((k_vec<Op, false>), dim3(g), dim3(VB), 0, c.stream, op, n, c.partials);
-        }
+        const int g = launch_vec(op, n, cplx, align_or, c.partials, c.stream);
         if (Op::NR > 0) pcnt.all(g);
         HIPCHK(hipGetLastError());
         return dbg(typeid(Op).name());
@@ -145,8 +148,11 @@ struct Driver {
     }
 
     // ---- state -------------------------------------------------------------------------------
+    // the solve begins here (not in the constructor: Placement's trial products come first, and must neither be counted nor
+    // honour a stop flag): launch counters zeroed, the built-in callbacks told that a solve runs, DevState initialised
     int init_state(double n_global)
     {
+        c.in_solve = true; c.ax_rc = 0; c.cnt_vec = c.cnt_scal = c.cnt_allreduce = c.cnt_ax = 0;
         DevState h;
         std::memset(&h, 0, sizeof h);
         h.eps = eps; h.abs_diff = abs_diff; h.n_global = n_global; h.host = c.hstat_dev;
@@ -685,5 +691,67 @@ struct Placement {
         return 0;
     }
 };
+
+// ---- one solve: the plumbing around a solver's loop (real and complex differ in callback types and NaN code) --------------------
+template <bool CPLX> struct SolveTypes;
+template <> struct SolveTypes<false> {
+    using Para = lcg_para; using Ax = lcg_axfunc_ptr; using Progress = lcg_progress_ptr;
+    static constexpr Ax csr_ax = lcg_hip_csr_ax;
+    static constexpr int NAN_CODE = LCG_NAN_VALUE;
+};
+template <> struct SolveTypes<true> {
+    using Para = clcg_para; using Ax = clcg_hip_axfunc_ptr; using Progress = clcg_hip_progress_ptr;
+    static constexpr Ax csr_ax = clcg_hip_csr_ax;
+    static constexpr int NAN_CODE = CLCG_NAN_VALUE;
+};
+
+// A solver's setup, after its own argument checks and ensure_init(), in this order: open() (m and B onto the device when they live
+// in host memory), get() (the work vectors -- the ORDER of the calls decides which pool vector a role receives), place() (real,
+// optional: before start(), whose counters its trial products must not bump), start(); the loop's return code goes through
+// finish(rc).  Destruction runs in reverse: the Driver, the Workspace (its vectors back to the pool), the HostBridge.
+template <bool CPLX>
+struct Solve {
+    using T = SolveTypes<CPLX>;
+    Ctx &c;
+    HostBridge hb;
+    Workspace ws;
+    Driver drv;
+    typename T::Para para; void *inst; typename T::Ax Afp; typename T::Progress Pfp;
+    int n;
+    size_t nb;              // bytes of one vector
+    double *m = nullptr;    // the solution vector on the device (set by open)
+    Solve(const typename T::Para &p, int n_, void *inst_, typename T::Ax A, typename T::Progress P)
+        : c(ctx()), drv(c, n_, CPLX, p.max_iterations, p.epsilon, p.abs_diff), para(p), inst(inst_), Afp(A), Pfp(P), n(n_),
+          nb(sizeof(double) * (CPLX ? 2 : 1) * (size_t)n_)
+    { drv.user_cb = A != T::csr_ax; }
+
+    int open(int mem, double *&m_, const double *&B) { TRY(hb.open(mem, m_, B, nb, c.stream)); m = m_; return 0; }
+    int get(double *&out, double *given = nullptr) { return ws.get(out, given, nb); }
+    int place(const double *x, std::initializer_list<double **> roles, int n_out) { return Placement::run(c, n, (const void *)Afp, inst, x, ws, roles, n_out); }
+    int start() { return drv.init_state(global_rows_of(c, n, (const void *)Afp, inst)); }
+    // a runtime failure of the loop (LCG_HIP_E_*) wins over one of the copy-back; that one over the loop's verdict
+    int finish(int rc) { const int rc2 = hb.close(c.stream); return rc <= -2000 ? rc : (rc2 ? rc2 : rc); }
+
+    int axop(const double *x, double *y, int layout, int conj) { return drv.timed_ax([&] { Afp(inst, x, y, n, layout, conj); }); }
+    int ax(const double *x, double *y)
+    {
+        if constexpr (CPLX) return axop(x, y, 0, 0);
+        else return drv.timed_ax([&] { Afp(inst, x, y, n); });
+    }
+    int run_loop(const std::function<int()> &body)
+    {
+        auto pfp = [&](double resid, int t) -> int { return Pfp(inst, m, resid, &para, n, t); };
+        // (the complex loops hand back the REAL enum's iteration-cap code, clcg.cpp:126,164 ...)
+        return drv.run(body, Pfp != nullptr, pfp, LCG_REACHED_MAX_ITERATIONS, T::NAN_CODE);
+    }
+};
+
+// the built-in Jacobi on a handle that owns its reciprocal diagonal: M^-1 folds into the update pass (its diagonal; else nullptr)
+inline const double *builtin_invdiag(const void *Mfp, void *inst, int n, bool cplx)
+{
+    if (Mfp != (cplx ? (const void *)clcg_hip_jacobi_mx : (const void *)lcg_hip_jacobi_mx) || !inst) return nullptr;
+    const lcg_hip_csr *A = static_cast<const lcg_hip_csr *>(inst);
+    return A->is_complex == cplx && A->n_rows == n ? A->invdiag : nullptr;
+}
 
 } // namespace lcgh

@@ -132,10 +132,17 @@ template <int SLOT> struct FinStore1 {   // park one reduced sum in DevState::s[
     __device__ void operator()(DevState *st, const double *sum) const { st->s[SLOT] = sum[0]; }
 };
 
-static inline uintptr_t al(const void *p) { return (uintptr_t)p; }
-double global_rows(Ctx &c, int n);
-double global_rows_of(Ctx &c, int n, const void *afp, const void *inst);   // comm.hip
-#define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
+// low / hig where the caller's vectors live in host memory: device copies in the solve's workspace
+static int stage_bounds(Solve<false> &k, int mem, const double *&low, const double *&hig)
+{
+    if (mem != LCG_HIP_MEM_HOST) return 0;
+    double *dlow, *dhig;
+    TRY(k.get(dlow)); TRY(k.get(dhig));
+    HIPCHK(hipMemcpyAsync(dlow, low, k.nb, hipMemcpyHostToDevice, k.c.stream));
+    HIPCHK(hipMemcpyAsync(dhig, hig, k.nb, hipMemcpyHostToDevice, k.c.stream));
+    low = dlow; hig = dhig;
+    return 0;
+}
 
 static int solve_pg(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, const double *B, const double *low,
                     const double *hig, int n, const lcg_para *param, void *inst, int mem)
@@ -147,39 +154,28 @@ static int solve_pg(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, const d
     if (p.step <= 0.0 || p.epsilon >= 1.0) return LCG_INVALID_LAMBDA;
     if (!m || !B || !low || !hig) return LCG_INVALID_POINTER;
     TRY(ensure_init());
-    Ctx &c = ctx();
-    const size_t nb = sizeof(double) * n;
-    HostBridge hb; TRY(hb.open(mem, m, B, nb, c.stream));
-    Workspace ws; double *g, *Ad, *mn, *dlow = nullptr, *dhig = nullptr;
-    TRY(ws.get(g, nullptr, nb)); TRY(ws.get(Ad, nullptr, nb)); TRY(ws.get(mn, nullptr, nb));
-    if (mem == LCG_HIP_MEM_HOST) {
-        TRY(ws.get(dlow, nullptr, nb)); TRY(ws.get(dhig, nullptr, nb));
-        HIPCHK(hipMemcpyAsync(dlow, low, nb, hipMemcpyHostToDevice, c.stream));
-        HIPCHK(hipMemcpyAsync(dhig, hig, nb, hipMemcpyHostToDevice, c.stream));
-        low = dlow; hig = dhig;
-    }
-    Driver drv(c, n, false, p.max_iterations, p.epsilon, p.abs_diff);
-    drv.user_cb = Afp != lcg_hip_csr_ax;
-    TRY(drv.init_state(global_rows_of(c, n, (const void *)Afp, inst)));
-    DevState *st = c.state;
+    Solve<false> k(p, n, inst, Afp, Pfp);
+    TRY(k.open(mem, m, B));
+    double *g, *Ad, *mn;
+    TRY(k.get(g)); TRY(k.get(Ad)); TRY(k.get(mn));
+    TRY(stage_bounds(k, mem, low, hig));
+    TRY(k.start());
+    Driver &drv = k.drv;
+    DevState *st = k.c.state;
     const uintptr_t a_all = al(m) | al(B) | al(g) | al(Ad) | al(mn) | al(low) | al(hig);
-    lcg_para para = p;
-    auto ax = [&](const double *x, double *y) { return drv.timed_ax([&] { Afp(inst, x, y, n); }); };
 
     TRY(drv.vec(OpClamp{st, m, low, hig}, a_all));                               // :1084-1088
-    TRY(ax(m, Ad));
+    TRY(k.ax(m, Ad));
     TRY(drv.vec(OpBoxInit{st, Ad, B, m, g}, a_all));
     TRY(drv.scal(FinBoxInit{p.step}));
-    auto pfp = [&](double resid, int t) -> int { return Pfp(inst, m, resid, &para, n, t); };
-    int rc = drv.run([&]() -> int {
+    int rc = k.run_loop([&]() -> int {
         TRY(drv.vec(OpPgStep{st, m, g, low, hig, mn, 0.0}, a_all));              // :1151-1155
-        TRY(ax(mn, Ad));                                                         // :1157
+        TRY(k.ax(mn, Ad));                                                       // :1157
         TRY(drv.vec(OpBoxUpdate{st, Ad, B, mn, m, g}, a_all));                   // :1159-1190
         TRY(drv.scal(FinBoxClose{}));
         return 0;
-    }, Pfp != nullptr, pfp, LCG_REACHED_MAX_ITERATIONS, LCG_NAN_VALUE);
-    int rc2 = hb.close(c.stream);
-    return rc <= -2000 ? rc : (rc2 ? rc2 : rc);
+    });
+    return k.finish(rc);
 }
 
 static int solve_spg(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, const double *B, const double *low,
@@ -195,40 +191,31 @@ static int solve_spg(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, const 
     if (p.maxi_m <= 0) return LCG_INVALID_MAXIM;
     if (!m || !B || !low || !hig) return LCG_INVALID_POINTER;
     TRY(ensure_init());
-    Ctx &c = ctx();
-    const size_t nb = sizeof(double) * n;
-    HostBridge hb; TRY(hb.open(mem, m, B, nb, c.stream));
-    Workspace ws; double *g, *Ad, *mn, *d, *dlow = nullptr, *dhig = nullptr;
-    TRY(ws.get(g, nullptr, nb)); TRY(ws.get(Ad, nullptr, nb)); TRY(ws.get(mn, nullptr, nb)); TRY(ws.get(d, nullptr, nb));
-    if (mem == LCG_HIP_MEM_HOST) {
-        TRY(ws.get(dlow, nullptr, nb)); TRY(ws.get(dhig, nullptr, nb));
-        HIPCHK(hipMemcpyAsync(dlow, low, nb, hipMemcpyHostToDevice, c.stream));
-        HIPCHK(hipMemcpyAsync(dhig, hig, nb, hipMemcpyHostToDevice, c.stream));
-        low = dlow; hig = dhig;
-    }
-    Driver drv(c, n, false, p.max_iterations, p.epsilon, p.abs_diff);
-    drv.user_cb = Afp != lcg_hip_csr_ax;
-    TRY(drv.init_state(global_rows_of(c, n, (const void *)Afp, inst)));
-    DevState *st = c.state;
+    Solve<false> k(p, n, inst, Afp, Pfp);
+    TRY(k.open(mem, m, B));
+    double *g, *Ad, *mn, *d;
+    TRY(k.get(g)); TRY(k.get(Ad)); TRY(k.get(mn)); TRY(k.get(d));
+    TRY(stage_bounds(k, mem, low, hig));
+    TRY(k.start());
+    Driver &drv = k.drv;
+    DevState *st = k.c.state;
     const uintptr_t a_all = al(m) | al(B) | al(g) | al(Ad) | al(mn) | al(d) | al(low) | al(hig);
-    lcg_para para = p;
-    auto ax = [&](const double *x, double *y) { return drv.timed_ax([&] { Afp(inst, x, y, n); }); };
 
     TRY(drv.vec(OpClamp{st, m, low, hig}, a_all));
-    TRY(ax(m, Ad));
+    TRY(k.ax(m, Ad));
     TRY(drv.vec(OpBoxInit{st, Ad, B, m, g}, a_all));
     TRY(drv.scal(FinBoxInit{p.step}));
     DevState h;
     TRY(drv.read_state(h));
-    auto leave = [&](int code) { drv.finish(h); int rc2 = hb.close(c.stream); return rc2 ? rc2 : code; };
+    auto leave = [&](int code) { drv.finish(h); return k.finish(code); };
     if (h.status == ST_ALREADY) {
-        if (Pfp) Pfp(inst, m, h.residual, &para, n, 0);
+        if (Pfp) Pfp(inst, m, h.residual, &k.para, n, 0);
         return leave(LCG_ALREADY_OPTIMIZIED);
     }
     std::vector<double> qm((size_t)p.maxi_m, -1e+30);                           // :1301-1305
     qm[0] = h.s[8];
     for (;;) {                                                                   // host-driven: see file header
-        if (Pfp && Pfp(inst, m, h.residual, &para, n, h.t)) return leave(LCG_STOP);
+        if (Pfp && Pfp(inst, m, h.residual, &k.para, n, h.t)) return leave(LCG_STOP);
         if (h.residual <= p.epsilon) return leave(LCG_CONVERGENCE);
         if (p.max_iterations > 0 && h.t + 1 > p.max_iterations) return leave(LCG_REACHED_MAX_ITERATIONS);
         const int t = h.t + 1;
@@ -237,7 +224,7 @@ static int solve_spg(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, const 
         double ak = 1.0;
         const double qmax = *std::max_element(qm.begin(), qm.end());             // :1366-1370
         for (;;) {
-            TRY(ax(mn, Ad));                                                     // :1351 / :1381
+            TRY(k.ax(mn, Ad));                                                   // :1351 / :1381
             TRY(drv.vec(OpSpgQ{st, mn, Ad, B}, a_all));
             TRY(drv.scal(FinStore1<8>{}));
             TRY(drv.read_state(h));
@@ -270,11 +257,7 @@ int lcg_hip_set2box(int n, const double *low, const double *hig, double *a)
     if (n <= 0 || !low || !hig || !a) return LCG_HIP_E_ARG;
     int rc = ensure_init(); if (rc) return rc;
     Ctx &c = ctx();
-    const bool v2 = ((al(low) | al(hig) | al(a)) & 15) == 0;
-    const int g = grid_for(v2 ? (n + 1) / 2 : n);
-    OpClamp op{nullptr, a, low, hig};
-    if (v2) hipLaunchKernelGGL((k_vec<OpClamp, true>), dim3(g), dim3(VB), 0, c.stream, op, (long)n, c.partials);
-    else hipLaunchKernelGGL((k_vec<OpClamp, false>), dim3(g), dim3(VB), 0, c.stream, op, (long)n, c.partials);
+    (void)launch_vec(OpClamp{nullptr, a, low, hig}, n, false, al(low) | al(hig) | al(a), c.partials, c.stream);
     HIPCHK(hipGetLastError());
     return 0;
 }

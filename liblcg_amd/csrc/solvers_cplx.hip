@@ -533,26 +533,7 @@ static int ccheck_args(const clcg_para &p, int n, const double *m, const double 
     return 0;
 }
 
-double global_rows(Ctx &c, int n);
-double global_rows_of(Ctx &c, int n, const void *afp, const void *inst);   // comm.hip
-
-#define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
-
-struct CplxCommon {
-    Ctx &c; Driver drv; clcg_para para; void *inst; clcg_hip_axfunc_ptr Afp; clcg_hip_progress_ptr Pfp;
-    double *m; int n;
-    CplxCommon(Ctx &c_, int n_, const clcg_para &p, void *inst_, clcg_hip_axfunc_ptr A, clcg_hip_progress_ptr P, double *m_)
-        : c(c_), drv(c_, n_, true, p.max_iterations, p.epsilon, p.abs_diff), para(p), inst(inst_), Afp(A), Pfp(P), m(m_), n(n_)
-    { drv.user_cb = A != clcg_hip_csr_ax; }
-    int ax(const double *x, double *y) { return drv.timed_ax([&] { Afp(inst, x, y, n, 0, 0); }); }
-    int axop(const double *x, double *y, int layout, int conj) { return drv.timed_ax([&] { Afp(inst, x, y, n, layout, conj); }); }
-    int run_loop(const std::function<int()> &body)
-    {
-        auto pfp = [&](double resid, int t) -> int { return Pfp(inst, m, resid, &para, n, t); };
-        // the complex loops hand back the REAL enum's iteration-cap code (clcg.cpp:126,164 ...)
-        return drv.run(body, Pfp != nullptr, pfp, LCG_REACHED_MAX_ITERATIONS, CLCG_NAN_VALUE);
-    }
-};
+using ClxSolve = Solve<true>;
 
 // rbar0 in [1,2] + 0i: lcg_complex.cpp:118-127 with an explicit seed; or the caller's vector
 static int make_shadow(Ctx &c, int n, double *dev)
@@ -577,15 +558,12 @@ static int solve_cbicg(clcg_hip_axfunc_ptr Afp, clcg_hip_progress_ptr Pfp, doubl
     const clcg_para p = param ? *param : clcg_hip_default_parameters();
     TRY(ccheck_args(p, n, m, B));
     TRY(ensure_init());
-    Ctx &c = ctx();
-    const size_t nb = sizeof(double) * 2 * (size_t)n;
-    HostBridge hb; TRY(hb.open(mem, m, B, nb, c.stream));
-    Workspace ws; double *r1, *r2, *d1, *d2, *Ax;
-    TRY(ws.get(r1, nullptr, nb)); TRY(ws.get(r2, nullptr, nb)); TRY(ws.get(d1, nullptr, nb));
-    TRY(ws.get(d2, nullptr, nb)); TRY(ws.get(Ax, nullptr, nb));
-    CplxCommon k(c, n, p, inst, Afp, Pfp, m);
-    TRY(k.drv.init_state(global_rows_of(c, n, (const void *)Afp, inst)));
-    DevState *st = c.state;
+    ClxSolve k(p, n, inst, Afp, Pfp);
+    TRY(k.open(mem, m, B));
+    double *r1, *r2, *d1, *d2, *Ax;
+    TRY(k.get(r1)); TRY(k.get(r2)); TRY(k.get(d1)); TRY(k.get(d2)); TRY(k.get(Ax));
+    TRY(k.start());
+    DevState *st = k.c.state;
 
     TRY(k.ax(m, Ax));                                                   // clcg.cpp:99
     TRY(k.drv.vec(OpZBicgInit{st, Ax, B, m, r1, r2, d1, d2}));           // :101-120
@@ -599,8 +577,7 @@ static int solve_cbicg(clcg_hip_axfunc_ptr Afp, clcg_hip_progress_ptr Pfp, doubl
         TRY(k.drv.vecf(FinZClose<0>{}, OpZBicgDirPair{st, d1, d2, r1, r2, {}}));   // :204-205 | :207-212
         return 0;
     });
-    int rc2 = hb.close(c.stream);
-    return rc <= -2000 ? rc : (rc2 ? rc2 : rc);
+    return k.finish(rc);
 }
 
 static int solve_cpcg(clcg_hip_axfunc_ptr Afp, clcg_hip_axfunc_ptr Mfp, clcg_hip_progress_ptr Pfp, double *m,
@@ -610,20 +587,14 @@ static int solve_cpcg(clcg_hip_axfunc_ptr Afp, clcg_hip_axfunc_ptr Mfp, clcg_hip
     TRY(ccheck_args(p, n, m, B));
     if (Mfp == nullptr) return LCG_NULL_PRECONDITION_MATRIX;
     TRY(ensure_init());
-    Ctx &c = ctx();
-    const size_t nb = sizeof(double) * 2 * (size_t)n;
-    HostBridge hb; TRY(hb.open(mem, m, B, nb, c.stream));
-    Workspace ws; double *r, *d, *s, *Ax;
-    TRY(ws.get(r, nullptr, nb)); TRY(ws.get(d, nullptr, nb)); TRY(ws.get(s, nullptr, nb)); TRY(ws.get(Ax, nullptr, nb));
-    CplxCommon k(c, n, p, inst, Afp, Pfp, m);
-    TRY(k.drv.init_state(global_rows_of(c, n, (const void *)Afp, inst)));
-    DevState *st = c.state;
-    const double *inv = nullptr;        // built-in Jacobi on a complex handle: fold M^-1 into the update
+    ClxSolve k(p, n, inst, Afp, Pfp);
+    TRY(k.open(mem, m, B));
+    double *r, *d, *s, *Ax;
+    TRY(k.get(r)); TRY(k.get(d)); TRY(k.get(s)); TRY(k.get(Ax));
+    TRY(k.start());
+    DevState *st = k.c.state;
     if (Mfp != clcg_hip_jacobi_mx) k.drv.user_cb = true;
-    if (Mfp == clcg_hip_jacobi_mx && inst) {
-        const lcg_hip_csr *A = static_cast<const lcg_hip_csr *>(inst);
-        if (A->is_complex && A->n_rows == n) inv = A->invdiag;
-    }
+    const double *inv = builtin_invdiag((const void *)Mfp, inst, n, true);
 
     TRY(k.ax(m, Ax));                                                   // clcg_cuda.cu:441
     TRY(k.drv.vec(OpZResid{st, Ax, B, r}));                             // :442-443
@@ -643,8 +614,7 @@ static int solve_cpcg(clcg_hip_axfunc_ptr Afp, clcg_hip_axfunc_ptr Mfp, clcg_hip
         TRY(k.drv.vecf(FinZPcg<false>{}, OpZXpay{st, d, s, {}}));   // :517 | :519-520  d = s + b d
         return 0;
     });
-    int rc2 = hb.close(c.stream);
-    return rc <= -2000 ? rc : (rc2 ? rc2 : rc);
+    return k.finish(rc);
 }
 
 static int solve_cpbicg(clcg_hip_axfunc_ptr Afp, clcg_hip_axfunc_ptr Mfp, clcg_hip_progress_ptr Pfp, double *m,
@@ -654,21 +624,14 @@ static int solve_cpbicg(clcg_hip_axfunc_ptr Afp, clcg_hip_axfunc_ptr Mfp, clcg_h
     TRY(ccheck_args(p, n, m, B));                                       // clcg_eigen.cpp:693-697
     if (Mfp == nullptr) return LCG_NULL_PRECONDITION_MATRIX;
     TRY(ensure_init());
-    Ctx &c = ctx();
-    const size_t nb = sizeof(double) * 2 * (size_t)n;
-    HostBridge hb; TRY(hb.open(mem, m, B, nb, c.stream));
-    Workspace ws; double *r, *rs, *z, *pk, *ps, *Ax, *Asx;
-    TRY(ws.get(r, nullptr, nb)); TRY(ws.get(rs, nullptr, nb)); TRY(ws.get(z, nullptr, nb)); TRY(ws.get(pk, nullptr, nb));
-    TRY(ws.get(ps, nullptr, nb)); TRY(ws.get(Ax, nullptr, nb)); TRY(ws.get(Asx, nullptr, nb));
-    CplxCommon k(c, n, p, inst, Afp, Pfp, m);
-    TRY(k.drv.init_state(global_rows_of(c, n, (const void *)Afp, inst)));
-    DevState *st = c.state;
-    const double *inv = nullptr;        // built-in Jacobi on a complex handle: fold M^-1 into the update
+    ClxSolve k(p, n, inst, Afp, Pfp);
+    TRY(k.open(mem, m, B));
+    double *r, *rs, *z, *pk, *ps, *Ax, *Asx;
+    TRY(k.get(r)); TRY(k.get(rs)); TRY(k.get(z)); TRY(k.get(pk)); TRY(k.get(ps)); TRY(k.get(Ax)); TRY(k.get(Asx));
+    TRY(k.start());
+    DevState *st = k.c.state;
     if (Mfp != clcg_hip_jacobi_mx) k.drv.user_cb = true;
-    if (Mfp == clcg_hip_jacobi_mx && inst) {
-        const lcg_hip_csr *A = static_cast<const lcg_hip_csr *>(inst);
-        if (A->is_complex && A->n_rows == n) inv = A->invdiag;
-    }
+    const double *inv = builtin_invdiag((const void *)Mfp, inst, n, true);
 
     TRY(k.ax(m, Ax));                                                   // :702
     TRY(k.drv.vec(OpZResid{st, Ax, B, r}));                             // :704
@@ -689,8 +652,7 @@ static int solve_cpbicg(clcg_hip_axfunc_ptr Afp, clcg_hip_axfunc_ptr Mfp, clcg_h
         TRY(k.drv.vecf(FinZClose<0>{}, OpZPbDir{st, pk, ps, z, {}}));   // :778-779 | :781-782
         return 0;
     });
-    int rc2 = hb.close(c.stream);
-    return rc <= -2000 ? rc : (rc2 ? rc2 : rc);
+    return k.finish(rc);
 }
 
 static int solve_bicg_sym(clcg_hip_axfunc_ptr Afp, clcg_hip_progress_ptr Pfp, double *m, const double *B, int n,
@@ -699,14 +661,12 @@ static int solve_bicg_sym(clcg_hip_axfunc_ptr Afp, clcg_hip_progress_ptr Pfp, do
     const clcg_para p = param ? *param : clcg_hip_default_parameters();
     TRY(ccheck_args(p, n, m, B));
     TRY(ensure_init());
-    Ctx &c = ctx();
-    const size_t nb = sizeof(double) * 2 * (size_t)n;
-    HostBridge hb; TRY(hb.open(mem, m, B, nb, c.stream));
-    Workspace ws; double *r, *d, *Ax;
-    TRY(ws.get(r, nullptr, nb)); TRY(ws.get(d, nullptr, nb)); TRY(ws.get(Ax, nullptr, nb));
-    CplxCommon k(c, n, p, inst, Afp, Pfp, m);
-    TRY(k.drv.init_state(global_rows_of(c, n, (const void *)Afp, inst)));
-    DevState *st = c.state;
+    ClxSolve k(p, n, inst, Afp, Pfp);
+    TRY(k.open(mem, m, B));
+    double *r, *d, *Ax;
+    TRY(k.get(r)); TRY(k.get(d)); TRY(k.get(Ax));
+    TRY(k.start());
+    DevState *st = k.c.state;
 
     TRY(k.ax(m, Ax));                                                   // clcg.cpp:250
     TRY(k.drv.vec(OpSymInit{st, Ax, B, m, r, d}));                      // :252-270
@@ -718,8 +678,7 @@ static int solve_bicg_sym(clcg_hip_axfunc_ptr Afp, clcg_hip_progress_ptr Pfp, do
         TRY(k.drv.vecf(FinZClose<1>{}, OpZXpay{st, d, r, {}}));   // :346-347 | :349-353
         return 0;
     });
-    int rc2 = hb.close(c.stream);
-    return rc <= -2000 ? rc : (rc2 ? rc2 : rc);
+    return k.finish(rc);
 }
 
 static int solve_ccgs(clcg_hip_axfunc_ptr Afp, clcg_hip_progress_ptr Pfp, double *m, const double *B, int n,
@@ -728,16 +687,13 @@ static int solve_ccgs(clcg_hip_axfunc_ptr Afp, clcg_hip_progress_ptr Pfp, double
     const clcg_para p = param ? *param : clcg_hip_default_parameters();
     TRY(ccheck_args(p, n, m, B));
     TRY(ensure_init());
-    Ctx &c = ctx();
-    const size_t nb = sizeof(double) * 2 * (size_t)n;
-    HostBridge hb; TRY(hb.open(mem, m, B, nb, c.stream));
-    Workspace ws; double *r, *rb, *pk, *Ax, *u, *q, *w;
-    TRY(ws.get(r, nullptr, nb)); TRY(ws.get(rb, nullptr, nb)); TRY(ws.get(pk, nullptr, nb)); TRY(ws.get(Ax, nullptr, nb));
-    TRY(ws.get(u, nullptr, nb)); TRY(ws.get(q, nullptr, nb)); TRY(ws.get(w, nullptr, nb));
-    CplxCommon k(c, n, p, inst, Afp, Pfp, m);
-    TRY(k.drv.init_state(global_rows_of(c, n, (const void *)Afp, inst)));
-    DevState *st = c.state;
-    TRY(make_shadow(c, n, rb));                                         // clcg.cpp:399-404
+    ClxSolve k(p, n, inst, Afp, Pfp);
+    TRY(k.open(mem, m, B));
+    double *r, *rb, *pk, *Ax, *u, *q, *w;
+    TRY(k.get(r)); TRY(k.get(rb)); TRY(k.get(pk)); TRY(k.get(Ax)); TRY(k.get(u)); TRY(k.get(q)); TRY(k.get(w));
+    TRY(k.start());
+    DevState *st = k.c.state;
+    TRY(make_shadow(k.c, n, rb));                                         // clcg.cpp:399-404
 
     TRY(k.ax(m, Ax));                                                   // :391
     TRY(k.drv.vec(OpZShadowInit<0>{st, Ax, B, m, rb, r, pk, u, nullptr}));  // :393-415
@@ -751,8 +707,7 @@ static int solve_ccgs(clcg_hip_axfunc_ptr Afp, clcg_hip_progress_ptr Pfp, double
         TRY(k.drv.vecf(FinZClose<0>{}, OpZUP{st, u, pk, r, q, {}}));   // :499-500 | :502-507
         return 0;
     });
-    int rc2 = hb.close(c.stream);
-    return rc <= -2000 ? rc : (rc2 ? rc2 : rc);
+    return k.finish(rc);
 }
 
 static int solve_cbicgstab(clcg_hip_axfunc_ptr Afp, clcg_hip_progress_ptr Pfp, double *m, const double *B, int n,
@@ -761,16 +716,13 @@ static int solve_cbicgstab(clcg_hip_axfunc_ptr Afp, clcg_hip_progress_ptr Pfp, d
     const clcg_para p = param ? *param : clcg_hip_default_parameters();
     TRY(ccheck_args(p, n, m, B));
     TRY(ensure_init());
-    Ctx &c = ctx();
-    const size_t nb = sizeof(double) * 2 * (size_t)n;
-    HostBridge hb; TRY(hb.open(mem, m, B, nb, c.stream));
-    Workspace ws; double *r, *rb, *pk, *s, *Ap, *As;
-    TRY(ws.get(r, nullptr, nb)); TRY(ws.get(rb, nullptr, nb)); TRY(ws.get(pk, nullptr, nb));
-    TRY(ws.get(s, nullptr, nb)); TRY(ws.get(Ap, nullptr, nb)); TRY(ws.get(As, nullptr, nb));
-    CplxCommon k(c, n, p, inst, Afp, Pfp, m);
-    TRY(k.drv.init_state(global_rows_of(c, n, (const void *)Afp, inst)));
-    DevState *st = c.state;
-    TRY(make_shadow(c, n, rb));                                         // clcg.cpp:556-561
+    ClxSolve k(p, n, inst, Afp, Pfp);
+    TRY(k.open(mem, m, B));
+    double *r, *rb, *pk, *s, *Ap, *As;
+    TRY(k.get(r)); TRY(k.get(rb)); TRY(k.get(pk)); TRY(k.get(s)); TRY(k.get(Ap)); TRY(k.get(As));
+    TRY(k.start());
+    DevState *st = k.c.state;
+    TRY(make_shadow(k.c, n, rb));                                         // clcg.cpp:556-561
 
     TRY(k.ax(m, Ap));                                                   // :548
     TRY(k.drv.vec(OpZShadowInit<1>{st, Ap, B, m, rb, r, pk, nullptr, nullptr}));   // :550-572
@@ -785,8 +737,7 @@ static int solve_cbicgstab(clcg_hip_axfunc_ptr Afp, clcg_hip_progress_ptr Pfp, d
         TRY(k.drv.vecf(FinZClose<2>{}, OpZBicgDir{st, pk, r, Ap, {}, {}}));   // :658-659 | :661-665
         return 0;
     });
-    int rc2 = hb.close(c.stream);
-    return rc <= -2000 ? rc : (rc2 ? rc2 : rc);
+    return k.finish(rc);
 }
 
 static int solve_tfqmr(clcg_hip_axfunc_ptr Afp, clcg_hip_progress_ptr Pfp, double *m, const double *B, int n,
@@ -795,17 +746,14 @@ static int solve_tfqmr(clcg_hip_axfunc_ptr Afp, clcg_hip_progress_ptr Pfp, doubl
     const clcg_para p = param ? *param : clcg_hip_default_parameters();
     TRY(ccheck_args(p, n, m, B));
     TRY(ensure_init());
-    Ctx &c = ctx();
-    const size_t nb = sizeof(double) * 2 * (size_t)n;
-    HostBridge hb; TRY(hb.open(mem, m, B, nb, c.stream));
-    Workspace ws; double *pk, *u, *v, *d, *rb, *r, *Ax, *q, *uq;
-    TRY(ws.get(pk, nullptr, nb)); TRY(ws.get(u, nullptr, nb)); TRY(ws.get(v, nullptr, nb)); TRY(ws.get(d, nullptr, nb));
-    TRY(ws.get(rb, nullptr, nb)); TRY(ws.get(r, nullptr, nb)); TRY(ws.get(Ax, nullptr, nb)); TRY(ws.get(q, nullptr, nb));
-    TRY(ws.get(uq, nullptr, nb));
-    CplxCommon k(c, n, p, inst, Afp, Pfp, m);
-    TRY(k.drv.init_state(global_rows_of(c, n, (const void *)Afp, inst)));
-    DevState *st = c.state;
-    TRY(make_shadow(c, n, rb));                                         // clcg.cpp:721-725
+    ClxSolve k(p, n, inst, Afp, Pfp);
+    TRY(k.open(mem, m, B));
+    double *pk, *u, *v, *d, *rb, *r, *Ax, *q, *uq;
+    TRY(k.get(pk)); TRY(k.get(u)); TRY(k.get(v)); TRY(k.get(d)); TRY(k.get(rb)); TRY(k.get(r)); TRY(k.get(Ax)); TRY(k.get(q));
+    TRY(k.get(uq));
+    TRY(k.start());
+    DevState *st = k.c.state;
+    TRY(make_shadow(k.c, n, rb));                                         // clcg.cpp:721-725
 
     TRY(k.ax(m, Ax));                                                   // :707
     TRY(k.drv.vec(OpZShadowInit<2>{st, Ax, B, m, rb, r, pk, u, d}));    // :709-735
@@ -828,8 +776,7 @@ static int solve_tfqmr(clcg_hip_axfunc_ptr Afp, clcg_hip_progress_ptr Pfp, doubl
         }
         return 0;
     });
-    int rc2 = hb.close(c.stream);
-    return rc <= -2000 ? rc : (rc2 ? rc2 : rc);
+    return k.finish(rc);
 }
 
 } // namespace lcgh

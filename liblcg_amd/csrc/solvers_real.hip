@@ -406,7 +406,6 @@ struct OpBicgDir {      // p = r + b (p - w Ap)                           lcg.cp
 };
 
 // ---- host drivers -------------------------------------------------------------------------------
-static inline uintptr_t al(const void *p) { return (uintptr_t)p; }
 
 // Cache policy of the vector passes.  On a system whose product streams far more than the 256 MB Infinity Cache holds, the passes
 // read and write what the NEXT kernels do not need (the iterate, A.d after the update, g in the direction pass, the Jacobi diagonal)
@@ -429,13 +428,9 @@ static bool stream_vectors(long n, lcg_axfunc_ptr Afp, void *inst)
     return n * 40L > (256L << 20);       // a product of the caller's own: nothing is known about its stream
 }
 
-struct RealCommon {
-    Ctx &c; Driver drv; lcg_para para; void *inst; lcg_axfunc_ptr Afp; lcg_progress_ptr Pfp;
-    double *m; int n;
-    RealCommon(Ctx &c_, int n_, const lcg_para &p, void *inst_, lcg_axfunc_ptr A, lcg_progress_ptr P, double *m_)
-        : c(c_), drv(c_, n_, false, p.max_iterations, p.epsilon, p.abs_diff), para(p), inst(inst_),
-          Afp(A), Pfp(P), m(m_), n(n_) { drv.user_cb = A != lcg_hip_csr_ax; }
-    int ax(const double *x, double *y) { return drv.timed_ax([&] { Afp(inst, x, y, n); }); }
+// The real solvers' scope: the common plumbing (driver.hpp: Solve) and the built-in product's extras
+struct RealSolve : Solve<false> {
+    using Solve::Solve;
     // y = A.m for the initial guess (lcg.cpp:168, 314, 476, 648).  With the built-in product: the zero-guess probe in front (above),
     // the product honouring its verdict, and no event pair around a launch that may be empty (lcg_hip_last_ax_mean_us is about products).
     int ax_setup(const double *m0, double *y)
@@ -475,10 +470,32 @@ struct RealCommon {
         }
         return rc;
     }
-    int run_loop(const std::function<int()> &body)
+
+    // ---- the one-reduction arrangements (CG, PCG + built-in Jacobi) ----
+    // The product that closes a body only serves the NEXT body's step length: the body the iteration cap ends the solve with goes
+    // without it (K iterations = K + 1 products, as in the reference's loop: lcg.cpp:168, 232).  Its closing step then finds NO
+    // partial sums in `row` -- neither the previous body's nor an unwritten table row: the count of that row is zero, the sum exactly
+    // 0, and the a_k, b_k the step leaves behind are a fixed function of the state; nothing reads them after the cap.
+    bool last_body(int row)
     {
-        auto pfp = [&](double resid, int t) -> int { return Pfp(inst, m, resid, &para, n, t); };
-        return drv.run(body, Pfp != nullptr, pfp, LCG_REACHED_MAX_ITERATIONS, LCG_NAN_VALUE);
+        const bool last = para.max_iterations > 0 && drv.enq + 1 >= para.max_iterations;
+        if (last) { drv.pcnt.ax_n = 0; drv.pcnt.ax_row = -1; drv.pcnt.g[row] = 0; }
+        return last;
+    }
+    // One GPU, no progress callback: the scalar step that closes body k (Close) rides in the update pass `upd` of body k + 1
+    // (FinCg1Start -- a_0, b_0 -- in front of the first); rest() enqueues the remainder of a body.  The last body is closed by the tail.
+    template <class Close, class Op, class Rest>
+    int run_self_closing(const Op &upd, uintptr_t align_or, Rest &&rest)
+    {
+        bool first = true;
+        drv.tail = [&]() -> int { return first ? drv.scal(FinCg1Start{}) : drv.scal(Close{}); };
+        const int rc = run_loop([&]() -> int {
+            TRY(first ? drv.vecf(FinCg1Start{}, upd, align_or) : drv.vecf(Close{}, upd, align_or));
+            first = false;
+            return rest();
+        });
+        drv.tail = nullptr;
+        return rc;
     }
 };
 
@@ -491,21 +508,17 @@ static int check_args(const lcg_para &p, int n, const double *m, const double *B
     return 0;
 }
 
-double global_rows(Ctx &c, int n);
-double global_rows_of(Ctx &c, int n, const void *afp, const void *inst);   // comm.hip   // comm.hip: n summed over ranks (n itself when single)
-
-#define TRY(x) do { int rc_ = (x); if (rc_) return rc_; } while (0)
-
 static int solve_cg(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, const double *B, int n,
                     const lcg_para *param, void *inst, double *Gk, double *Dk, double *ADk, int mem)
 {
     const lcg_para p = param ? *param : lcg_hip_default_parameters();
     TRY(check_args(p, n, m, B));
     TRY(ensure_init());
-    Ctx &c = ctx();
-    HostBridge hb; TRY(hb.open(mem, m, B, sizeof(double) * n, c.stream));
-    Workspace ws; double *g, *d, *Ad;
-    TRY(ws.get(g, Gk, sizeof(double) * n)); TRY(ws.get(d, Dk, sizeof(double) * n)); TRY(ws.get(Ad, ADk, sizeof(double) * n));
+    RealSolve k(p, n, inst, Afp, Pfp);
+    Ctx &c = k.c;
+    TRY(k.open(mem, m, B));
+    double *g, *d, *Ad;
+    TRY(k.get(g, Gk)); TRY(k.get(d, Dk)); TRY(k.get(Ad, ADk));
     // AUTO: the one-reduction schedule when the rows are sharded (one all-reduce per iteration) and on one GPU for systems so
     // small that a launch costs more than a word per row (< 2^20 rows): two launches per iteration instead of three
     // (a callback of the caller's own keeps the reference's recurrence and with it the reference's sequence of callback calls:
@@ -513,13 +526,12 @@ static int solve_cg(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, const d
     const bool one_reduction = c.cg_schedule == LCG_HIP_CG_ONE_REDUCTION ||
                                (c.cg_schedule == LCG_HIP_CG_AUTO && (comm_active() || (n < CG1_AUTO_ROWS && Afp == lcg_hip_csr_ax)));
     double *w = nullptr;
-    if (one_reduction) TRY(ws.get(w, nullptr, sizeof(double) * n));
+    if (one_reduction) TRY(k.get(w));
     // roles by weight (driver.hpp: Placement): what the loop's product writes (A.d; w = A.g in the one-reduction arrangement), what it
     // reads, the rest
-    if (one_reduction) TRY(Placement::run(c, n, (const void *)Afp, inst, B, ws, {&w, &g, &d, &Ad}, 1));
-    else TRY(Placement::run(c, n, (const void *)Afp, inst, B, ws, {&Ad, &d, &g}, 1));
-    RealCommon k(c, n, p, inst, Afp, Pfp, m);
-    TRY(k.drv.init_state(global_rows_of(c, n, (const void *)Afp, inst)));
+    if (one_reduction) TRY(k.place(B, {&w, &g, &d, &Ad}, 1));
+    else TRY(k.place(B, {&Ad, &d, &g}, 1));
+    TRY(k.start());
     DevState *st = c.state;
     const bool nt = stream_vectors(n, Afp, inst);      // (n: the rows THIS process holds)
 
@@ -530,76 +542,36 @@ static int solve_cg(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, const d
     if (one_reduction) {
         bool fused; TRY(k.ax_dot(g, w, g, false, 0, &fused));
         if (!fused) TRY(k.drv.vec(OpDot1{st, g, w}, al(g) | al(w)));
-        int rc;
-        // The product that closes a body only serves the NEXT body's step length: the body the iteration cap ends the solve with goes
-        // without it (K iterations = K + 1 products, as in the reference's loop: lcg.cpp:168, 232).
-        // (Its closing step then finds NO partial sums for g.w -- neither the previous body's nor an unwritten table row: the count of
-        //  that row is zero, the sum exactly 0, and the a_k, b_k the step leaves behind are a fixed function of the state; nothing
-        //  reads them after the cap.)
-        auto last_body = [&]() {
-            const bool last = p.max_iterations > 0 && k.drv.enq + 1 >= p.max_iterations;
-            if (last) { k.drv.pcnt.ax_n = 0; k.drv.pcnt.ax_row = -1; k.drv.pcnt.g[2] = 0; }
-            return last;
+        const OpCg1UpdateSums upd{st, m, g, d, Ad, w, 0.0, 0.0, nt};
+        auto product = [&]() -> int {       // w = A g carrying g.w as sum 2 (or a pass of its own where the product never could)
+            bool f; TRY(k.ax_dot(g, w, g, false, 2, &f));   // (a product that cannot carry the sum is made all the same)
+            if (f) return 0;
+            if (fused) { c.err = "A.x stopped carrying its dot in the middle of a solve"; return LCG_HIP_E_ARG; }
+            return k.drv.vec_rows(OpDot1{st, g, w}, 2, al(g) | al(w));
         };
-        if (fused && Pfp == nullptr && !comm_active()) {
-            // The product carries g.w, the update pass the other sums of the body: a body is TWO launches, `[step] update + sums |
-            // A.g + g.w`; the scalar step that closes body k rides in the update of body k+1, the last one is closed by the tail.
-            bool first = true;
-            k.drv.tail = [&]() -> int { return first ? k.drv.scal(FinCg1Start{}) : k.drv.scal(FinCg1Close{}); };
-            rc = k.run_loop([&]() -> int {
-                if (first) { TRY(k.drv.vecf(FinCg1Start{}, OpCg1UpdateSums{st, m, g, d, Ad, w, 0.0, 0.0, nt}, a_upd | al(w))); first = false; }
-                else TRY(k.drv.vecf(FinCg1Close{}, OpCg1UpdateSums{st, m, g, d, Ad, w, 0.0, 0.0, nt}, a_upd | al(w)));
-                if (last_body()) return 0;
-                bool f; TRY(k.ax_dot(g, w, g, false, 2, &f));
-                if (!f) { c.err = "A.x stopped carrying its dot in the middle of a solve"; return LCG_HIP_E_ARG; }
-                return 0;
-            });
-            k.drv.tail = nullptr;
-        } else if (fused) {
-            // with a progress callback the state is read after every body: the same passes with the scalar step as its own
-            // kernel at the end of the body (the same arithmetic: bit-identical iterates).  Sharded rows take this form too: the step
-            // is where the ranks' sums meet (update + m.m, g.g, NaN | product, pushes, remote part + g.w | reduce, exchange, step)
-            TRY(k.drv.scal(FinCg1Start{}));
-            rc = k.run_loop([&]() -> int {
-                TRY(k.drv.vec(OpCg1UpdateSums{st, m, g, d, Ad, w, 0.0, 0.0, nt}, a_upd | al(w)));
-                if (!last_body()) {
-                    bool f; TRY(k.ax_dot(g, w, g, false, 2, &f));
-                    if (!f) { c.err = "A.x stopped carrying its dot in the middle of a solve"; return LCG_HIP_E_ARG; }
-                }
-                TRY(k.drv.scal(FinCg1Close{}));
-                return 0;
-            });
-        } else if (Pfp == nullptr && !comm_active()) {
-            // One GPU, no progress callback: the scalar step that closes body k rides in the first pass of body k+1
-            // (FinCg1Start in front of the first one), so a body is three launches: update | A.g | dots.  The last body is
-            // closed by the tail.  Same arithmetic in the same order as the four-launch form below.
-            bool first = true;
-            k.drv.tail = [&]() -> int { return first ? k.drv.scal(FinCg1Start{}) : k.drv.scal(FinCg1Close{}); };
-            rc = k.run_loop([&]() -> int {
-                if (first) { TRY(k.drv.vecf(FinCg1Start{}, OpCg1UpdateSums{st, m, g, d, Ad, w, 0.0, 0.0, nt}, a_upd | al(w))); first = false; }
-                else TRY(k.drv.vecf(FinCg1Close{}, OpCg1UpdateSums{st, m, g, d, Ad, w, 0.0, 0.0, nt}, a_upd | al(w)));
-                if (last_body()) return 0;
+        int rc;
+        if (Pfp == nullptr && !comm_active()) {
+            // Where the product carries g.w, the update pass the other sums of the body, a body is TWO launches: `[step] update + sums
+            // | A.g + g.w`; else three: update | A.g | dots (same arithmetic in the same order as the four-launch form below)
+            rc = k.run_self_closing<FinCg1Close>(upd, a_upd | al(w), [&]() -> int {
+                if (k.last_body(2)) return 0;
+                if (fused) return product();
                 TRY(k.ax(g, w));
-                TRY(k.drv.vec_rows(OpDot1{st, g, w}, 2, al(g) | al(w)));
-                return 0;
+                return k.drv.vec_rows(OpDot1{st, g, w}, 2, al(g) | al(w));
             });
-            k.drv.tail = nullptr;
         } else {
-            // sharded rows (and callbacks that are not the built-in product): m.m, g.g and the NaN count ride in the update pass,
-            // which has m and g in registers anyway; the pass after the product only takes g.w (two words per row instead of three)
+            // With a progress callback the state is read after every body: the same passes with the scalar step as its own kernel at
+            // the end of the body (the same arithmetic: bit-identical iterates).  Sharded rows take this form too: the step is where the
+            // ranks' sums meet (update + m.m, g.g, NaN | product, pushes, remote part + g.w | reduce, exchange, step).  m.m, g.g and
+            // the NaN count ride in the update pass, which has m and g in registers anyway.
             TRY(k.drv.scal(FinCg1Start{}));
             rc = k.run_loop([&]() -> int {
-                TRY(k.drv.vec(OpCg1UpdateSums{st, m, g, d, Ad, w, 0.0, 0.0, nt}, a_upd | al(w)));
-                if (!last_body()) {
-                    bool f; TRY(k.ax_dot(g, w, g, false, 2, &f));   // (a product that cannot carry the sum is made all the same)
-                    if (!f) TRY(k.drv.vec_rows(OpDot1{st, g, w}, 2, al(g) | al(w)));
-                }
-                TRY(k.drv.scal(FinCg1Close{}));
-                return 0;
+                TRY(k.drv.vec(upd, a_upd | al(w)));
+                if (!k.last_body(2)) TRY(product());
+                return k.drv.scal(FinCg1Close{});
             });
         }
-        int rc2 = hb.close(c.stream);
-        return rc <= -2000 ? rc : (rc2 ? rc2 : rc);
+        return k.finish(rc);
     }
     int rc = k.run_loop([&]() -> int {
         bool f; TRY(k.ax_dot(d, Ad, d, false, 0, &f));                          // :232
@@ -608,8 +580,7 @@ static int solve_cg(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, const d
         TRY(k.drv.vecf(FinClose<false>{}, OpCgDir{st, d, g, 0.0, nt}, al(d) | al(g)));   // :244-257, :259-263
         return 0;
     });
-    int rc2 = hb.close(c.stream);
-    return rc <= -2000 ? rc : (rc2 ? rc2 : rc);
+    return k.finish(rc);
 }
 
 static int solve_pcg(lcg_axfunc_ptr Afp, lcg_axfunc_ptr Mfp, lcg_progress_ptr Pfp, double *m, const double *B,
@@ -619,23 +590,17 @@ static int solve_pcg(lcg_axfunc_ptr Afp, lcg_axfunc_ptr Mfp, lcg_progress_ptr Pf
     TRY(check_args(p, n, m, B));
     if (Mfp == nullptr) return LCG_NULL_PRECONDITION_MATRIX;
     TRY(ensure_init());
-    Ctx &c = ctx();
-    HostBridge hb; TRY(hb.open(mem, m, B, sizeof(double) * n, c.stream));
-    Workspace ws; double *r, *z, *d, *Ad;
-    TRY(ws.get(r, nullptr, sizeof(double) * n)); TRY(ws.get(z, nullptr, sizeof(double) * n));
-    TRY(ws.get(d, nullptr, sizeof(double) * n)); TRY(ws.get(Ad, nullptr, sizeof(double) * n));
-    TRY(Placement::run(c, n, (const void *)Afp, inst, B, ws, {&Ad, &d, &r, &z}, 1));      // (roles by weight: A.d, the product's x, the rest)
-    RealCommon k(c, n, p, inst, Afp, Pfp, m);
-    TRY(k.drv.init_state(global_rows_of(c, n, (const void *)Afp, inst)));
+    RealSolve k(p, n, inst, Afp, Pfp);
+    Ctx &c = k.c;
+    TRY(k.open(mem, m, B));
+    double *r, *z, *d, *Ad;
+    TRY(k.get(r)); TRY(k.get(z)); TRY(k.get(d)); TRY(k.get(Ad));
+    TRY(k.place(B, {&Ad, &d, &r, &z}, 1));      // (roles by weight: A.d, the product's x, the rest)
+    TRY(k.start());
     DevState *st = c.state;
     const bool nt = stream_vectors(n, Afp, inst);      // (n: the rows THIS process holds)
-    // built-in Jacobi on a handle that owns its reciprocal diagonal: fold M^-1 into the update
-    const double *invdiag = nullptr;
     if (Mfp != lcg_hip_jacobi_mx) k.drv.user_cb = true;
-    if (Mfp == lcg_hip_jacobi_mx && inst) {
-        const lcg_hip_csr *A = static_cast<const lcg_hip_csr *>(inst);
-        if (!A->is_complex && A->n_rows == n) invdiag = A->invdiag;
-    }
+    const double *invdiag = builtin_invdiag((const void *)Mfp, inst, n, false);
 
     TRY(k.ax_setup(m, Ad));                                                      // lcg.cpp:314
     TRY(k.drv.vec(OpResidual{st, Ad, B, r, Ad}, al(Ad) | al(B) | al(r)));        // :317-321
@@ -647,7 +612,7 @@ static int solve_pcg(lcg_axfunc_ptr Afp, lcg_axfunc_ptr Mfp, lcg_progress_ptr Pf
                                (c.cg_schedule == LCG_HIP_CG_ONE_REDUCTION ||
                                 (c.cg_schedule == LCG_HIP_CG_AUTO && (comm_active() || (n < CG1_AUTO_ROWS && !k.drv.user_cb))));
     if (one_reduction) {
-        double *w; TRY(ws.get(w, nullptr, sizeof(double) * n));
+        double *w; TRY(k.get(w));
         {   // w = A u_0 and w.u_0 (sum 0): a_0 = u.r / w.u, b_0 = 0
             bool f; TRY(k.ax_dot(z, w, z, false, 0, &f));
             if (!f) TRY(k.drv.vec(OpDot1{st, z, w}, al(z) | al(w)));
@@ -657,37 +622,22 @@ static int solve_pcg(lcg_axfunc_ptr Afp, lcg_axfunc_ptr Mfp, lcg_progress_ptr Pf
             if (!f) TRY(k.drv.vec_rows(OpDot1{st, z, w}, 4, al(z) | al(w)));
             return 0;
         };
-        auto last_body = [&]() {       // (as in solve_cg: the capped body's closing step finds an empty row for w.u, not a stale one)
-            const bool last = p.max_iterations > 0 && k.drv.enq + 1 >= p.max_iterations;
-            if (last) { k.drv.pcnt.ax_n = 0; k.drv.pcnt.ax_row = -1; k.drv.pcnt.g[4] = 0; }
-            return last;
-        };
         const OpPcg1UpdateSums upd{st, m, r, z, d, Ad, w, invdiag, 0.0, 0.0};
         int rc;
         if (Pfp == nullptr && !comm_active()) {
-            // the step that closes body k rides in the update of body k + 1 (FinCg1Start -- a_0, b_0 -- in front of the first): TWO
-            // launches per body; the last body is closed by the tail
-            bool first = true;
-            k.drv.tail = [&]() -> int { return first ? k.drv.scal(FinCg1Start{}) : k.drv.scal(FinPcg1Close{}); };
-            rc = k.run_loop([&]() -> int {
-                if (first) { TRY(k.drv.vecf(FinCg1Start{}, upd, a_all | al(w))); first = false; }
-                else TRY(k.drv.vecf(FinPcg1Close{}, upd, a_all | al(w)));
-                if (last_body()) return 0;
-                return product();
-            });
-            k.drv.tail = nullptr;
+            // TWO launches per body
+            rc = k.run_self_closing<FinPcg1Close>(upd, a_all | al(w), [&]() -> int { return k.last_body(4) ? 0 : product(); });
         } else {
             // progress callback (the state is read after every body) or sharded rows (the step is where the ranks' sums meet)
             TRY(k.drv.scal(FinCg1Start{}));
             rc = k.run_loop([&]() -> int {
                 TRY(k.drv.vec(upd, a_all | al(w)));
-                if (!last_body()) TRY(product());
+                if (!k.last_body(4)) TRY(product());
                 TRY(k.drv.scal(FinPcg1Close{}));
                 return 0;
             });
         }
-        int rc2 = hb.close(c.stream);
-        return rc <= -2000 ? rc : (rc2 ? rc2 : rc);
+        return k.finish(rc);
     }
     int rc = k.run_loop([&]() -> int {
         bool f; TRY(k.ax_dot(d, Ad, d, false, 0, &f));                          // :387
@@ -702,8 +652,7 @@ static int solve_pcg(lcg_axfunc_ptr Afp, lcg_axfunc_ptr Mfp, lcg_progress_ptr Pf
         TRY(k.drv.vecf(FinClose<false>{}, OpPcgDir{st, d, z, 0.0, nt && invdiag != nullptr}, al(d) | al(z)));  // :415-416, :418-422
         return 0;
     });
-    int rc2 = hb.close(c.stream);
-    return rc <= -2000 ? rc : (rc2 ? rc2 : rc);
+    return k.finish(rc);
 }
 
 static int solve_cgs(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, const double *B, int n,
@@ -713,16 +662,14 @@ static int solve_cgs(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, const 
     const lcg_para p = param ? *param : lcg_hip_default_parameters();
     TRY(check_args(p, n, m, B));
     TRY(ensure_init());
-    Ctx &c = ctx();
-    HostBridge hb; TRY(hb.open(mem, m, B, sizeof(double) * n, c.stream));
-    Workspace ws; double *r, *r0, *pk, *Ax, *u, *q, *w;
-    const size_t nb = sizeof(double) * n;
-    TRY(ws.get(r, RK, nb)); TRY(ws.get(r0, R0T, nb)); TRY(ws.get(pk, PK, nb)); TRY(ws.get(Ax, AX, nb));
-    TRY(ws.get(u, UK, nb)); TRY(ws.get(q, QK, nb)); TRY(ws.get(w, WK, nb));
-    TRY(Placement::run(c, n, (const void *)Afp, inst, B, ws, {&Ax, &pk, &w, &u, &q, &r, &r0}, 1));        // (both products write Ax; they read p and w)
-    RealCommon k(c, n, p, inst, Afp, Pfp, m);
-    TRY(k.drv.init_state(global_rows_of(c, n, (const void *)Afp, inst)));
-    DevState *st = c.state;
+    RealSolve k(p, n, inst, Afp, Pfp);
+    TRY(k.open(mem, m, B));
+    double *r, *r0, *pk, *Ax, *u, *q, *w;
+    TRY(k.get(r, RK)); TRY(k.get(r0, R0T)); TRY(k.get(pk, PK)); TRY(k.get(Ax, AX));
+    TRY(k.get(u, UK)); TRY(k.get(q, QK)); TRY(k.get(w, WK));
+    TRY(k.place(B, {&Ax, &pk, &w, &u, &q, &r, &r0}, 1));        // (both products write Ax; they read p and w)
+    TRY(k.start());
+    DevState *st = k.c.state;
     const bool nt = stream_vectors(n, Afp, inst);      // (n: the rows THIS process holds)
     const uintptr_t a_all = al(m) | al(B) | al(r) | al(r0) | al(pk) | al(Ax) | al(u) | al(q) | al(w);
 
@@ -738,8 +685,7 @@ static int solve_cgs(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, const 
         TRY(k.drv.vecf(FinClose<false>{}, OpCgsDir{st, u, pk, r, q, 0.0, nt}, a_all));   // :589-590, :593-597
         return 0;
     });
-    int rc2 = hb.close(c.stream);
-    return rc <= -2000 ? rc : (rc2 ? rc2 : rc);
+    return k.finish(rc);
 }
 
 static int solve_bicgstab(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, const double *B, int n,
@@ -748,16 +694,13 @@ static int solve_bicgstab(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, c
     const lcg_para p = param ? *param : lcg_hip_default_parameters();
     TRY(check_args(p, n, m, B));
     TRY(ensure_init());
-    Ctx &c = ctx();
-    HostBridge hb; TRY(hb.open(mem, m, B, sizeof(double) * n, c.stream));
-    Workspace ws; double *r, *r0, *pk, *Ax, *s, *Ap;
-    const size_t nb = sizeof(double) * n;
-    TRY(ws.get(r, nullptr, nb)); TRY(ws.get(r0, nullptr, nb)); TRY(ws.get(pk, nullptr, nb));
-    TRY(ws.get(Ax, nullptr, nb)); TRY(ws.get(s, nullptr, nb)); TRY(ws.get(Ap, nullptr, nb));
-    TRY(Placement::run(c, n, (const void *)Afp, inst, B, ws, {&Ap, &Ax, &pk, &s, &r, &r0}, 2));           // (A.p and A.s; p and s are read)
-    RealCommon k(c, n, p, inst, Afp, Pfp, m);
-    TRY(k.drv.init_state(global_rows_of(c, n, (const void *)Afp, inst)));
-    DevState *st = c.state;
+    RealSolve k(p, n, inst, Afp, Pfp);
+    TRY(k.open(mem, m, B));
+    double *r, *r0, *pk, *Ax, *s, *Ap;
+    TRY(k.get(r)); TRY(k.get(r0)); TRY(k.get(pk)); TRY(k.get(Ax)); TRY(k.get(s)); TRY(k.get(Ap));
+    TRY(k.place(B, {&Ap, &Ax, &pk, &s, &r, &r0}, 2));           // (A.p and A.s; p and s are read)
+    TRY(k.start());
+    DevState *st = k.c.state;
     const bool nt = stream_vectors(n, Afp, inst);      // (n: the rows THIS process holds)
     const uintptr_t a_all = al(m) | al(B) | al(r) | al(r0) | al(pk) | al(Ax) | al(s) | al(Ap);
 
@@ -774,8 +717,7 @@ static int solve_bicgstab(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, c
         TRY(k.drv.vecf(FinClose<true>{}, OpBicgDir{st, pk, r, Ap, 0.0, 0.0, nt}, a_all));          // :773-774, :776-780
         return 0;
     });
-    int rc2 = hb.close(c.stream);
-    return rc <= -2000 ? rc : (rc2 ? rc2 : rc);
+    return k.finish(rc);
 }
 
 // ---- BiCGStab with restart (lcg.cpp:812-1034) ---------------------------------------------------
@@ -891,16 +833,13 @@ static int solve_bicgstab2(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, 
     if (p.restart_epsilon <= 0.0 || p.epsilon >= 1.0) return LCG_INVILAD_RESTART_EPSILON;
     if (m == nullptr || B == nullptr) return LCG_INVALID_POINTER;
     TRY(ensure_init());
-    Ctx &c = ctx();
-    HostBridge hb; TRY(hb.open(mem, m, B, sizeof(double) * n, c.stream));
-    Workspace ws; double *r, *r0, *pk, *Ax, *s, *Ap;
-    const size_t nb = sizeof(double) * n;
-    TRY(ws.get(r, nullptr, nb)); TRY(ws.get(r0, nullptr, nb)); TRY(ws.get(pk, nullptr, nb));
-    TRY(ws.get(Ax, nullptr, nb)); TRY(ws.get(s, nullptr, nb)); TRY(ws.get(Ap, nullptr, nb));
-    TRY(Placement::run(c, n, (const void *)Afp, inst, B, ws, {&Ap, &Ax, &pk, &s, &r, &r0}, 2));           // (A.p and A.s; p and s are read)
-    RealCommon k(c, n, p, inst, Afp, Pfp, m);
-    TRY(k.drv.init_state(global_rows_of(c, n, (const void *)Afp, inst)));
-    DevState *st = c.state;
+    RealSolve k(p, n, inst, Afp, Pfp);
+    TRY(k.open(mem, m, B));
+    double *r, *r0, *pk, *Ax, *s, *Ap;
+    TRY(k.get(r)); TRY(k.get(r0)); TRY(k.get(pk)); TRY(k.get(Ax)); TRY(k.get(s)); TRY(k.get(Ap));
+    TRY(k.place(B, {&Ap, &Ax, &pk, &s, &r, &r0}, 2));           // (A.p and A.s; p and s are read)
+    TRY(k.start());
+    DevState *st = k.c.state;
     const uintptr_t a_all = al(m) | al(B) | al(r) | al(r0) | al(pk) | al(Ax) | al(s) | al(Ap);
     const int halves = p.abs_diff ? 1 : 0;
 
@@ -937,8 +876,7 @@ static int solve_bicgstab2(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, 
         DevState h; TRY(k.drv.read_state(h));
         if (h.status == ST_NAN) rc = LCG_NAN_VALUE;
     }
-    int rc2 = hb.close(c.stream);
-    return rc <= -2000 ? rc : (rc2 ? rc2 : rc);
+    return k.finish(rc);
 }
 
 } // namespace lcgh
