@@ -1273,16 +1273,137 @@ static bool long_rows_packed()
     return on;
 }
 
+// What one part's A.x runs (ax_choose below): the kernel family and its template arguments
+enum class Ax { none, long_rows, ranges, binned, tiled, run1, ldsp, ldsp_long, lds1, ldsw, wave };
+enum class AxAsk { product, dot, part_dot };        // who asks: spmv_dispatch, csr_ax_dot, csr_part_ax_dot
+struct AxChoice {
+    Ax family = Ax::none;
+    int R = 0, T = 0;               // rows per block (the LDS-staged families), lanes per row (k_spmv_wave)
+    int ns = 0, bits = 0, win = 0;  // k_spmv_ldsp: gathers per lane in the first batch, bits per column; LDS window (+ k_spmv_lds1)
+    bool onewin = false;            // every block's slice fits the largest window
+};
+
+// f(std::integral_constant<int, V>()) for the V of Vs that equals v (false: none does).  Only the listed values are instantiated:
+// the lists below name exactly the template arguments their kernels are built for.
+template <int... Vs, class F> static bool pick(int v, F &&f) { return ((v == Vs ? (f(std::integral_constant<int, Vs>()), true) : false) || ...); }
+
+// k_spmv_ldsp's gathers per lane in its first batch (NS): the smallest instantiated one that covers the longest row.
+// Blocks of 64 rows: enough for the longest row when that is 9..12 per lane.
+// Long rows (a block of 64 does not fit the window): blocks of 32 / 16 rows, 8 / 16 lanes per row, packed columns only.
+// ONE predicated batch of NS gathers per lane, NS the smallest of the instantiated ones that covers the longest row
+// (nine where the rows are longer still: the loop takes the rest) -- every gather beyond a lane's entries is a wasted
+// instruction, and with nine for all the packed form was no faster than the plain one.
+static int ldsp_ns(const CsrPart &P, int R)
+{
+    const int per_lane = (P.pk_maxrow + VB / R - 1) / (VB / R);
+    if (R == 32) return per_lane <= 7 ? 7 : 9;
+    if (R == 16) return per_lane <= 6 ? 6 : 9;
+    return per_lane <= 6 ? 6 : per_lane <= 7 ? 7 : per_lane <= 8 ? 8 : per_lane <= 9 ? 9 : per_lane <= 10 ? 10 : per_lane <= 12 ? 12 : 8;
+}
+
+// k_spmv_ldsp as a choice asks for it.  Instances: 64 rows per block with every NS of ldsp_ns, pushing or not, carrying the dot or
+// not; long rows (RR = 32 / 16) neither pushing nor carrying the dot.
+template <bool PUSH, bool DOT, int RR = PK_R>
+static void ldsp_launch(const AxChoice &c, const CsrPart &P, const double *x, double *y, hipStream_t s, const int *done,
+                        const PushPlan &pp, const DotPlan &dp)
+{
+    const unsigned g = (unsigned)((P.n_rows + RR - 1) / RR) + (PUSH ? (unsigned)(pp.nblocks + pp.nrecv) : 0u);
+    const auto go = [&](auto ns) {
+        pick<18, 21>(c.bits, [&](auto bits) {
+            pick<PK_CH_8, PK_CH_7, PK_CH_SMALL, LdsCfg<double>::CH>(c.win, [&](auto win) {
+                hipLaunchKernelGGL((k_spmv_ldsp<PUSH, decltype(ns)::value, decltype(bits)::value, DOT, decltype(win)::value, RR>), dim3(g),
+                                   dim3(VB), 0, s, P.n_rows, P.rowptr, static_cast<const v4i *>(P.pk_data), P.pk_ofs, P.pk_base, P.val,
+                                   x, y, done, pp, dp);
+            });
+        });
+    };
+    if constexpr (RR == PK_R) pick<6, 7, 8, 9, 10, 12>(c.ns, go);
+    else if constexpr (RR == 32) pick<7, 9>(c.ns, go);
+    else pick<6, 9>(c.ns, go);
+}
+
+// (A/B runs) LCG_HIP_RUN1=0: no k_spmv_run1 / run1d; LCG_HIP_AX_DOT_PACKED=0: k_spmv_ldsp keeps the dot as a pass of its own
+static bool run1_off() { static const bool off = [] { const char *e = lab_env("LCG_HIP_RUN1"); return e && atoi(e) == 0; }(); return off; }
+static bool ax_dot_packed_off() { static const bool off = [] { const char *e = lab_env("LCG_HIP_AX_DOT_PACKED"); return e && atoi(e) == 0; }(); return off; }
+
+// The kernel a part's A.x takes: DESIGN 3.6's rules in order, the first that holds decides.  `push`: a shard's pushing blocks ride
+// in front.  The dot askers then map the choice to the dot forms they take (csr_ax_dot, part_dot_launch); anything else: no dot.
+// The plans below are built by the first call that consults them and are fixed from then on, so each is consulted under the same
+// conditions and in the same order as always -- these accidents included (kept on purpose):
+//  - packed_build is one-shot: the first of runs-only (R = 256 / 128, run1) and full (packed_ready: R = 64 or 32 / 16) fixes
+//    pk_state.  So are the slice scan of lds_shape (slice_R), ranges_chosen, binned_chosen, tiled_chosen (and ensure_dot_part).
+//  - a part's dot consults neither lr_mode nor ranges, nor tries run1 or the long-row packed form; with pushing blocks neither it
+//    nor the product consults binned: tiled is tried directly.  The single-GPU dot does not consult lr_mode.
+//  - the dot askers leave at > 160 entries per row or misaligned arrays before binned, and where a slice exceeds the window
+//    before packed_build.  LCG_HIP_AX_DOT_PACKED=0 stops a part's dot before packed_ready, the single-GPU dot after it.
+//  - plain k_spmv_run1 takes rows of up to 30 entries, its dot form run1d up to 15 (csr_ax_dot).
+//  - plain k_spmv_lds1 takes a smaller window only if real, not accumulating, one-window and >= 2^22 entries; lds1d never.
+//  - long-row packed blocks, windowed, wave, binned, ranges and complex matrices never carry the dot.
+// Nothing is cached across calls (set_kernel, set_packed and ranges_free would have to invalidate it).
+template <class V, bool ACC>
+static int ax_choose(const CsrPart &P, int variant, double mean_row, bool push, AxAsk ask, hipStream_t s, AxChoice &c)
+{
+    c = AxChoice();
+    const bool dot = ask != AxAsk::product;
+    const bool automatic = variant == 0 || variant == -1;
+    if (P.n_rows <= 0 || (dot && !automatic)) return 0;
+    const bool al16 = (((uintptr_t)P.val | (uintptr_t)P.col) & 15) == 0;
+    const bool whole = !push && ask != AxAsk::part_dot;      // a whole matrix (or one of its ranges), not a shard's part
+    if constexpr (sizeof(V) == 8 && !ACC) {
+        if (ask == AxAsk::product && whole && P.lr_mode == 1) { c.family = Ax::long_rows; return 0; }    // a range of long rows (ranges_chosen, class 3)
+        if (whole && automatic && ranges_chosen(P, s)) { c.family = Ax::ranges; return 0; }
+        if (dot && (mean_row > 160.0 || !al16)) return 0;
+        if (!push && automatic && binned_chosen(P, s)) { c.family = Ax::binned; return 0; }
+        if (automatic && tiled_chosen(P, s)) { c.family = Ax::tiled; return 0; }
+    }
+    if (variant == 0) variant = (!al16 || mean_row > 160.0) ? (mean_row > 48 ? 64 : (mean_row > 24 ? 32 : (mean_row > 12 ? 16 : 8))) : -1;
+    if (variant > 0) { c.family = Ax::wave; c.T = variant; return 0; }
+    if (!al16) return fail(hipErrorInvalidValue, "LDS-staged A.x needs 16-byte aligned col/val", __FILE__, __LINE__);
+    { int rc = lds_shape<V>(P, variant, mean_row, s, &c.R, &c.onewin); if (rc) return rc; }
+    const int R = c.R;
+    c.family = c.onewin ? Ax::lds1 : Ax::ldsw;
+    c.win = LdsCfg<V>::CH;
+    if constexpr (sizeof(V) == 8 && !ACC) {
+        if (dot && (!c.onewin || (ask == AxAsk::part_dot && ax_dot_packed_off()))) return 0;
+        // short rows whose blocks of 64 are mostly runs: one wavefront per block, no staging (k_spmv_run1)
+        // (its wavefront-private LDS is dynamic: 4 wavefronts x 64 rows x LP doubles must stay within the 64 KB a launch
+        //  may ask for without further ado -- rows of up to 30 entries)
+        if (whole && !run1_off() && variant == -1 && (R == 256 || R == 128) && packed_build(P, s, true) && P.pk_maxrow <= 30) { c.family = Ax::run1; return 0; }
+        if ((R == PK_R && c.onewin && packed_ready(P, s)) ||
+            (whole && (R == 32 || R == 16) && c.onewin && long_rows_packed() && packed_ready(P, s, R))) {     // (long rows: ldsp_ns)
+            c.family = R == PK_R ? Ax::ldsp : Ax::ldsp_long; c.ns = ldsp_ns(P, R); c.bits = P.pk_bits;
+            c.win = pk_window(P.max_slice);                 // the smallest LDS window every block fits: more workgroups per CU
+            return 0;
+        }
+        // (real matrices, large enough for the memory system to matter: the smallest LDS window every block fits -- 27-point stencil
+        //  x 3 unknowns, 16 rows of 81 entries per block: 625 us with five workgroups per CU -> see DESIGN 3.1)
+        if (c.onewin && P.nnz >= (1 << 22)) c.win = pk_window(P.max_slice);
+    }
+    return 0;
+}
+
 template <class V, bool ACC, bool PUSH = false>
 static int spmv_dispatch(const CsrPart &P, int variant, double mean_row, const V *x, V *y, hipStream_t s,
                          const int *done, const PushPlan &pp = PushPlan())
 {
     const int n = P.n_rows;
     const unsigned xb = PUSH ? (unsigned)(pp.nblocks + pp.nrecv) : 0u;       // pushing blocks in front of the grid, receiving blocks behind it
-    if constexpr (sizeof(V) == 8 && !ACC && !PUSH) {
-        if (n > 0 && P.lr_mode == 1)        // a range of long rows (ranges_chosen, class 3)
-            return long_rows_launch(P, reinterpret_cast<const double *>(x), reinterpret_cast<double *>(y), s, done);
-        if (n > 0 && (variant == 0 || variant == -1) && ranges_chosen(P, s)) {
+    const V *val = reinterpret_cast<const V *>(P.val);
+    if (n == 0) {
+        if (PUSH && xb > 0) {       // nothing to multiply, but the neighbours still wait for x and the flags
+            hipLaunchKernelGGL((k_spmv_wave<V, 1, ACC, PUSH>), dim3(xb), dim3(VB), 0, s, 0, P.rowptr, P.col, val, x, y, done, pp);
+            HIPCHK(hipGetLastError());
+        }
+        return 0;
+    }
+    AxChoice c;
+    { int rc = ax_choose<V, ACC>(P, variant, mean_row, PUSH, AxAsk::product, s, c); if (rc) return rc; }
+    if constexpr (sizeof(V) == 8 && !ACC) {
+        const double *xd = reinterpret_cast<const double *>(x);
+        double *yd = reinterpret_cast<double *>(y);
+        switch (c.family) {
+        case Ax::long_rows: return long_rows_launch(P, xd, yd, s, done);
+        case Ax::ranges: {
             RangePlan *R = static_cast<RangePlan *>(P.rg_plan);
             bool changed = false;
             for (size_t i = 0; i < R->parts.size(); i++) {
@@ -1302,154 +1423,68 @@ static int spmv_dispatch(const CsrPart &P, int variant, double mean_row, const V
             P.last_kernel = R->desc.c_str();
             return 0;
         }
-        if (n > 0 && (variant == 0 || variant == -1) && binned_chosen(P, s)) {
+        case Ax::binned:
             P.last_kernel = "k_bin_expand + k_bin_reduce (two-pass binned product, x and row sums in LDS)";
-            return binned_launch(P, reinterpret_cast<const double *>(x), reinterpret_cast<double *>(y), s, done);
-        }
-        if (n > 0 && (variant == 0 || variant == -1) && tiled_chosen(P, s)) {
-            P.last_kernel = "k_tile_spmv (one-pass tiled product: x tiles and row sums in LDS)";
-            return tiled_launch(P, reinterpret_cast<const double *>(x), reinterpret_cast<double *>(y), s, done);
-        }
-    }
-    if constexpr (sizeof(V) == 8 && !ACC && PUSH) {     // sharded rows, direct exchange: the tiled product carries the pushing blocks too
-        if (n > 0 && (variant == 0 || variant == -1) && tiled_chosen(P, s)) {
-            P.last_kernel = "k_tile_spmv (one-pass tiled product: x tiles and row sums in LDS) + pushing blocks";
-            return tiled_launch(P, reinterpret_cast<const double *>(x), reinterpret_cast<double *>(y), s, done, &pp);
-        }
-    }
-    if (n == 0) {
-        if (PUSH && xb > 0) {       // nothing to multiply, but the neighbours still wait for x and the flags
-            hipLaunchKernelGGL((k_spmv_wave<V, 1, ACC, PUSH>), dim3(xb), dim3(VB), 0, s, 0, P.rowptr, P.col,
-                               reinterpret_cast<const V *>(P.val), x, y, done, pp);
+            return binned_launch(P, xd, yd, s, done);
+        case Ax::tiled:     // (sharded rows, direct exchange: the tiled product carries the pushing blocks too)
+            P.last_kernel = PUSH ? "k_tile_spmv (one-pass tiled product: x tiles and row sums in LDS) + pushing blocks"
+                                 : "k_tile_spmv (one-pass tiled product: x tiles and row sums in LDS)";
+            return tiled_launch(P, xd, yd, s, done, PUSH ? &pp : nullptr);
+        case Ax::run1: {
+            const unsigned g = (unsigned)(((n + 63) / 64 + VB / 64 - 1) / (VB / 64));
+            const int LP = P.pk_maxrow | 1;
+            const size_t lds = sizeof(double) * (VB / 64) * 64 * (size_t)LP;
+            pick<1, 2>(c.R == 256 ? 1 : 2, [&](auto t) {
+                hipLaunchKernelGGL((k_spmv_run1<decltype(t)::value>), dim3(g), dim3(VB), lds, s, n, LP, P.rowptr, P.col, P.val, P.pk_ofs,
+                                   P.pk_base, static_cast<const int *>(P.pk_data), xd, yd, done); });
             HIPCHK(hipGetLastError());
+            P.last_kernel = "k_spmv_run1 (one wavefront per 64-row block, run blocks without staging)";
+            return 0;
         }
-        return 0;
-    }
-    const V *val = reinterpret_cast<const V *>(P.val);
-    const bool al16 = (((uintptr_t)P.val | (uintptr_t)P.col) & 15) == 0;
-    if (variant == 0) {
-        if (!al16 || mean_row > 160.0) variant = mean_row > 48 ? 64 : (mean_row > 24 ? 32 : (mean_row > 12 ? 16 : 8));
-        else variant = -1;
-    }
-    if (variant < 0) {
-        if (!al16) return fail(hipErrorInvalidValue, "LDS-staged A.x needs 16-byte aligned col/val", __FILE__, __LINE__);
-        int R = 0; bool onewin = false;
-        { int rc = lds_shape<V>(P, variant, mean_row, s, &R, &onewin); if (rc) return rc; }
-        if constexpr (sizeof(V) == 8 && !ACC) {
+        case Ax::ldsp:
+            ldsp_launch<PUSH, false>(c, P, xd, yd, s, done, pp, ldsp_plain_plan());
+            HIPCHK(hipGetLastError());
+            P.last_kernel = ldsp_name(P, false);
+            return 0;
+        case Ax::ldsp_long:
             if constexpr (!PUSH) {
-                // short rows whose blocks of 64 are mostly runs: one wavefront per block, no staging (k_spmv_run1)
-                static const bool run1_off = [] { const char *e = lab_env("LCG_HIP_RUN1"); return e && atoi(e) == 0; }();
-                // (its wavefront-private LDS is dynamic: 4 wavefronts x 64 rows x LP doubles must stay within the 64 KB a launch
-                //  may ask for without further ado -- rows of up to 30 entries)
-                if (!run1_off && variant == -1 && (R == 256 || R == 128) && packed_build(P, s, true) && P.pk_maxrow <= 30) {
-                    const unsigned g = (unsigned)(((n + 63) / 64 + VB / 64 - 1) / (VB / 64));
-                    const int LP = P.pk_maxrow | 1;
-                    const size_t lds = sizeof(double) * (VB / 64) * 64 * (size_t)LP;
-                    if (R == 256)
-                        hipLaunchKernelGGL((k_spmv_run1<1>), dim3(g), dim3(VB), lds, s, n, LP, P.rowptr, P.col, reinterpret_cast<const double *>(val), P.pk_ofs, P.pk_base,
-                                           static_cast<const int *>(P.pk_data), reinterpret_cast<const double *>(x), reinterpret_cast<double *>(y), done);
-                    else
-                        hipLaunchKernelGGL((k_spmv_run1<2>), dim3(g), dim3(VB), lds, s, n, LP, P.rowptr, P.col, reinterpret_cast<const double *>(val), P.pk_ofs, P.pk_base,
-                                           static_cast<const int *>(P.pk_data), reinterpret_cast<const double *>(x), reinterpret_cast<double *>(y), done);
-                    HIPCHK(hipGetLastError());
-                    P.last_kernel = "k_spmv_run1 (one wavefront per 64-row block, run blocks without staging)";
-                    return 0;
-                }
-            }
-            if (R == PK_R && onewin && packed_ready(P, s)) {
-                // gathers per lane in the first batch: enough for the longest row when that is 9..12 per lane
-                const int per_lane = (P.pk_maxrow + VB / PK_R - 1) / (VB / PK_R);
-                const int ns = per_lane <= 6 ? 6 : per_lane <= 7 ? 7 : per_lane <= 8 ? 8 : per_lane <= 9 ? 9 : per_lane <= 10 ? 10 : per_lane <= 12 ? 12 : 8;
-                const int win = pk_window(P.max_slice);             // the smallest LDS window every block fits: more workgroups per CU
-#define PK_LAUNCH(NSS, BB, CC)                                                                                      \
-        hipLaunchKernelGGL((k_spmv_ldsp<PUSH, NSS, BB, false, CC>), dim3((n + PK_R - 1) / PK_R + xb), dim3(VB), 0, s, n, P.rowptr, \
-                           static_cast<const v4i *>(P.pk_data), P.pk_ofs, P.pk_base, reinterpret_cast<const double *>(val), \
-                           reinterpret_cast<const double *>(x), reinterpret_cast<double *>(y), done, pp, ldsp_plain_plan())
-#define PK_CASE(NSS)                                                                                                \
-    case NSS:                                                                                                       \
-        if (win == PK_CH_8) { if (P.pk_bits == 18) PK_LAUNCH(NSS, 18, PK_CH_8); else PK_LAUNCH(NSS, 21, PK_CH_8); } \
-        else if (win == PK_CH_7) { if (P.pk_bits == 18) PK_LAUNCH(NSS, 18, PK_CH_7); else PK_LAUNCH(NSS, 21, PK_CH_7); } \
-        else if (win == PK_CH_SMALL) { if (P.pk_bits == 18) PK_LAUNCH(NSS, 18, PK_CH_SMALL); else PK_LAUNCH(NSS, 21, PK_CH_SMALL); } \
-        else { if (P.pk_bits == 18) PK_LAUNCH(NSS, 18, LdsCfg<double>::CH); else PK_LAUNCH(NSS, 21, LdsCfg<double>::CH); } \
-        break;
-                switch (ns) { PK_CASE(6) PK_CASE(7) PK_CASE(8) PK_CASE(9) PK_CASE(10) PK_CASE(12) }
-#undef PK_LAUNCH
-#undef PK_CASE
+                DotPlan dp = ldsp_plain_plan(); dp.dof = P.pk_dof;
+                (c.R == 32 ? ldsp_launch<false, false, 32> : ldsp_launch<false, false, 16>)(c, P, xd, yd, s, done, PushPlan(), dp);
                 HIPCHK(hipGetLastError());
-                P.last_kernel = ldsp_name(P, false);
+                P.last_kernel = P.pk_dof > 1 ? (P.pk_bits == 18 ? "k_spmv_ldsp (LDS-staged, long rows: one 18-bit packed column per group of consecutive columns)"
+                                                               : "k_spmv_ldsp (LDS-staged, long rows: one 21-bit packed column per group of consecutive columns)")
+                                             : (P.pk_bits == 18 ? "k_spmv_ldsp (LDS-staged, long rows: 18-bit packed columns)" : "k_spmv_ldsp (LDS-staged, long rows: 21-bit packed columns)");
                 return 0;
             }
-            if constexpr (!PUSH) {
-                // long rows (a block of 64 does not fit the window): blocks of 32 / 16 rows, 8 / 16 lanes per row, packed columns only.
-                // ONE predicated batch of NS gathers per lane, NS the smallest of the instantiated ones that covers the longest row
-                // (nine where the rows are longer still: the loop takes the rest) -- every gather beyond a lane's entries is a wasted
-                // instruction, and with nine for all the packed form was no faster than the plain one.
-                if ((R == 32 || R == 16) && onewin && long_rows_packed() && packed_ready(P, s, R)) {
-                    const int T = VB / R;
-                    const int per_lane = (P.pk_maxrow + T - 1) / T;
-                    const int win = pk_window(P.max_slice);
-                    DotPlan pkl_plan = ldsp_plain_plan(); pkl_plan.dof = P.pk_dof;
-#define PKL_LAUNCH(NSS, BB, CC, RRR)                                                                                \
-        hipLaunchKernelGGL((k_spmv_ldsp<false, NSS, BB, false, CC, RRR>), dim3((n + RRR - 1) / RRR), dim3(VB), 0, s, n, P.rowptr, \
-                           static_cast<const v4i *>(P.pk_data), P.pk_ofs, P.pk_base, reinterpret_cast<const double *>(val), \
-                           reinterpret_cast<const double *>(x), reinterpret_cast<double *>(y), done, PushPlan(), pkl_plan)
-#define PKL_WIN(NSS, BB, RRR)                                                                                       \
-        do { if (win == PK_CH_8) PKL_LAUNCH(NSS, BB, PK_CH_8, RRR); else if (win == PK_CH_7) PKL_LAUNCH(NSS, BB, PK_CH_7, RRR);   \
-             else if (win == PK_CH_SMALL) PKL_LAUNCH(NSS, BB, PK_CH_SMALL, RRR); else PKL_LAUNCH(NSS, BB, LdsCfg<double>::CH, RRR); } while (0)
-#define PKL_BITS(NSS, RRR) do { if (P.pk_bits == 18) PKL_WIN(NSS, 18, RRR); else PKL_WIN(NSS, 21, RRR); } while (0)
-                    if (R == 32) { if (per_lane <= 7) PKL_BITS(7, 32); else PKL_BITS(9, 32); }
-                    else { if (per_lane <= 6) PKL_BITS(6, 16); else PKL_BITS(9, 16); }
-#undef PKL_LAUNCH
-#undef PKL_WIN
-#undef PKL_BITS
-                    HIPCHK(hipGetLastError());
-                    P.last_kernel = P.pk_dof > 1 ? (P.pk_bits == 18 ? "k_spmv_ldsp (LDS-staged, long rows: one 18-bit packed column per group of consecutive columns)"
-                                                                   : "k_spmv_ldsp (LDS-staged, long rows: one 21-bit packed column per group of consecutive columns)")
-                                                 : (P.pk_bits == 18 ? "k_spmv_ldsp (LDS-staged, long rows: 18-bit packed columns)" : "k_spmv_ldsp (LDS-staged, long rows: 21-bit packed columns)");
-                    return 0;
-                }
-            }
+            break;
+        default: break;
         }
-        // (real matrices, large enough for the memory system to matter: the smallest LDS window every block fits -- 27-point stencil
-        //  x 3 unknowns, 16 rows of 81 entries per block: 625 us with five workgroups per CU -> see DESIGN 3.1)
-        int win = 0;
-        if constexpr (sizeof(V) == 8 && !ACC) { if (onewin && P.nnz >= (1 << 22)) win = pk_window(P.max_slice); }
-#define LDS1_LAUNCH(RR, CC)                                                                            \
-            hipLaunchKernelGGL((k_spmv_lds1<V, RR, ACC, PUSH, CC>), dim3((n + RR - 1) / RR + xb), dim3(VB), 0, s, n, \
-                               (long)(P.end_abs >= 0 ? P.end_abs : P.nnz), P.rowptr, P.col, val, x, y, done, pp)
-#define LDS_CASE(RR)                                                                                   \
-    case RR:                                                                                           \
-        if (onewin) {                                                                                  \
-            if constexpr (sizeof(V) == 8 && !ACC) {                                                    \
-                if (win == PK_CH_8) LDS1_LAUNCH(RR, PK_CH_8);                                          \
-                else if (win == PK_CH_7) LDS1_LAUNCH(RR, PK_CH_7);                                     \
-                else if (win == PK_CH_SMALL) LDS1_LAUNCH(RR, PK_CH_SMALL);                             \
-                else LDS1_LAUNCH(RR, LdsCfg<V>::CH);                                                   \
-            } else LDS1_LAUNCH(RR, LdsCfg<V>::CH);                                                     \
-        } else                                                                                          \
-            hipLaunchKernelGGL((k_spmv_ldsw<V, RR, ACC, PUSH>), dim3((n + RR - 1) / RR + xb), dim3(VB), 0, s, n, \
-                               (long)(P.end_abs >= 0 ? P.end_abs : P.nnz), P.rowptr, P.col, val, x, y, done, pp); \
-        break;
-        switch (R) {
-            LDS_CASE(256) LDS_CASE(128) LDS_CASE(64) LDS_CASE(32) LDS_CASE(16)
-        default: return fail(hipErrorInvalidValue, "bad LDS A.x rows-per-block", __FILE__, __LINE__);
-        }
-#undef LDS_CASE
-#undef LDS1_LAUNCH
-        P.last_kernel = onewin ? "k_spmv_lds1 (LDS-staged CSR)" : "k_spmv_ldsw (LDS-staged CSR, windowed)";
-    } else {
-#define WAVE_CASE(TT)                                                                                  \
-    case TT: {                                                                                         \
-        const long threads = (long)n * TT;                                                             \
-        hipLaunchKernelGGL((k_spmv_wave<V, TT, ACC, PUSH>), dim3((unsigned)((threads + VB - 1) / VB) + xb), dim3(VB), 0, s, \
-                           n, P.rowptr, P.col, val, x, y, done, pp);                                   \
-    } break;
-        switch (variant) {
-            WAVE_CASE(1) WAVE_CASE(2) WAVE_CASE(4) WAVE_CASE(8) WAVE_CASE(16) WAVE_CASE(32) WAVE_CASE(64)
-        default: return fail(hipErrorInvalidValue, "bad A.x lanes-per-row", __FILE__, __LINE__);
-        }
-#undef WAVE_CASE
+    }
+    if (c.family == Ax::wave) {
+        const bool ok = pick<1, 2, 4, 8, 16, 32, 64>(c.T, [&](auto T) {
+            constexpr int TT = decltype(T)::value;
+            hipLaunchKernelGGL((k_spmv_wave<V, TT, ACC, PUSH>), dim3((unsigned)(((long)n * TT + VB - 1) / VB) + xb), dim3(VB), 0, s,
+                               n, P.rowptr, P.col, val, x, y, done, pp);
+        });
+        if (!ok) return fail(hipErrorInvalidValue, "bad A.x lanes-per-row", __FILE__, __LINE__);
         P.last_kernel = "k_spmv_wave (lanes per row, shuffle reduction)";
+    } else {
+        const long nnz = P.end_abs >= 0 ? P.end_abs : P.nnz;
+        const bool ok = pick<256, 128, 64, 32, 16>(c.R, [&](auto R) {
+            constexpr int RR = decltype(R)::value;
+            const dim3 g((n + RR - 1) / RR + xb);
+            if (!c.onewin)
+                hipLaunchKernelGGL((k_spmv_ldsw<V, RR, ACC, PUSH>), g, dim3(VB), 0, s, n, nnz, P.rowptr, P.col, val, x, y, done, pp);
+            else if constexpr (sizeof(V) == 8 && !ACC)
+                pick<PK_CH_8, PK_CH_7, PK_CH_SMALL, LdsCfg<double>::CH>(c.win, [&](auto win) {
+                    hipLaunchKernelGGL((k_spmv_lds1<V, RR, ACC, PUSH, decltype(win)::value>), g, dim3(VB), 0, s, n, nnz, P.rowptr, P.col,
+                                       val, x, y, done, pp);
+                });
+            else
+                hipLaunchKernelGGL((k_spmv_lds1<V, RR, ACC, PUSH>), g, dim3(VB), 0, s, n, nnz, P.rowptr, P.col, val, x, y, done, pp);
+        });
+        if (!ok) return fail(hipErrorInvalidValue, "bad LDS A.x rows-per-block", __FILE__, __LINE__);
+        P.last_kernel = c.onewin ? "k_spmv_lds1 (LDS-staged CSR)" : "k_spmv_ldsw (LDS-staged CSR, windowed)";
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -1492,79 +1527,49 @@ static bool ensure_dot_part(const CsrPart &P, long count)
     return true;
 }
 
-int csr_part_ax_dot(const CsrPart &P, int variant, double mean_row, const double *x, double *y, const double *u, int yy, double *part,
-                    int *slots, hipStream_t s, const int *done, const PushPlan *pp, int *nofold)
+// the dot forms a part's own buffer takes: the tiled product or k_spmv_ldsp<DOT>, as chosen
+static int part_dot_launch(const CsrPart &P, const AxChoice &c, const double *x, double *y, const double *u, int yy, double *part,
+                           int *slots, hipStream_t s, const int *done, const PushPlan *pp, int *nofold)
 {
-    const int n = P.n_rows;
-    if (n <= 0 || (variant != 0 && variant != -1)) return 0;
-    if (mean_row > 160.0 || ((((uintptr_t)P.val | (uintptr_t)P.col) & 15) != 0)) return 0;
-    if (!pp && binned_chosen(P, s)) return 0;
-    if (tiled_chosen(P, s)) {
+    int nsum = 0;
+    if (c.family == Ax::tiled) {
         // the tiled product: one sum per chunk of 1024 rows (per consumer wavefront), folded like the packed kernel's per-block sums
         static const bool tl_off = [] { const char *e = lab_env("LCG_HIP_AX_DOT_TILED"); return e && atoi(e) == 0; }();
         if (tl_off || !tiled_dot_ok(P)) return 0;
-        const int nchunk = tiled_chunks(P);
-        if (nchunk <= 0) return 0;
-        if (!ensure_dot_part(P, nchunk)) return 0;
-        DotPlan dp; dp.u = u; dp.part = P.dot_part; dp.yy = yy; dp.stride = nchunk;
+        nsum = tiled_chunks(P);
+        if (nsum <= 0 || !ensure_dot_part(P, nsum)) return 0;
+        DotPlan dp; dp.u = u; dp.part = P.dot_part; dp.yy = yy; dp.stride = nsum;
         int rc = tiled_launch(P, x, y, s, done, pp, &dp);
         if (rc) return rc;
         P.last_kernel = pp ? "k_tile_spmv (one-pass tiled product: x tiles and row sums in LDS) + pushing blocks, carrying the dot that follows the product"
                            : "k_tile_spmv (one-pass tiled product: x tiles and row sums in LDS) carrying the dot that follows the product";
-        if (nofold) { *nofold = nchunk; *slots = 0; return 1; }
-        const int g2 = std::min(512, (nchunk + VB - 1) / VB);
-        const int per = (nchunk + g2 - 1) / g2;
-        hipLaunchKernelGGL(k_axp_fold, dim3((nchunk + per - 1) / per), dim3(VB), 0, s, P.dot_part, nchunk, nchunk, per, yy, part, done);
+    } else if (c.family == Ax::ldsp) {
+        nsum = (P.n_rows + PK_R - 1) / PK_R;
+        if (!ensure_dot_part(P, nsum)) return 0;
+        DotPlan dp; dp.u = u; dp.part = P.dot_part; dp.yy = yy; dp.stride = nsum; dp.ystore = y_store_policy();
+        {   static const bool ux_off = [] { const char *e = lab_env("LCG_HIP_DOT_UX"); return e && atoi(e) == 0; }();      // (A/B runs)
+            dp.ux = (u == x && !ux_off) ? 1 : 0; }
+        if (pp) ldsp_launch<true, true>(c, P, x, y, s, done, *pp, dp);
+        else ldsp_launch<false, true>(c, P, x, y, s, done, PushPlan(), dp);
         HIPCHK(hipGetLastError());
-        *slots = (nchunk + per - 1) / per;
-        return 1;
-    }
-    int R = 0; bool onewin = false;
-    { int rc = lds_shape<double>(P, -1, mean_row, s, &R, &onewin); if (rc) return rc; }
-    static const bool big_off = [] { const char *e = lab_env("LCG_HIP_AX_DOT_PACKED"); return e && atoi(e) == 0; }();
-    if (!onewin || big_off) return 0;
-    // (long rows -- blocks of 32 / 16 rows with packed columns, spmv_dispatch -- keep the dot as a pass of its own: carried in the
-    //  product it cost 32 us on the 27-point stencil x 3 unknowns, 187,500 blocks of 16 rows, where the separate pass costs 7)
-    if (R != PK_R || !packed_ready(P, s)) return 0;
-    const int nblk = (n + PK_R - 1) / PK_R;
-    if (!ensure_dot_part(P, nblk)) return 0;
-    DotPlan dp; dp.u = u; dp.part = P.dot_part; dp.yy = yy; dp.stride = nblk; dp.ystore = y_store_policy();
-    {   static const bool ux_off = [] { const char *e = lab_env("LCG_HIP_DOT_UX"); return e && atoi(e) == 0; }();      // (A/B runs)
-        dp.ux = (u == x && !ux_off) ? 1 : 0; }
-    const int per_lane = (P.pk_maxrow + VB / PK_R - 1) / (VB / PK_R);
-    const int ns = per_lane <= 6 ? 6 : per_lane <= 7 ? 7 : per_lane <= 8 ? 8 : per_lane <= 9 ? 9 : per_lane <= 10 ? 10 : per_lane <= 12 ? 12 : 8;
-    const PushPlan ppv = pp ? *pp : PushPlan();
-    const unsigned xb = pp ? (unsigned)(pp->nblocks + pp->nrecv) : 0u;
-    const int win = pk_window(P.max_slice);
-#define PKD_LAUNCH1(PU, NSS, BB, CC)                                                                                \
-            hipLaunchKernelGGL((k_spmv_ldsp<PU, NSS, BB, true, CC>), dim3(nblk + xb), dim3(VB), 0, s, n, P.rowptr,  \
-                               static_cast<const v4i *>(P.pk_data), P.pk_ofs, P.pk_base, P.val, x, y, done, ppv, dp)
-#define PKD_LAUNCH(PU, NSS, BB)                                                                                     \
-    do {                                                                                                            \
-        if (win == PK_CH_8) PKD_LAUNCH1(PU, NSS, BB, PK_CH_8);                                                      \
-        else if (win == PK_CH_7) PKD_LAUNCH1(PU, NSS, BB, PK_CH_7);                                                 \
-        else if (win == PK_CH_SMALL) PKD_LAUNCH1(PU, NSS, BB, PK_CH_SMALL);                                         \
-        else PKD_LAUNCH1(PU, NSS, BB, LdsCfg<double>::CH);                                                          \
-    } while (0)
-#define PKD_CASE(NSS)                                                                                               \
-    case NSS:                                                                                                       \
-        if (pp) { if (P.pk_bits == 18) PKD_LAUNCH(true, NSS, 18); else PKD_LAUNCH(true, NSS, 21); }                 \
-        else { if (P.pk_bits == 18) PKD_LAUNCH(false, NSS, 18); else PKD_LAUNCH(false, NSS, 21); }                  \
-        break;
-    switch (ns) { PKD_CASE(6) PKD_CASE(7) PKD_CASE(8) PKD_CASE(9) PKD_CASE(10) PKD_CASE(12) }
-#undef PKD_LAUNCH
-#undef PKD_LAUNCH1
-#undef PKD_CASE
+        P.last_kernel = ldsp_name(P, true);
+    } else
+        return 0;
+    if (nofold) { *nofold = nsum; *slots = 0; return 1; }
+    const int g2 = std::min(512, (nsum + VB - 1) / VB);
+    const int per = (nsum + g2 - 1) / g2;
+    hipLaunchKernelGGL(k_axp_fold, dim3((nsum + per - 1) / per), dim3(VB), 0, s, P.dot_part, nsum, nsum, per, yy, part, done);
     HIPCHK(hipGetLastError());
-    P.last_kernel = ldsp_name(P, true);
-    if (nofold) { *nofold = nblk; *slots = 0; return 1; }
-    const int g2 = std::min(512, (nblk + VB - 1) / VB);
-    const int per = (nblk + g2 - 1) / g2;
-    hipLaunchKernelGGL(k_axp_fold, dim3((nblk + per - 1) / per), dim3(VB), 0, s, P.dot_part, nblk, nblk, per, yy, part, done);
-    HIPCHK(hipGetLastError());
-    P.last_kernel = ldsp_name(P, true);
-    *slots = (nblk + per - 1) / per;
+    *slots = (nsum + per - 1) / per;
     return 1;
+}
+
+int csr_part_ax_dot(const CsrPart &P, int variant, double mean_row, const double *x, double *y, const double *u, int yy, double *part,
+                    int *slots, hipStream_t s, const int *done, const PushPlan *pp, int *nofold)
+{
+    AxChoice c;
+    { int rc = ax_choose<double, false>(P, variant, mean_row, pp != nullptr, AxAsk::part_dot, s, c); if (rc) return rc; }
+    return part_dot_launch(P, c, x, y, u, yy, part, slots, s, done, pp, nofold);
 }
 
 // A.x with the dot(s) that follow it in the Krylov loops carried in the product (k_spmv_lds1d / k_spmv_ldsp<DOT> / k_spmv_run1d): real
@@ -1577,55 +1582,47 @@ int csr_ax_dot(lcg_hip_csr *A, const double *x, double *y, const double *u, int 
     if (A->distributed) return dist_ax_dot(A, x, y, u, yy, part, slots);
     const CsrPart &P = A->main;
     const int n = P.n_rows;
-    if (A->variant != 0 && A->variant != -1) return 0;
-    if (ranges_chosen(P, s)) return 0;  // multiplied range by range: the dot keeps its own pass
-    if (A->mean_row > 160.0 || ((((uintptr_t)P.val | (uintptr_t)P.col) & 15) != 0)) return 0;
-    if (binned_chosen(P, s)) return 0;
-    if (tiled_chosen(P, s)) return csr_part_ax_dot(P, A->variant, A->mean_row, x, y, u, yy, part, slots, s, done, nullptr, nullptr);
-    int R = 0; bool onewin = false;
-    { int rc = lds_shape<double>(P, -1, A->mean_row, s, &R, &onewin); if (rc) return rc; }
-    if (!onewin) return 0;
-    if (R == PK_R && packed_ready(P, s)) return csr_part_ax_dot(P, A->variant, A->mean_row, x, y, u, yy, part, slots, s, done, nullptr, nullptr);
-    if ((R == 32 || R == 16) && long_rows_packed() && packed_ready(P, s, R)) return 0;     // (the product alone: see csr_part_ax_dot)
-    const int nblk = (n + R - 1) / R;
-    static const bool run1_off = [] { const char *e = lab_env("LCG_HIP_RUN1"); return e && atoi(e) == 0; }();
-    if (!run1_off && (R == 256 || R == 128) && packed_build(P, s, true) && P.pk_maxrow <= 15) {
+    AxChoice c;
+    { int rc = ax_choose<double, false>(P, A->variant, A->mean_row, false, AxAsk::dot, s, c); if (rc) return rc; }
+    switch (c.family) {
+    case Ax::tiled: return part_dot_launch(P, c, x, y, u, yy, part, slots, s, done, nullptr, nullptr);
+    case Ax::ldsp: return ax_dot_packed_off() ? 0 : part_dot_launch(P, c, x, y, u, yy, part, slots, s, done, nullptr, nullptr);
+    case Ax::run1: {
         // short-row stencils (k_spmv_run1d): eight wavefronts, one partial per workgroup of 512 rows (8 x 64 x LP doubles of
-        // dynamic LDS: rows of up to 15 entries; longer ones take the plain product and the separate pass)
+        // dynamic LDS: rows of up to 15 entries; longer ones take k_spmv_lds1d below)
         const int nwg = (int)((((long)n + 63) / 64 + RUN1D_WG / 64 - 1) / (RUN1D_WG / 64));
-        if (nwg <= AXP_CAP) {
-            DotPlan dp; dp.u = u; dp.part = part; dp.yy = yy;
-            const int LP = P.pk_maxrow | 1;
-            const size_t lds = sizeof(double) * (RUN1D_WG / 64) * 64 * (size_t)LP;
-            if (R == 256)
-                hipLaunchKernelGGL((k_spmv_run1d<1>), dim3(nwg), dim3(RUN1D_WG), lds, s, n, LP, P.rowptr, P.col, P.val, P.pk_ofs, P.pk_base,
-                                   static_cast<const int *>(P.pk_data), x, y, done, dp);
-            else
-                hipLaunchKernelGGL((k_spmv_run1d<2>), dim3(nwg), dim3(RUN1D_WG), lds, s, n, LP, P.rowptr, P.col, P.val, P.pk_ofs, P.pk_base,
-                                   static_cast<const int *>(P.pk_data), x, y, done, dp);
-            HIPCHK(hipGetLastError());
-            P.last_kernel = "k_spmv_run1d (one wavefront per 64-row block, run blocks without staging) carrying the dot that follows the product";
-            *slots = nwg;
-            return 1;
-        }
+        if (P.pk_maxrow > 15 || nwg > AXP_CAP) break;
+        DotPlan dp; dp.u = u; dp.part = part; dp.yy = yy;
+        const int LP = P.pk_maxrow | 1;
+        const size_t lds = sizeof(double) * (RUN1D_WG / 64) * 64 * (size_t)LP;
+        pick<1, 2>(c.R == 256 ? 1 : 2, [&](auto t) {
+            hipLaunchKernelGGL((k_spmv_run1d<decltype(t)::value>), dim3(nwg), dim3(RUN1D_WG), lds, s, n, LP, P.rowptr, P.col, P.val, P.pk_ofs,
+                               P.pk_base, static_cast<const int *>(P.pk_data), x, y, done, dp); });
+        HIPCHK(hipGetLastError());
+        P.last_kernel = "k_spmv_run1d (one wavefront per 64-row block, run blocks without staging) carrying the dot that follows the product";
+        *slots = nwg;
+        return 1;
+    }
+    case Ax::lds1: break;
+    // (long rows -- blocks of 32 / 16 rows with packed columns, Ax::ldsp_long -- keep the dot as a pass of its own: carried in the
+    //  product it cost 32 us on the 27-point stencil x 3 unknowns, 187,500 blocks of 16 rows, where the separate pass costs 7)
+    default: return 0;      // (ranges, binned, windowed: the product alone)
     }
     // Where it pays (measured, scripts/ax_dot_lab.py + scripts/ab_small.py): systems whose iteration is a chain of kernel
     // latencies -- the product grows by ~0.6 us, a ~3 us pass and its launch go.  At 1M rows (3907 row blocks) the product grew by
     // 3.2 us and every block of the consuming pass re-added 3907 partials: 39.2 vs 38.5 us per PCG iteration, so from
     // LCG_HIP_AX_DOT_MAXBLK (default 2048) row blocks on the separate pass stays.
     static const int maxblk = [] { const char *e = lab_env("LCG_HIP_AX_DOT_MAXBLK"); const int v = e ? atoi(e) : 2048; return v < 1 ? 1 : (v > AXP_CAP ? AXP_CAP : v); }();
+    const int nblk = (n + c.R - 1) / c.R;
     if (nblk > maxblk) return 0;
     DotPlan dp; dp.u = u; dp.part = part; dp.yy = yy;
-    const int g = nblk;
-#define LDSD_CASE(RR) case RR: hipLaunchKernelGGL((k_spmv_lds1d<RR>), dim3(g), dim3(VB), 0, s, n, P.rowptr, P.col, P.val, x, y, done, dp); break;
-    switch (R) {
-        LDSD_CASE(256) LDSD_CASE(128) LDSD_CASE(64) LDSD_CASE(32) LDSD_CASE(16)
-    default: return 0;
-    }
-#undef LDSD_CASE
+    const bool ok = pick<256, 128, 64, 32, 16>(c.R, [&](auto R) {
+        hipLaunchKernelGGL((k_spmv_lds1d<decltype(R)::value>), dim3(nblk), dim3(VB), 0, s, n, P.rowptr, P.col, P.val, x, y, done, dp);
+    });
+    if (!ok) return 0;
     HIPCHK(hipGetLastError());
     P.last_kernel = "k_spmv_lds1d (LDS-staged CSR carrying the dot that follows the product)";
-    *slots = g;
+    *slots = nblk;
     return 1;
 }
 
