@@ -334,6 +334,33 @@ void clcg_hip_csr_ax(void *instance, const double *x, double *prod_Ax, const int
 void clcg_hip_jacobi_mx(void *instance, const double *x, double *prod_Mx, const int n_size,
                         int layout, int conjugate);                                             /* sample10.cu:99-120 (Jacobi branch) */
 
+/* ---------------------------------------------------------------- IC(0) preconditioner */
+/* Incomplete Cholesky with zero fill on the pattern of A's lower triangle (diagonal included; the upper triangle is ignored,
+ * duplicate entries are summed, columns may come in any order): A ~ L.L^T, unconjugated with the principal square root for
+ * complex A.  Factored on the device over the forward solve's level schedule; L and L^T are copies (rebuild after rewriting an
+ * adopted matrix), freed by lcg_hip_csr_destroy.  Rebuilds on repeat.  LCG_HIP_E_ARG for a non-square or sharded matrix or a
+ * failed pivot (<= 0 or not finite, real; 0 or not finite, complex): lcg_hip_last_error() names the smallest such row.
+ * Stands in for cusparseDcsric02 (sample8.cu:183-238), cusparseZcsric02 (sample10.cu:226-266) and
+ * clcg_incomplete_Cholesky_cuda_full (preconditioner_cuda.cu:207-259; sample12.cu:153, sample13.cu:156). */
+int  lcg_hip_csr_build_ic0(lcg_hip_csr_t A);
+/* Levels of L and L^T, kernel launches of one full apply, the failed pivot's row (-1 = none; what
+ * cusparseXcsric02_zeroPivot reports), host milliseconds of the build, device bytes held by the factor.  Any pointer may be NULL. */
+int  lcg_hip_csr_ic0_info(lcg_hip_csr_t A, int *levels_lower, int *levels_upper, int *launches_per_apply,
+                          int *zero_pivot, double *build_ms, int64_t *bytes);
+/* Device arrays of L in natural row order: rows sorted by column, the diagonal last. */
+int  lcg_hip_csr_ic0_factor(lcg_hip_csr_t A, const int **rowptr, const int **col, const double **val);
+/* y = L^-1 x (which 0), L^-T x (1) or (L.L^T)^-1 x (2) on the current stream; x, y on the device and not overlapping
+ * (cusparseDcsrsv2_solve, sample8.cu:105-119; cusparseSpSV, sample12.cu:153). */
+int  lcg_hip_ic0_solve(lcg_hip_csr_t A, int which, const double *x, double *y);
+/* Ready-made preconditioner callbacks, z = (L.L^T)^-1 x; pass the lcg_hip_csr_t as `instance`.  A handle without a factor, the
+ * wrong value type, n_size other than the row count or conjugate = 1 end the solve with LCG_HIP_E_ARG; layout is ignored
+ * (M is (complex-)symmetric). */
+void lcg_hip_ic0_mx(void *instance, const double *x, double *prod_Mx, const int n_size);          /* sample8.cu:105-119 */
+void clcg_hip_ic0_mx(void *instance, const double *x, double *prod_Mx, const int n_size,
+                     int layout, int conjugate);                                                  /* sample10.cu:99-120 (IC branch) */
+/* Test hook: the widest level a one-workgroup launch may take over several levels (0: one launch per level; -1: production). */
+int  lcg_hip_csr_ic0_schedule_for_test(lcg_hip_csr_t A, int max_merged_rows);
+
 /* ---------------------------------------------------------------- kernels */
 /* Stand-alone launches of the hot-path kernels on the current stream (device pointers).
  * Scalar results are written to host memory after a stream synchronise. */

@@ -93,6 +93,13 @@ SIGNATURES = {
     "lcg_hip_csr_last_traffic_model": (C.c_int64, [vp]),
     "lcg_hip_csr_plan_info": (C.c_int, [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "lcg_hip_csr_build_jacobi": (C.c_int, [vp, vp]),
+    "lcg_hip_csr_build_ic0": (C.c_int, [vp]),
+    "lcg_hip_csr_ic0_info": (C.c_int, [vp, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p, C.POINTER(C.c_int64)]),
+    "lcg_hip_csr_ic0_factor": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "lcg_hip_ic0_solve": (C.c_int, [vp, C.c_int, vp, vp]),
+    "lcg_hip_ic0_mx": (None, [vp, vp, vp, C.c_int]),
+    "clcg_hip_ic0_mx": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
+    "lcg_hip_csr_ic0_schedule_for_test": (C.c_int, [vp, C.c_int]),
     "lcg_hip_csr_ax": (None, [vp, vp, vp, C.c_int]),
     "lcg_hip_jacobi_mx": (None, [vp, vp, vp, C.c_int]),
     "clcg_hip_csr_ax": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),

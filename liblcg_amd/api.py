@@ -142,6 +142,37 @@ class CsrMatrix:
         p = None if diag_out is None else _ptr(diag_out)[0]
         _chk(L.load().lcg_hip_csr_build_jacobi(self.h, p), "build_jacobi")
 
+    # -- IC(0) preconditioner (csr_ic0.hip) -------------------------------------------------
+    def build_ic0(self):
+        """Factor A ~ L.L^T with zero fill on the device; pass "lcg_hip_ic0_mx" / "clcg_hip_ic0_mx" as Mfp afterwards."""
+        _chk(L.load().lcg_hip_csr_build_ic0(self.h), "build_ic0")
+
+    def ic0_info(self) -> dict:
+        ll, lu, la, zp = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        ms, nb = C.c_double(), C.c_int64()
+        _chk(L.load().lcg_hip_csr_ic0_info(self.h, C.byref(ll), C.byref(lu), C.byref(la), C.byref(zp), C.byref(ms), C.byref(nb)),
+             "ic0_info")
+        return {"levels_lower": ll.value, "levels_upper": lu.value, "launches_per_apply": la.value,
+                "zero_pivot": zp.value, "build_ms": ms.value, "bytes": nb.value}
+
+    def ic0_factor_to_host(self):
+        """(rowptr, col, val) of L copied to numpy: natural row order, rows sorted, the diagonal last."""
+        lib = L.load()
+        pr, pc, pv = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _chk(lib.lcg_hip_csr_ic0_factor(self.h, C.byref(pr), C.byref(pc), C.byref(pv)), "ic0_factor")
+        rowptr = np.empty(self.n + 1, np.int32)
+        _chk(lib.lcg_hip_memcpy(rowptr.ctypes.data, pr, rowptr.nbytes, 2), "memcpy d2h")
+        nnz = int(rowptr[-1])
+        col = np.empty(nnz, np.int32)
+        val = np.empty(nnz, np.complex128 if self.is_complex else np.float64)
+        for dst, src in ((col, pc), (val, pv)):
+            _chk(lib.lcg_hip_memcpy(dst.ctypes.data, src, dst.nbytes, 2), "memcpy d2h")
+        return rowptr, col, val
+
+    def ic0_solve(self, x, y, which=2):
+        """y = L^-1 x (which 0), L^-T x (1) or (L.L^T)^-1 x (2); device tensors, on the library's stream."""
+        _chk(L.load().lcg_hip_ic0_solve(self.h, which, _ptr(x)[0], _ptr(y)[0]), "ic0_solve")
+
     def spmv(self, x, y):
         _chk(L.load().lcg_hip_spmv(self.h, _ptr(x)[0], _ptr(y)[0]), "spmv")
 

@@ -441,6 +441,38 @@ __global__ void k_conj_copy(long nnz, const double2 *in, double2 *out)
         out[k] = make_double2(in[k].x, -in[k].y);
 }
 
+// T = S^T (S: n rows, nt columns, nnz entries) with sorted rows; cnt: nt ints of workspace.  Drains the stream.
+int transpose_launch(int n, int nt, long nnz, const int *rowptr, const int *col, const double *val, int *rpT, int *colT, double *valT,
+                     bool cplx, int conj, int *cnt, hipStream_t s)
+{
+    HIPCHK(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)nt, s));
+    hipLaunchKernelGGL(k_tr_count, dim3(1024), dim3(VB), 0, s, nnz, col, cnt);
+    long total = 0;
+    int rc = device_exclusive_scan(nt, cnt, rpT, s, &total);
+    if (rc || total != nnz) return rc ? rc : fail(hipErrorUnknown, "transpose count", __FILE__, __LINE__);
+    HIPCHK(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)nt, s));
+    const unsigned g = (unsigned)((n + VB - 1) / VB);
+    const unsigned gt = (unsigned)((nt + VB - 1) / VB);
+    if (cplx) {
+        hipLaunchKernelGGL((k_tr_fill<double2>), dim3(g), dim3(VB), 0, s, n, rowptr, col, reinterpret_cast<const double2 *>(val), rpT, cnt,
+                           colT, reinterpret_cast<double2 *>(valT), conj);
+        hipLaunchKernelGGL((k_row_sort<double2>), dim3(gt), dim3(VB), 0, s, nt, rpT, colT, reinterpret_cast<double2 *>(valT));
+    } else {
+        hipLaunchKernelGGL((k_tr_fill<double>), dim3(g), dim3(VB), 0, s, n, rowptr, col, val, rpT, cnt, colT, valT, 0);
+        hipLaunchKernelGGL((k_row_sort<double>), dim3(gt), dim3(VB), 0, s, nt, rpT, colT, valT);
+    }
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) return fail(e, "transpose build", __FILE__, __LINE__);
+    return 0;
+}
+
+void row_sort_launch(int n, const int *rowptr, int *col, double *val, bool cplx, hipStream_t s)
+{
+    const unsigned g = (unsigned)((n + VB - 1) / VB);
+    if (cplx) hipLaunchKernelGGL((k_row_sort<double2>), dim3(g), dim3(VB), 0, s, n, rowptr, col, reinterpret_cast<double2 *>(val));
+    else hipLaunchKernelGGL((k_row_sort<double>), dim3(g), dim3(VB), 0, s, n, rowptr, col, val);
+}
+
 // part of `A` that realises op(A); built on first use.  layout/conjugate as in algebra.h:31-50.
 int op_part(lcg_hip_csr *A, int layout, int conjugate, const CsrPart **out)
 {
@@ -476,25 +508,10 @@ int op_part(lcg_hip_csr *A, int layout, int conjugate, const CsrPart **out)
     } else {
         int *cnt = nullptr;
         HIPCHK(hipMalloc(&cnt, sizeof(int) * (size_t)nt));
-        HIPCHK(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)nt, c.stream));
-        hipLaunchKernelGGL(k_tr_count, dim3(1024), dim3(VB), 0, c.stream, nnz, A->main.col, cnt);
-        long total = 0;
-        rc = device_exclusive_scan((int)nt, cnt, T.rowptr, c.stream, &total);
-        if (rc || total != nnz) { hipFree(cnt); return rc ? rc : fail(hipErrorUnknown, "transpose count", __FILE__, __LINE__); }
-        HIPCHK(hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)nt, c.stream));
-        const unsigned g = (unsigned)((n + VB - 1) / VB), gt = (unsigned)((nt + VB - 1) / VB);
-        if (A->is_complex) {
-            hipLaunchKernelGGL((k_tr_fill<double2>), dim3(g), dim3(VB), 0, c.stream, n, A->main.rowptr, A->main.col,
-                               reinterpret_cast<const double2 *>(A->main.val), T.rowptr, cnt, T.col, reinterpret_cast<double2 *>(T.val), conjugate);
-            hipLaunchKernelGGL((k_row_sort<double2>), dim3(gt), dim3(VB), 0, c.stream, (int)nt, T.rowptr, T.col, reinterpret_cast<double2 *>(T.val));
-        } else {
-            hipLaunchKernelGGL((k_tr_fill<double>), dim3(g), dim3(VB), 0, c.stream, n, A->main.rowptr, A->main.col, A->main.val,
-                               T.rowptr, cnt, T.col, T.val, 0);
-            hipLaunchKernelGGL((k_row_sort<double>), dim3(gt), dim3(VB), 0, c.stream, (int)nt, T.rowptr, T.col, T.val);
-        }
-        hipError_t e = hipStreamSynchronize(c.stream);
+        rc = transpose_launch(n, (int)nt, nnz, A->main.rowptr, A->main.col, A->main.val, T.rowptr, T.col, T.val, A->is_complex,
+                              conjugate, cnt, c.stream);
         hipFree(cnt);
-        if (e != hipSuccess) return fail(e, "transpose build", __FILE__, __LINE__);
+        if (rc) return rc;
     }
     HIPCHK(hipGetLastError());
     *out = &T;

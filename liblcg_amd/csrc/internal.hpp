@@ -330,6 +330,7 @@ struct lcg_hip_csr {
     double *op_z = nullptr;     // (A_r)^T . x_r over the padded global height, and one rows-per-rank block behind it (dist_spmv_op)
     void *halo = nullptr;       // neighbour-exchange plan (comm.hip)
     void *direct = nullptr;     // direct (peer-mapped) exchange state (comm.hip, mode 2)
+    void *ic0 = nullptr;        // incomplete-Cholesky factor and its level schedules (csr_ic0.hip), a copy: built by lcg_hip_csr_build_ic0
 };
 
 namespace lcgh {
@@ -368,6 +369,12 @@ size_t tiled_plan_bytes(const CsrPart &P);
 int op_part(lcg_hip_csr *A, int layout, int conjugate, const CsrPart **out);
 int alloc_part(CsrPart &P, int n_rows, long nnz, bool cplx);        // owned, padded arrays of a part
 int device_exclusive_scan(int n, const int *counts, int *rowptr, hipStream_t s, long *total);
+// T = S^T with sorted rows by k_tr_count / k_tr_fill / k_row_sort (op(A), the IC(0) factor's L^T); drains the stream
+int transpose_launch(int n, int nt, long nnz, const int *rowptr, const int *col, const double *val, int *rpT, int *colT, double *valT,
+                     bool cplx, int conj, int *cnt, hipStream_t s);
+void row_sort_launch(int n, const int *rowptr, int *col, double *val, bool cplx, hipStream_t s);    // k_row_sort: by (column, value)
+// csr_ic0.hip
+void ic0_free(lcg_hip_csr *A);
 // csr.hip
 void free_part(CsrPart &P);                                          // a part's arrays and every plan built beside them
 
