@@ -159,12 +159,21 @@ def test_solves_match_scipy_and_repeat_bitwise(api, case10k, case1kc, case10kc, 
     A.destroy()
 
 
+def _launches_rule(rp, ci, groupings=(1024,)):
+    """Launches per apply by DESIGN 11's rule over the checker's level sets of both triangles, for each max_merged given."""
+    fw, bw = K.levels(len(rp) - 1, rp, ci)
+    wf, wb = K.widths(fw), K.widths(bw)
+    return [K.segments(wf, mm) + K.segments(wb, mm) for mm in groupings]
+
+
 def test_launch_counts(api, case10k, case1kc, case10kc):
+    from liblcg_amd import _lib
+    lib = _lib.load()
     for name, want in (("case10k", 2), ("tridiag50k", 2)):
-        A = _matrix(api, name, case10k, case1kc, case10kc)[0]
+        A, rp, ci, _ = _matrix(api, name, case10k, case1kc, case10kc)
         A.build_ic0()
         info = A.ic0_info()
-        assert info["launches_per_apply"] == want, (name, info)
+        assert [info["launches_per_apply"]] == [want] == _launches_rule(rp, ci), (name, info)
         if name == "tridiag50k":
             assert info["levels_lower"] == info["levels_upper"] == 50000
         A.destroy()
@@ -173,7 +182,17 @@ def test_launch_counts(api, case10k, case1kc, case10kc):
     A.build_ic0()
     info = A.ic0_info()
     assert info["levels_lower"] == info["levels_upper"] == 3 * 63 + 1
-    assert info["launches_per_apply"] > 2                   # the middle planes are wider than a workgroup
+    # the middle planes are wider than a workgroup: exactly the launches the rule gives, under every grouping
+    groupings = (0, 1, 2, 63, 64, 1023, 1024)
+    rule = _launches_rule(rp, ci, groupings)
+    assert info["launches_per_apply"] == rule[-1] > 2
+    try:
+        for mm, want in zip(groupings, rule):
+            assert lib.lcg_hip_csr_ic0_schedule_for_test(A.h, mm) == 0
+            assert A.ic0_info()["launches_per_apply"] == want, mm
+    finally:
+        assert lib.lcg_hip_csr_ic0_schedule_for_test(A.h, -1) == 0
+    assert A.ic0_info()["launches_per_apply"] == info["launches_per_apply"]
     A.destroy()
 
 

@@ -83,3 +83,93 @@ def test_case10k_iteration_counts(sys10k, eps, abs_diff, want_ic, want_jacobi):
     assert K.lpcg(A, M.solve, b, eps, abs_diff)[1] == want_ic
     dinv = 1.0 / A.diagonal()
     assert K.lpcg(A, lambda r: r * dinv, b, eps, abs_diff)[1] == want_jacobi
+
+
+# ------------------------------------------------------------------------------------------ level sets and launches
+def _longest_paths(n, edges):
+    """Longest path ending at every node of a DAG by n rounds of relaxation over all edges (u -> v: v after u)."""
+    lev = np.zeros(n, np.int64)
+    for _ in range(n):
+        changed = False
+        for u, v in edges:
+            if lev[v] < lev[u] + 1:
+                lev[v] = lev[u] + 1; changed = True
+        if not changed:
+            break
+    return lev
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_levels_are_longest_paths(seed):
+    from conftest import FUZZ_SEED_OFFSET
+    rng = np.random.default_rng(500 + seed + FUZZ_SEED_OFFSET)
+    n = int(rng.integers(1, 40))
+    A = (rng.uniform(size=(n, n)) < rng.uniform(0.02, 0.3)).astype(float)
+    A[rng.uniform(size=n) < 0.2] = 0.0                          # some empty rows
+    rp, ci, _ = _dense_to_csr(A)
+    # both triangles may hold entries: only the strictly lower ones are dependencies (row i reads row j < i)
+    deps = {(int(j), i) for i in range(n) for j in ci[rp[i]:rp[i + 1]] if j < i}
+    fw, bw = K.levels(n, rp, ci)
+    np.testing.assert_array_equal(fw, _longest_paths(n, sorted(deps)))
+    np.testing.assert_array_equal(bw, _longest_paths(n, sorted((i, j) for j, i in deps)))
+
+
+def test_levels_follow_rows_not_storage_order():
+    # row 2 reads row 1 (and stores an upper entry); row 3 reads rows 2 and 0, unsorted, row 0 twice
+    rp = np.array([0, 1, 2, 5, 9]); ci = np.array([0, 1, 2, 1, 3, 3, 0, 2, 0])
+    fw, bw = K.levels(4, rp, ci)
+    np.testing.assert_array_equal(fw, [0, 0, 1, 2])
+    np.testing.assert_array_equal(bw, [1, 2, 1, 0])     # L^T: row 1 waits for 2, which waits for 3; row 0 for 3 only
+
+
+@pytest.mark.parametrize("widths,max_merged,want", [
+    ([1024, 1025, 1024], 1024, 3),          # narrow, wide, narrow
+    ([1024, 1024, 1024], 1024, 1),          # a level of exactly max_merged rows is narrow
+    ([1025, 1025], 1024, 2),                # all wide
+    ([3, 1, 700, 1024, 5], 1024, 1),        # all narrow: one run
+    ([1, 2, 1, 3], 0, 4),                   # max_merged = 0: one launch per level
+    ([1, 1, 2, 1, 1], 1, 3),                # 1: runs of single-row levels
+    ([1023, 1024, 1023, 1], 1023, 3),       # 1023: the 1024-row level is wide
+    ([2048, 1, 1, 2048, 7, 2048], 1024, 5),
+    ([], 1024, 0),
+])
+def test_segments_rule(widths, max_merged, want):
+    assert K.segments(widths, max_merged) == want
+
+
+def test_laplace3d_40_levels_and_launches():
+    rp, ci, _ = K.laplace3d(40)
+    fw, bw = K.levels(len(rp) - 1, rp, ci)
+    wf, wb = K.widths(fw), K.widths(bw)
+    assert len(wf) == len(wb) == 118
+    assert (wf > 1024).sum() == (wb > 1024).sum() == 26
+    assert K.segments(wf, 1024) + K.segments(wb, 1024) == 56
+
+
+@pytest.mark.parametrize("cplx", [False, True])
+def test_layered_generator_gives_the_widths_asked(cplx):
+    widths = [1024, 1025, 1, 1023, 3000, 1024, 5, 2048]
+    rp, ci, v = K.layered(widths, 41, cplx)
+    n = len(rp) - 1
+    assert n == sum(widths) and np.iscomplexobj(v) == cplx
+    fw, _ = K.levels(n, rp, ci)
+    assert list(K.widths(fw)) == widths
+    srp, sci, sv = K.shuffle_split(rp, ci, v, 42)
+    assert list(K.widths(K.levels(n, srp, sci)[0])) == widths
+    As, Ass = K.to_sparse(n, rp, ci, v), K.to_sparse(n, srp, sci, sv)
+    assert abs(As - As.T).max() == 0 and abs(As - Ass).max() < 1e-15
+    assert K.ic0(n, rp, ci, v)[3] == -1
+
+
+def test_checker_pbicg_converges_on_complex_case():
+    from conftest import _ccase
+    n, rp, ci, v, b, xs = _ccase("1K")
+    Lr, Lc, Lv, zp = K.ic0(n, rp, ci, v)
+    assert zp == -1
+    A = K.to_sparse(n, rp, ci, v)
+    M = K.IcApply(K.to_sparse(n, Lr, Lc, Lv))
+    m, t = K.clpbicg(A, M.solve, b, 1e-10, 1)
+    assert t == 17 and np.linalg.norm(m - xs) < 1e-8
+    # A complex-symmetric and M = M^T: the shadow recurrence walks conj of the primal one, so PBiCG meets PCG
+    mp, tp = K.clpcg(A, M.solve, b, 1e-10, 1)
+    assert tp == t and np.linalg.norm(m - mp) <= 1e-10 * np.linalg.norm(mp)
