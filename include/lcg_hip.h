@@ -96,6 +96,16 @@ typedef void (*clcg_hip_axfunc_ptr)(void *instance, const double *x, double *pro
 typedef int (*clcg_hip_progress_ptr)(void *instance, const double *m, const double converge,
                                      const clcg_para *param, const int n_size, const int k);
 
+/* clcg_cudaf.h's callbacks with complex64 vectors: interleaved (re,im) floats == cuComplex == std::complex<float>.  x and
+ * prod_Ax are DEVICE pointers; layout / conjugate as clcg_hip_axfunc_ptr (BiCG asks for A^H.x: layout 1, conjugate 1 --
+ * CUSPARSE_OPERATION_CONJUGATE_TRANSPOSE, clcg_cudaf.cu:217).  Replaces clcg_axfunc_cudaf_ptr, whose cuSPARSE descriptors
+ * do not cross this boundary. */
+typedef void (*clcg_hip_axfunc_c64_ptr)(void *instance, const float *x, float *prod_Ax, const int n_size,
+                                        int layout, int conjugate);
+/* clcg_progress_cudaf_ptr: m is the DEVICE solution vector, converge the fp32 residual; non-zero stops with CLCG_STOP. */
+typedef int (*clcg_hip_progress_c64_ptr)(void *instance, const float *m, const float converge,
+                                         const clcg_para *param, const int n_size, const int k);
+
 /* ------------------------------------------------------- runtime / stream */
 int  lcg_hip_init(int device);                 /* selects the device; idempotent. */
 int  lcg_hip_set_stream(void *hip_stream);     /* NULL = the library's own stream */
@@ -221,6 +231,24 @@ int clcg_hip_solver(clcg_hip_axfunc_ptr Afp, clcg_hip_progress_ptr Pfp, double *
 int clcg_hip_solver_preconditioned(clcg_hip_axfunc_ptr Afp, clcg_hip_axfunc_ptr Mfp, clcg_hip_progress_ptr Pfp,
                                    double *m, const double *B, int n_size, const clcg_para *param,
                                    void *instance, int solver_id, int mem);
+/* Complex64 (single-precision complex) solvers: clcg_cudaf.cu, the CUDA fp32 family.  m, B: n interleaved float pairs where `mem`
+ * says.  clcg_solver_cuda (clcg_cudaf.cu:42-60): CLCG_BICG runs clbicg (:86-252; the callback is asked for A^H.x, :217),
+ * CLCG_BICG_SYM clbicg_symmetric (:254-401); any other id returns CLCG_UNKNOWN_SOLVER before the arguments are checked.
+ * Vectors and the reference's float scalars (ak, betak, norms, residual) are fp32; dots and norms sum exact products in fp64 in a
+ * fixed order and are rounded to fp32 once (bit-identical from run to run).  Stop rule |r|^2 / max(|m|, 1)^2, or |r| / n with
+ * abs_diff (which then tests |r| / n only, where the reference reads m_mod uninitialised: :162).  Codes as the reference,
+ * LCG_REACHED_MAX_ITERATIONS at the cap.  Where the reference spins to the cap after a breakdown (for ever with max_iterations = 0),
+ * these stop at the first iteration whose |m|^2 or |r|^2 is NaN with CLCG_NAN_VALUE, as the c128 loops do.  Afp == NULL returns
+ * CLCG_INVALID_POINTER.
+ * clcg_hip_csr_ax_c64 is the ready-made A.x. */
+int clcg_hip_solver_c64(clcg_hip_axfunc_c64_ptr Afp, clcg_hip_progress_c64_ptr Pfp, float *m, const float *B,
+                        int n_size, const clcg_para *param, void *instance, int solver_id, int mem);
+/* clcg_solver_preconditioned_cuda (clcg_cudaf.cu:66-84): CLCG_PCG runs clpcg (:403-558: unconjugated dots, complex-symmetric A),
+ * any other id returns CLCG_UNKNOWN_SOLVER; Mfp == NULL returns LCG_NULL_PRECONDITION_MATRIX.  clcg_hip_jacobi_mx_c64 is the
+ * ready-made Jacobi (its reciprocal multiply then rides in the update pass). */
+int clcg_hip_solver_preconditioned_c64(clcg_hip_axfunc_c64_ptr Afp, clcg_hip_axfunc_c64_ptr Mfp, clcg_hip_progress_c64_ptr Pfp,
+                                       float *m, const float *B, int n_size, const clcg_para *param, void *instance,
+                                       int solver_id, int mem);
 int lcg_hip_set_shadow_seed(unsigned seed);
 /* Replace the drawn shadow residual by an explicit vector (n complex, host memory) for the
  * next complex solve only; lets a test replay the reference's own rbar0. */
@@ -238,6 +266,15 @@ typedef struct lcg_hip_csr *lcg_hip_csr_t;
  * admits the fastest A.x kernel (copied matrices always have that slack). */
 int lcg_hip_csr_create(lcg_hip_csr_t *A, int n_rows, int n_cols, int64_t nnz, const int *rowptr,
                        const int *col, const double *val, int is_complex, int mem, int adopt);
+/* The same with complex64 values: val = nnz interleaved (re, im) floats (cuComplex; the CUDA_C_32F matrix of clcg_cudaf.cu's
+ * callers, sample14.cu).  Copy / adopt as lcg_hip_csr_create (adopt == 2: 64 readable bytes behind col[nnz] and val[nnz]).
+ * Such a handle serves lcg_hip_spmv_c64, clcg_hip_csr_ax_c64, clcg_hip_jacobi_mx_c64, lcg_hip_csr_build_jacobi and the
+ * read-only queries (lcg_hip_csr_arrays then hands back `val` typed const double *: it points to nnz interleaved float pairs --
+ * cast it to const float *); every other entry that takes a matrix (set_kernel / packed / binned / tiled / ranges, distribute, build_ic0,
+ * lcg_hip_spmv, lcg_hip_spmv_op, lcg_hip_spmv_dot) and the fp64 / c128 ready-made callbacks return LCG_HIP_E_ARG
+ * (lcg_hip_last_error() says why); a c128 or real handle in the _c64 entries likewise.  Not shardable. */
+int lcg_hip_csr_create_c64(lcg_hip_csr_t *A, int n_rows, int n_cols, int64_t nnz, const int *rowptr,
+                           const int *col, const float *val, int mem, int adopt);
 /* COO (row-sorted or not) -> CSR on the device: data/README:1-10 files, sample8.cu:30-64,169. */
 int lcg_hip_csr_from_coo(lcg_hip_csr_t *A, int n, int64_t nnz, const int *row, const int *col,
                          const double *val, int is_complex, int mem);
@@ -323,7 +360,8 @@ int64_t lcg_hip_csr_last_traffic_model(lcg_hip_csr_t A);
 int lcg_hip_csr_plan_info(lcg_hip_csr_t A, double *build_ms, int64_t *extra_bytes);
 /* Extract the diagonal and keep its reciprocal for lcg_hip_jacobi_mx
  * (lcg_smDcsr_get_diagonal algebra_cuda.cu:40-57,85-92; clcg_smZcsr_get_diagonal
- * lcg_complex_cuda.cu:46-63).  diag_out (device, n values) may be NULL. */
+ * lcg_complex_cuda.cu:46-63).  diag_out (device, n values) may be NULL.  A complex64 handle keeps complex64 reciprocals (for
+ * clcg_hip_jacobi_mx_c64) and diag_out, if given, receives n interleaved float pairs. */
 int lcg_hip_csr_build_jacobi(lcg_hip_csr_t A, double *diag_out);
 
 /* Ready-made callbacks; pass the lcg_hip_csr_t as `instance`. */
@@ -333,6 +371,12 @@ void clcg_hip_csr_ax(void *instance, const double *x, double *prod_Ax, const int
                      int layout, int conjugate);                                                /* sample10.cu:90-97 */
 void clcg_hip_jacobi_mx(void *instance, const double *x, double *prod_Mx, const int n_size,
                         int layout, int conjugate);                                             /* sample10.cu:99-120 (Jacobi branch) */
+/* The complex64 ones.  clcg_hip_csr_ax_c64 = lcg_hip_spmv_c64 (all four forms; sample14.cu's cusparseSpMV callback);
+ * clcg_hip_jacobi_mx_c64: z = x .* (1 / diag) after lcg_hip_csr_build_jacobi, layout / conjugate ignored. */
+void clcg_hip_csr_ax_c64(void *instance, const float *x, float *prod_Ax, const int n_size,
+                         int layout, int conjugate);
+void clcg_hip_jacobi_mx_c64(void *instance, const float *x, float *prod_Mx, const int n_size,
+                            int layout, int conjugate);
 
 /* ---------------------------------------------------------------- IC(0) preconditioner */
 /* Incomplete Cholesky with zero fill on the pattern of A's lower triangle (diagonal included; the upper triangle is ignored,
@@ -376,6 +420,12 @@ int lcg_hip_spmv_op(lcg_hip_csr_t A, const double *x, double *y, int layout, int
  * allows, the sums ride in the product's epilogue (what the built-in solvers use on one GPU: lcg_hip_csr_last_kernel says
  * "carrying the dot"); otherwise product and reduction run as two launches.  Real matrices. */
 int lcg_hip_spmv_dot(lcg_hip_csr_t A, const double *x, double *y, const double *u, double *result2);
+/* y = op(A).x for a complex64 handle (layout / conjugate as lcg_hip_spmv_op: A, A^T, conj(A), A^H), summed in fp32 as cuSPARSE's
+ * CUDA_C_32F (clcg_cudaf.cu's Afp), each row in one fixed order: bit-identical from call to call.  k_c64_rows (W lanes per row,
+ * each pair of entries one 16-byte value load and one 8-byte column load, row ends masked by selects) and, for rows of more than max(256, 64 W) entries, k_c64_long (one workgroup per row);
+ * chosen at the first product of each form, whose transposed / conjugated copy is built then on the device
+ * (lcg_hip_csr_last_kernel names them).  Later calls neither allocate nor synchronise. */
+int lcg_hip_spmv_c64(lcg_hip_csr_t A, const float *x, float *y, int layout, int conjugate);
 int lcg_hip_dot(int n, const double *a, const double *b, double *result);      /* lcg_dot, algebra.cpp:154-163; cublasDdot lcg_cuda.cu:187 */
 int lcg_hip_nrm2(int n, const double *a, double *result);                      /* cublasDznrm2-style 2-norm */
 int lcg_hip_axpy(int n, double alpha, const double *x, double *y);             /* y += alpha*x, cublasDaxpy lcg_cuda.cu:190 */

@@ -36,6 +36,8 @@ AXFUNC = C.CFUNCTYPE(None, vp, vp, vp, C.c_int)
 PROGRESS = C.CFUNCTYPE(C.c_int, vp, vp, C.c_double, C.POINTER(LcgPara), C.c_int, C.c_int)
 CAXFUNC = C.CFUNCTYPE(None, vp, vp, vp, C.c_int, C.c_int, C.c_int)
 CPROGRESS = C.CFUNCTYPE(C.c_int, vp, vp, C.c_double, C.POINTER(ClcgPara), C.c_int, C.c_int)
+# the complex64 family (clcg_cudaf.h): float vectors, a float residual
+CPROGRESS_C64 = C.CFUNCTYPE(C.c_int, vp, vp, C.c_float, C.POINTER(ClcgPara), C.c_int, C.c_int)
 
 # every symbol include/lcg_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
@@ -71,6 +73,12 @@ SIGNATURES = {
     "clcg_hip_solver": (C.c_int, [vp, vp, vp, vp, C.c_int, C.POINTER(ClcgPara), vp, C.c_int, C.c_int]),
     "clcg_hip_solver_preconditioned": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.POINTER(ClcgPara), vp, C.c_int, C.c_int]),
     "clcg_hip_jacobi_mx": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
+    "clcg_hip_solver_c64": (C.c_int, [vp, vp, vp, vp, C.c_int, C.POINTER(ClcgPara), vp, C.c_int, C.c_int]),
+    "clcg_hip_solver_preconditioned_c64": (C.c_int, [vp, vp, vp, vp, vp, C.c_int, C.POINTER(ClcgPara), vp, C.c_int, C.c_int]),
+    "lcg_hip_csr_create_c64": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int64, vp, vp, vp, C.c_int, C.c_int]),
+    "lcg_hip_spmv_c64": (C.c_int, [vp, vp, vp, C.c_int, C.c_int]),
+    "clcg_hip_csr_ax_c64": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
+    "clcg_hip_jacobi_mx_c64": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
     "lcg_hip_set_shadow_seed": (C.c_int, [C.c_uint]),
     "lcg_hip_set_shadow_vector": (C.c_int, [vp, C.c_int]),
     "lcg_hip_csr_create": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, C.c_int64, vp, vp, vp, C.c_int, C.c_int, C.c_int]),

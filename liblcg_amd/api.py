@@ -13,7 +13,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib as L
-from ._lib import CAXFUNC, CPROGRESS, AXFUNC, PROGRESS, ClcgPara, LcgPara  # noqa: F401
+from ._lib import CAXFUNC, CPROGRESS, CPROGRESS_C64, AXFUNC, PROGRESS, ClcgPara, LcgPara  # noqa: F401
 
 LCG_CG, LCG_PCG, LCG_CGS, LCG_BICGSTAB, LCG_BICGSTAB2, LCG_PG, LCG_SPG = range(7)
 CLCG_BICG, CLCG_BICG_SYM, CLCG_CGS, CLCG_BICGSTAB, CLCG_TFQMR, CLCG_PCG, CLCG_PBICG = range(7)
@@ -65,6 +65,7 @@ def use_torch_stream():
 
 class CsrMatrix:
     """An HBM-resident CSR matrix (handle ``lcg_hip_csr_t``)."""
+    is_c64 = False      # values are complex64 (from_csr_c64)
 
     def __init__(self, handle: int, n_rows: int, is_complex: bool, keep=()):
         self.h = C.c_void_p(handle)
@@ -86,6 +87,30 @@ class CsrMatrix:
         h = C.c_void_p()
         _chk(lib.lcg_hip_csr_create(C.byref(h), n, n_cols or n, nnz, pr, pc, pv, int(is_c), mem, int(adopt)), "csr_create")
         return cls(h.value, n, is_c, keep=(rowptr, col, val) if adopt else ())
+
+    @classmethod
+    def from_csr_c64(cls, rowptr, col, val, n_cols=None, adopt=False):
+        """A complex64 matrix (lcg_hip_csr_create_c64): val is cast to complex64 (numpy) or must be a torch.complex64
+        tensor.  Products: spmv_c64 / 'clcg_hip_csr_ax_c64'; solvers: clcg_solver_c64, clcg_solver_preconditioned_c64."""
+        lib = L.load()
+        if isinstance(val, np.ndarray):
+            rowptr = np.ascontiguousarray(rowptr, np.int32); col = np.ascontiguousarray(col, np.int32)
+            val = np.ascontiguousarray(val, np.complex64)
+        else:
+            import torch
+            if val.dtype != torch.complex64:
+                raise TypeError(f"from_csr_c64 takes complex64 values, not {val.dtype}")
+        n = len(rowptr) - 1
+        (pr, mem), (pc, _), (pv, _) = _ptr(rowptr), _ptr(col), _ptr(val)
+        h = C.c_void_p()
+        _chk(lib.lcg_hip_csr_create_c64(C.byref(h), n, n_cols or n, len(col), pr, pc, pv, mem, int(adopt)), "csr_create_c64")
+        M = cls(h.value, n, True, keep=(rowptr, col, val) if adopt else ())
+        M.is_c64 = True
+        return M
+
+    def spmv_c64(self, x, y, layout=0, conjugate=0):
+        """y = op(A).x for a complex64 matrix (torch.complex64 CUDA tensors)."""
+        return _chk(L.load().lcg_hip_spmv_c64(self.h, _ptr(x)[0], _ptr(y)[0], layout, conjugate), "spmv_c64")
 
     @classmethod
     def from_coo(cls, n, row, col, val):
@@ -302,6 +327,40 @@ def clcg_solver_preconditioned(Afp, Mfp, Pfp, m, B, n_size, param, instance, sol
     rc = lib.clcg_hip_solver_preconditioned(a, mm, p, pm, pb, n_size, C.byref(param) if param is not None else None,
                                             _instance(instance), solver_id, mem)
     _chk(rc, "clcg_solver_preconditioned")
+    return SolveInfo(rc, lib.lcg_hip_last_iterations(), lib.lcg_hip_last_residual())
+
+
+def _c64_vectors(m, B):
+    import torch
+    for v in (m, B):
+        if isinstance(v, np.ndarray) and v.dtype != np.complex64 or isinstance(v, torch.Tensor) and v.dtype != torch.complex64:
+            raise TypeError(f"the complex64 solvers take complex64 vectors, not {v.dtype}")
+    (pm, mem), (pb, mem_b) = _ptr(m), _ptr(B)
+    if mem != mem_b:
+        raise ValueError("m and B must live in the same memory space")
+    return pm, pb, mem
+
+
+def clcg_solver_c64(Afp, Pfp, m, B, n_size, param, instance, solver_id=CLCG_BICG) -> SolveInfo:
+    """clcg_solver_cuda() of clcg_cudaf.cu (CLCG_BICG, CLCG_BICG_SYM).  m, B: complex64 (torch CUDA or numpy); Afp
+    'clcg_hip_csr_ax_c64' or a callable (instance, x_ptr, Ax_ptr, n, layout, conjugate)."""
+    lib = L.load()
+    a, k1 = _cb(Afp, CAXFUNC); p, k2 = _cb(Pfp, CPROGRESS_C64)
+    pm, pb, mem = _c64_vectors(m, B)
+    rc = lib.clcg_hip_solver_c64(a, p, pm, pb, n_size, C.byref(param) if param is not None else None,
+                                 _instance(instance), solver_id, mem)
+    _chk(rc, "clcg_solver_c64")
+    return SolveInfo(rc, lib.lcg_hip_last_iterations(), lib.lcg_hip_last_residual())
+
+
+def clcg_solver_preconditioned_c64(Afp, Mfp, Pfp, m, B, n_size, param, instance, solver_id=CLCG_PCG) -> SolveInfo:
+    """clcg_solver_preconditioned_cuda() of clcg_cudaf.cu -> clpcg in complex64; Mfp e.g. 'clcg_hip_jacobi_mx_c64'."""
+    lib = L.load()
+    a, k1 = _cb(Afp, CAXFUNC); mm, k3 = _cb(Mfp, CAXFUNC); p, k2 = _cb(Pfp, CPROGRESS_C64)
+    pm, pb, mem = _c64_vectors(m, B)
+    rc = lib.clcg_hip_solver_preconditioned_c64(a, mm, p, pm, pb, n_size, C.byref(param) if param is not None else None,
+                                                _instance(instance), solver_id, mem)
+    _chk(rc, "clcg_solver_preconditioned_c64")
     return SolveInfo(rc, lib.lcg_hip_last_iterations(), lib.lcg_hip_last_residual())
 
 

@@ -1121,6 +1121,7 @@ int lcg_hip_comm_size(void) { return g_comm.nranks; }
 int lcg_hip_csr_distribute(lcg_hip_csr_t A, int64_t n_global, int mode)
 {
     if (!A || n_global <= 0) return LCG_HIP_E_ARG;
+    TRY_C64(A, "lcg_hip_csr_distribute");
     if (mode < 0 || mode > 2) return LCG_HIP_E_ARG;
     if (mode != 2 && !g_comm.comm && world_size() > 1) {
         ctx().err = "modes 0 and 1 move x with RCCL: no communicator (lcg_hip_comm_init)";
@@ -1163,6 +1164,7 @@ int lcg_hip_csr_need_ranges_for_test(lcg_hip_csr_t A, int nranks, int64_t *lohi)
 int lcg_hip_csr_split_for_test(lcg_hip_csr_t A, int64_t n_global, int nranks, int rank)
 {
     if (!A) return LCG_HIP_E_ARG;
+    TRY_C64(A, "lcg_hip_csr_split_for_test");
     return dist_split(A, n_global, nranks, rank);
 }
 

@@ -1578,7 +1578,7 @@ int csr_ax_dot(lcg_hip_csr *A, const double *x, double *y, const double *u, int 
                const int *done)
 {
     static const bool off = [] { const char *e = std::getenv("LCG_HIP_AX_DOT"); return e && atoi(e) == 0; }();
-    if (off || !A || A->is_complex || A->n_rows <= 0) return 0;
+    if (off || !A || A->is_complex || A->c64 || A->n_rows <= 0) return 0;
     if (A->distributed) return dist_ax_dot(A, x, y, u, yy, part, slots);
     const CsrPart &P = A->main;
     const int n = P.n_rows;
@@ -1686,6 +1686,7 @@ int lcg_hip_csr_destroy(lcg_hip_csr_t A)
     for (int i = 1; i < 4; i++) free_part(A->op[i]);
     if (A->invdiag) hipFree(A->invdiag);
     ic0_free(A);
+    c64_free(A);
     delete A;
     return 0;
 }
@@ -1703,6 +1704,7 @@ int lcg_hip_csr_arrays(lcg_hip_csr_t A, const int **rowptr, const int **col, con
 int lcg_hip_csr_set_kernel(lcg_hip_csr_t A, int variant)
 {
     if (!A) return LCG_HIP_E_ARG;
+    TRY_C64(A, "lcg_hip_csr_set_kernel");
     A->variant = variant;
     return 0;
 }
@@ -1710,6 +1712,7 @@ int lcg_hip_csr_set_kernel(lcg_hip_csr_t A, int variant)
 int lcg_hip_csr_set_packed(lcg_hip_csr_t A, int mode)
 {
     if (!A || mode < -1 || mode > 1) return LCG_HIP_E_ARG;
+    TRY_C64(A, "lcg_hip_csr_set_packed");
     for (CsrPart *P : {&A->main, &A->loc}) {
         P->pk_mode = mode;
         ranges_free(*P);                    // the ranges inherit the modes: cut again at the next product
@@ -1726,6 +1729,7 @@ int lcg_hip_csr_set_packed(lcg_hip_csr_t A, int mode)
 int lcg_hip_csr_set_binned(lcg_hip_csr_t A, int mode)
 {
     if (!A || mode < -1 || mode > 1) return LCG_HIP_E_ARG;
+    TRY_C64(A, "lcg_hip_csr_set_binned");
     for (CsrPart *P : {&A->main, &A->loc}) {
         P->bn_mode = mode;
         ranges_free(*P);                    // the ranges inherit the modes: cut again at the next product
@@ -1738,6 +1742,7 @@ int lcg_hip_csr_set_binned(lcg_hip_csr_t A, int mode)
 int lcg_hip_csr_set_tiled(lcg_hip_csr_t A, int mode)
 {
     if (!A || mode < -1 || mode > 1) return LCG_HIP_E_ARG;
+    TRY_C64(A, "lcg_hip_csr_set_tiled");
     for (CsrPart *P : {&A->main, &A->loc}) {
         P->tl_mode = mode;
         ranges_free(*P);                    // the ranges inherit the modes: cut again at the next product
@@ -1750,6 +1755,7 @@ int lcg_hip_csr_set_tiled(lcg_hip_csr_t A, int mode)
 int lcg_hip_csr_set_ranges(lcg_hip_csr_t A, int mode)
 {
     if (!A || mode < -1 || mode > 1) return LCG_HIP_E_ARG;
+    TRY_C64(A, "lcg_hip_csr_set_ranges");
     if (ctx().inited) (void)hipDeviceSynchronize();
     for (CsrPart *P : {&A->main, &A->loc}) { ranges_free(*P); P->rg_mode = mode; }
     return 0;
@@ -1826,7 +1832,7 @@ int64_t lcg_hip_csr_packed_templates(lcg_hip_csr_t A)
 
 int64_t lcg_hip_csr_last_traffic_model(lcg_hip_csr_t A)
 {
-    if (!A || A->is_complex) return 0;
+    if (!A || A->is_complex || A->c64) return 0;
     return part_traffic_model(A->distributed ? A->loc : A->main);
 }
 
@@ -1875,6 +1881,7 @@ void lcg_hip_jacobi_mx(void *instance, const double *x, double *z, const int n)
 int lcg_hip_spmv_op(lcg_hip_csr_t A, const double *x, double *y, int layout, int conjugate)
 {
     if (!A || !x || !y) return LCG_HIP_E_ARG;
+    TRY_C64(A, "lcg_hip_spmv_op");
     if (!layout && (!conjugate || !A->is_complex)) return lcg_hip_spmv(A, x, y);
     Ctx &c = ctx();
     const CsrPart *P = nullptr;
@@ -1889,6 +1896,7 @@ int lcg_hip_spmv_op(lcg_hip_csr_t A, const double *x, double *y, int layout, int
 int lcg_hip_spmv(lcg_hip_csr_t A, const double *x, double *y)
 {
     if (!A || !x || !y) return LCG_HIP_E_ARG;
+    TRY_C64(A, "lcg_hip_spmv");
     Ctx &c = ctx();
     if (A->distributed) return dist_spmv(A, x, y);
     return spmv_launch(A->main, A->is_complex, A->variant, A->mean_row, x, y, false, c.stream,

@@ -68,6 +68,7 @@ template <class Op> static int launch_vec(Op op, long n, uintptr_t align_or, hip
 
 int jacobi_launch(const lcg_hip_csr *A, const double *x, double *z, int n, hipStream_t s)
 {
+    TRY_C64(A, "the Jacobi callback (lcg_hip_jacobi_mx / clcg_hip_jacobi_mx)");
     if (!A->invdiag) return fail(hipErrorInvalidValue, "lcg_hip_csr_build_jacobi() was not called", __FILE__, __LINE__);
     if (A->is_complex) {
         hipLaunchKernelGGL(k_cmul, dim3(grid_for(n)), dim3(VB), 0, s, (long)n,
@@ -476,6 +477,7 @@ void row_sort_launch(int n, const int *rowptr, int *col, double *val, bool cplx,
 // part of `A` that realises op(A); built on first use.  layout/conjugate as in algebra.h:31-50.
 int op_part(lcg_hip_csr *A, int layout, int conjugate, const CsrPart **out)
 {
+    TRY_C64(A, "op(A)");
     if (!A->is_complex) conjugate = 0;
     const int idx = (layout ? 2 : 0) + (conjugate ? 1 : 0);
     if (idx == 0) { *out = &A->main; return 0; }
@@ -615,6 +617,7 @@ int lcg_hip_csr_from_coo(lcg_hip_csr_t *out, int n, int64_t nnz, const int *row,
 int lcg_hip_csr_build_jacobi(lcg_hip_csr_t A, double *diag_out)
 {
     if (!A) return LCG_HIP_E_ARG;
+    if (A->c64) return c64_build_jacobi(A, diag_out);
     Ctx &c = ctx();
     const size_t w = A->is_complex ? 2 : 1;
     if (!A->invdiag) HIPCHK(hipMalloc(&A->invdiag, sizeof(double) * w * (size_t)A->n_rows));

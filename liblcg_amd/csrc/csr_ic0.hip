@@ -375,6 +375,7 @@ static int arg_error(const char *fmt, long v = 0)
 static int ic0_call(lcg_hip_csr *A, bool cplx, int which, const double *x, double *y, long n_size)
 {
     if (!A || !x || !y) return LCG_HIP_E_ARG;
+    TRY_C64(A, "IC(0) apply");
     const Ic0 *F = ic0_of(A);
     if (!F || !F->ok) return arg_error("IC(0): the handle has no factor (lcg_hip_csr_build_ic0)");
     if (F->cplx != cplx) return arg_error(cplx ? "IC(0): complex callback on a real factor" : "IC(0): real callback on a complex factor");
@@ -396,6 +397,7 @@ extern "C" {
 int lcg_hip_csr_build_ic0(lcg_hip_csr_t A)
 {
     if (!A) return LCG_HIP_E_ARG;
+    TRY_C64(A, "lcg_hip_csr_build_ic0");
     if (A->distributed) return arg_error("IC(0): not available on a sharded matrix");
     if (A->n_cols != A->n_rows) return arg_error("IC(0): the matrix is not square");
     int rc = ensure_init(); if (rc) return rc;

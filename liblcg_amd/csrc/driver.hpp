@@ -430,7 +430,7 @@ struct Placement {
     {
         if (c.place_mode == 0 || afp != (const void *)lcg_hip_csr_ax || inst == nullptr) return false;
         const lcg_hip_csr *A = static_cast<const lcg_hip_csr *>(inst);
-        if (A->is_complex || n != A->n_rows || n < 4096) return false;
+        if (A->is_complex || A->c64 || n != A->n_rows || n < 4096) return false;
         return c.place_mode > 0 || streams(c, A);
     }
     // the rows this process multiplies by itself: the whole matrix, or -- sharded -- the entries with locally owned columns

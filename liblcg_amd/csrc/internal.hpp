@@ -331,6 +331,9 @@ struct lcg_hip_csr {
     void *halo = nullptr;       // neighbour-exchange plan (comm.hip)
     void *direct = nullptr;     // direct (peer-mapped) exchange state (comm.hip, mode 2)
     void *ic0 = nullptr;        // incomplete-Cholesky factor and its level schedules (csr_ic0.hip), a copy: built by lcg_hip_csr_build_ic0
+    // --- complex64 values (csr_c64.hip) ---
+    bool c64 = false;           // main.val holds n_nnz interleaved (re, im) floats (8 B per entry); is_complex stays false
+    void *c64p = nullptr;       // the products' plans and the Jacobi reciprocals of such a matrix (csr_c64.hip: C64Data)
 };
 
 namespace lcgh {
@@ -377,6 +380,21 @@ void row_sort_launch(int n, const int *rowptr, int *col, double *val, bool cplx,
 void ic0_free(lcg_hip_csr *A);
 // csr.hip
 void free_part(CsrPart &P);                                          // a part's arrays and every plan built beside them
+
+// csr_c64.hip
+void c64_free(lcg_hip_csr *A);
+int c64_build_jacobi(lcg_hip_csr *A, void *diag_out);
+const float *c64_builtin_invdiag(const void *Mfp, void *inst, int n);     // the reciprocals behind clcg_hip_jacobi_mx_c64 (else null)
+// An entry that serves fp64 / complex128 matrices only, handed a complex64 one: LCG_HIP_E_ARG with lcg_hip_last_error() naming the
+// entry (0: A may be used).  The bytes of such a matrix are never read as doubles.
+inline int refuse_c64(const lcg_hip_csr *A, const char *entry)
+{
+    if (!A || !A->c64) return 0;
+    ctx().err = std::string(entry) + ": the matrix holds complex64 values; this entry serves fp64 and complex128 matrices "
+                "(complex64: lcg_hip_spmv_c64, clcg_hip_csr_ax_c64, clcg_hip_jacobi_mx_c64)";
+    return LCG_HIP_E_ARG;
+}
+#define TRY_C64(A, entry) do { int rc_ = ::lcgh::refuse_c64((A), (entry)); if (rc_) return rc_; } while (0)
 
 // comm.hip
 int comm_allreduce(double *dev, int count, hipStream_t s);
