@@ -1,7 +1,8 @@
 // sample_csr_c64.cpp -- liblcg's sample14.cu on the complex64 entries: the bundled complex system case_10K_cA cast to single
 // precision (sample14.cu:154-170), solved with BiCG for complex-symmetric A and with PCG, and the error against case_10K_cB
 // reported as sample14 does (avg_error, sample14.cu:71-81).  sample14 preconditions its PCG with an fp32 IC(0); this one uses
-// the ready-made Jacobi (clcg_hip_jacobi_mx_c64).  Plain C++ on the C ABI: no HIP headers, no vendor handles.
+// the ready-made Jacobi (clcg_hip_jacobi_mx_c64), and sample_csr_c64_ic0.cpp runs sample14's IC(0) leg.  Plain C++ on the C ABI:
+// no HIP headers, no vendor handles.
 //
 //   g++ -O2 -std=c++11 -Iinclude examples/sample_csr_c64.cpp -Lliblcg_amd/lib -llcg_hip
 //       -Wl,-rpath,$PWD/liblcg_amd/lib -o sample_csr_c64 && ./sample_csr_c64 tests/golden

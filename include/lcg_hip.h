@@ -245,7 +245,8 @@ int clcg_hip_solver_c64(clcg_hip_axfunc_c64_ptr Afp, clcg_hip_progress_c64_ptr P
                         int n_size, const clcg_para *param, void *instance, int solver_id, int mem);
 /* clcg_solver_preconditioned_cuda (clcg_cudaf.cu:66-84): CLCG_PCG runs clpcg (:403-558: unconjugated dots, complex-symmetric A),
  * any other id returns CLCG_UNKNOWN_SOLVER; Mfp == NULL returns LCG_NULL_PRECONDITION_MATRIX.  clcg_hip_jacobi_mx_c64 is the
- * ready-made Jacobi (its reciprocal multiply then rides in the update pass). */
+ * ready-made Jacobi (its reciprocal multiply then rides in the update pass); clcg_hip_ic0_mx_c64, after
+ * lcg_hip_csr_build_ic0_c64, the ready-made fp32 IC(0) (sample14.cu's MxProduct). */
 int clcg_hip_solver_preconditioned_c64(clcg_hip_axfunc_c64_ptr Afp, clcg_hip_axfunc_c64_ptr Mfp, clcg_hip_progress_c64_ptr Pfp,
                                        float *m, const float *B, int n_size, const clcg_para *param, void *instance,
                                        int solver_id, int mem);
@@ -268,10 +269,11 @@ int lcg_hip_csr_create(lcg_hip_csr_t *A, int n_rows, int n_cols, int64_t nnz, co
                        const int *col, const double *val, int is_complex, int mem, int adopt);
 /* The same with complex64 values: val = nnz interleaved (re, im) floats (cuComplex; the CUDA_C_32F matrix of clcg_cudaf.cu's
  * callers, sample14.cu).  Copy / adopt as lcg_hip_csr_create (adopt == 2: 64 readable bytes behind col[nnz] and val[nnz]).
- * Such a handle serves lcg_hip_spmv_c64, clcg_hip_csr_ax_c64, clcg_hip_jacobi_mx_c64, lcg_hip_csr_build_jacobi and the
- * read-only queries (lcg_hip_csr_arrays then hands back `val` typed const double *: it points to nnz interleaved float pairs --
+ * Such a handle serves lcg_hip_spmv_c64, clcg_hip_csr_ax_c64, clcg_hip_jacobi_mx_c64, lcg_hip_csr_build_jacobi, the complex64
+ * IC(0) entries (lcg_hip_csr_build_ic0_c64, lcg_hip_ic0_solve_c64, clcg_hip_ic0_mx_c64) and the read-only queries
+ * (lcg_hip_csr_arrays and lcg_hip_csr_ic0_factor then hand back `val` typed const double *: it points to interleaved float pairs --
  * cast it to const float *); every other entry that takes a matrix (set_kernel / packed / binned / tiled / ranges, distribute, build_ic0,
- * lcg_hip_spmv, lcg_hip_spmv_op, lcg_hip_spmv_dot) and the fp64 / c128 ready-made callbacks return LCG_HIP_E_ARG
+ * lcg_hip_ic0_solve, lcg_hip_spmv, lcg_hip_spmv_op, lcg_hip_spmv_dot) and the fp64 / c128 ready-made callbacks return LCG_HIP_E_ARG
  * (lcg_hip_last_error() says why); a c128 or real handle in the _c64 entries likewise.  Not shardable. */
 int lcg_hip_csr_create_c64(lcg_hip_csr_t *A, int n_rows, int n_cols, int64_t nnz, const int *rowptr,
                            const int *col, const float *val, int mem, int adopt);
@@ -372,7 +374,8 @@ void clcg_hip_csr_ax(void *instance, const double *x, double *prod_Ax, const int
 void clcg_hip_jacobi_mx(void *instance, const double *x, double *prod_Mx, const int n_size,
                         int layout, int conjugate);                                             /* sample10.cu:99-120 (Jacobi branch) */
 /* The complex64 ones.  clcg_hip_csr_ax_c64 = lcg_hip_spmv_c64 (all four forms; sample14.cu's cusparseSpMV callback);
- * clcg_hip_jacobi_mx_c64: z = x .* (1 / diag) after lcg_hip_csr_build_jacobi, layout / conjugate ignored. */
+ * clcg_hip_jacobi_mx_c64: z = x .* (1 / diag) after lcg_hip_csr_build_jacobi, layout / conjugate ignored.  (The fp32 IC(0)
+ * callback, clcg_hip_ic0_mx_c64, is declared with the IC(0) entries below.) */
 void clcg_hip_csr_ax_c64(void *instance, const float *x, float *prod_Ax, const int n_size,
                          int layout, int conjugate);
 void clcg_hip_jacobi_mx_c64(void *instance, const float *x, float *prod_Mx, const int n_size,
@@ -385,23 +388,39 @@ void clcg_hip_jacobi_mx_c64(void *instance, const float *x, float *prod_Mx, cons
  * adopted matrix), freed by lcg_hip_csr_destroy.  Rebuilds on repeat.  LCG_HIP_E_ARG for a non-square or sharded matrix or a
  * failed pivot (<= 0 or not finite, real; 0 or not finite, complex): lcg_hip_last_error() names the smallest such row.
  * Stands in for cusparseDcsric02 (sample8.cu:183-238), cusparseZcsric02 (sample10.cu:226-266) and
- * clcg_incomplete_Cholesky_cuda_full (preconditioner_cuda.cu:207-259; sample12.cu:153, sample13.cu:156). */
+ * clcg_incomplete_Cholesky_cuda_full (preconditioner_cuda.cu:207-259; sample12.cu:153, sample13.cu:156).
+ * Serves fp64 and complex128 handles; a complex64 handle returns LCG_HIP_E_ARG (its entry is lcg_hip_csr_build_ic0_c64). */
 int  lcg_hip_csr_build_ic0(lcg_hip_csr_t A);
+/* The same for a handle from lcg_hip_csr_create_c64, in fp32 complex arithmetic throughout (cuCmulf / cuCdivf's products and
+ * quotients, the principal fp32 square root; the order of operations of the other types): the same rules (square, not
+ * sharded, rebuild on repeat, LCG_HIP_E_ARG naming the smallest failed pivot row: 0 or not finite).  A real or complex128
+ * handle returns LCG_HIP_E_ARG.  Stands in for clcg_incomplete_Cholesky_cuda_half with cuComplex (preconditioner_cuda.cu;
+ * sample14.cu). */
+int  lcg_hip_csr_build_ic0_c64(lcg_hip_csr_t A);
 /* Levels of L and L^T, kernel launches of one full apply, the failed pivot's row (-1 = none; what
- * cusparseXcsric02_zeroPivot reports), host milliseconds of the build, device bytes held by the factor.  Any pointer may be NULL. */
+ * cusparseXcsric02_zeroPivot reports), host milliseconds of the build, device bytes held by the factor.  Any pointer may be NULL.
+ * This, lcg_hip_csr_ic0_factor and lcg_hip_csr_ic0_schedule_for_test serve every value type. */
 int  lcg_hip_csr_ic0_info(lcg_hip_csr_t A, int *levels_lower, int *levels_upper, int *launches_per_apply,
                           int *zero_pivot, double *build_ms, int64_t *bytes);
-/* Device arrays of L in natural row order: rows sorted by column, the diagonal last. */
+/* Device arrays of L in natural row order: rows sorted by column, the diagonal last.  For a complex64 factor `val` points to
+ * interleaved float pairs (cast it to const float *, as for lcg_hip_csr_arrays). */
 int  lcg_hip_csr_ic0_factor(lcg_hip_csr_t A, const int **rowptr, const int **col, const double **val);
 /* y = L^-1 x (which 0), L^-T x (1) or (L.L^T)^-1 x (2) on the current stream; x, y on the device and not overlapping
  * (cusparseDcsrsv2_solve, sample8.cu:105-119; cusparseSpSV, sample12.cu:153). */
 int  lcg_hip_ic0_solve(lcg_hip_csr_t A, int which, const double *x, double *y);
+/* The same for a complex64 factor (lcg_hip_csr_build_ic0_c64), fp32 throughout, with the same checks (which, overlap, factor
+ * present; another handle type: LCG_HIP_E_ARG).  cusparseSpSV with CUDA_C_32F (sample14.cu). */
+int  lcg_hip_ic0_solve_c64(lcg_hip_csr_t A, int which, const float *x, float *y);
 /* Ready-made preconditioner callbacks, z = (L.L^T)^-1 x; pass the lcg_hip_csr_t as `instance`.  A handle without a factor, the
  * wrong value type, n_size other than the row count or conjugate = 1 end the solve with LCG_HIP_E_ARG; layout is ignored
  * (M is (complex-)symmetric). */
 void lcg_hip_ic0_mx(void *instance, const double *x, double *prod_Mx, const int n_size);          /* sample8.cu:105-119 */
 void clcg_hip_ic0_mx(void *instance, const double *x, double *prod_Mx, const int n_size,
                      int layout, int conjugate);                                                  /* sample10.cu:99-120 (IC branch) */
+/* The complex64 one, for clcg_hip_solver_preconditioned_c64 (sample14.cu's MxProduct: the SpSV with L, then with L^T).  Neither
+ * allocates nor synchronises; honours the solve's stop flag. */
+void clcg_hip_ic0_mx_c64(void *instance, const float *x, float *prod_Mx, const int n_size,
+                         int layout, int conjugate);
 /* Test hook: the widest level a one-workgroup launch may take over several levels (0: one launch per level; -1: production). */
 int  lcg_hip_csr_ic0_schedule_for_test(lcg_hip_csr_t A, int max_merged_rows);
 

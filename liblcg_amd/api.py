@@ -169,8 +169,12 @@ class CsrMatrix:
 
     # -- IC(0) preconditioner (csr_ic0.hip) -------------------------------------------------
     def build_ic0(self):
-        """Factor A ~ L.L^T with zero fill on the device; pass "lcg_hip_ic0_mx" / "clcg_hip_ic0_mx" as Mfp afterwards."""
-        _chk(L.load().lcg_hip_csr_build_ic0(self.h), "build_ic0")
+        """Factor A ~ L.L^T with zero fill on the device; pass "lcg_hip_ic0_mx" / "clcg_hip_ic0_mx" (a complex64 matrix:
+        "clcg_hip_ic0_mx_c64", factored in fp32) as Mfp afterwards."""
+        if self.is_c64:
+            _chk(L.load().lcg_hip_csr_build_ic0_c64(self.h), "build_ic0_c64")
+        else:
+            _chk(L.load().lcg_hip_csr_build_ic0(self.h), "build_ic0")
 
     def ic0_info(self) -> dict:
         ll, lu, la, zp = C.c_int(), C.c_int(), C.c_int(), C.c_int()
@@ -181,7 +185,8 @@ class CsrMatrix:
                 "zero_pivot": zp.value, "build_ms": ms.value, "bytes": nb.value}
 
     def ic0_factor_to_host(self):
-        """(rowptr, col, val) of L copied to numpy: natural row order, rows sorted, the diagonal last."""
+        """(rowptr, col, val) of L copied to numpy: natural row order, rows sorted, the diagonal last (complex64 values for
+        a complex64 matrix)."""
         lib = L.load()
         pr, pc, pv = C.c_void_p(), C.c_void_p(), C.c_void_p()
         _chk(lib.lcg_hip_csr_ic0_factor(self.h, C.byref(pr), C.byref(pc), C.byref(pv)), "ic0_factor")
@@ -189,14 +194,17 @@ class CsrMatrix:
         _chk(lib.lcg_hip_memcpy(rowptr.ctypes.data, pr, rowptr.nbytes, 2), "memcpy d2h")
         nnz = int(rowptr[-1])
         col = np.empty(nnz, np.int32)
-        val = np.empty(nnz, np.complex128 if self.is_complex else np.float64)
+        val = np.empty(nnz, np.complex64 if self.is_c64 else np.complex128 if self.is_complex else np.float64)
         for dst, src in ((col, pc), (val, pv)):
             _chk(lib.lcg_hip_memcpy(dst.ctypes.data, src, dst.nbytes, 2), "memcpy d2h")
         return rowptr, col, val
 
     def ic0_solve(self, x, y, which=2):
         """y = L^-1 x (which 0), L^-T x (1) or (L.L^T)^-1 x (2); device tensors, on the library's stream."""
-        _chk(L.load().lcg_hip_ic0_solve(self.h, which, _ptr(x)[0], _ptr(y)[0]), "ic0_solve")
+        if self.is_c64:
+            _chk(L.load().lcg_hip_ic0_solve_c64(self.h, which, _ptr(x)[0], _ptr(y)[0]), "ic0_solve_c64")
+        else:
+            _chk(L.load().lcg_hip_ic0_solve(self.h, which, _ptr(x)[0], _ptr(y)[0]), "ic0_solve")
 
     def spmv(self, x, y):
         _chk(L.load().lcg_hip_spmv(self.h, _ptr(x)[0], _ptr(y)[0]), "spmv")
@@ -354,7 +362,8 @@ def clcg_solver_c64(Afp, Pfp, m, B, n_size, param, instance, solver_id=CLCG_BICG
 
 
 def clcg_solver_preconditioned_c64(Afp, Mfp, Pfp, m, B, n_size, param, instance, solver_id=CLCG_PCG) -> SolveInfo:
-    """clcg_solver_preconditioned_cuda() of clcg_cudaf.cu -> clpcg in complex64; Mfp e.g. 'clcg_hip_jacobi_mx_c64'."""
+    """clcg_solver_preconditioned_cuda() of clcg_cudaf.cu -> clpcg in complex64; Mfp e.g. 'clcg_hip_jacobi_mx_c64' or, after
+    build_ic0(), 'clcg_hip_ic0_mx_c64'."""
     lib = L.load()
     a, k1 = _cb(Afp, CAXFUNC); mm, k3 = _cb(Mfp, CAXFUNC); p, k2 = _cb(Pfp, CPROGRESS_C64)
     pm, pb, mem = _c64_vectors(m, B)

@@ -12,11 +12,20 @@
 // ONE launch of one workgroup that walks those levels with a barrier between them (workgroup-scope visibility only: no flag,
 // no wait on another workgroup).  Every row is computed by one thread in one fixed order -- s = x_i, minus L(i,k).y_k in
 // column order, divided by L(i,i) -- so results are the same bits from call to call and under every grouping of the levels.
+//
+// value types: double (real), double2 (complex128) and float2 (complex64: clcg_incomplete_Cholesky_cuda_half's cuComplex
+// overload, preconditioner_cuda.cu, and the two cusparseSpSV solves with CUDA_C_32F of sample14.cu).  The complex64 factor and
+// solves are fp32 throughout: products by c64_mul, quotients by c64_div (cuCdivf's scaled formula, c64common.hpp), the
+// principal root by csqrt_principal_f, in the same order of operations as the other two types.  Its values are 8 bytes, so
+// the build moves them with the real type's helpers as opaque 8-byte words (alloc_part / row_sort_launch / transpose_launch with
+// cplx = false).  k_row_sort breaks ties between duplicate (row, column) entries on those words: duplicates are summed in a
+// fixed order unless an imaginary part is Inf / NaN.  (L^T has no duplicate columns.)
 #include <chrono>
 #include <cmath>
 #include <numeric>
 
 #include "devcommon.hpp"
+#include "c64common.hpp"
 
 namespace lcgh {
 
@@ -34,9 +43,10 @@ struct IcTri {                                  // one triangle's schedule
 struct Ic0 {
     int n = 0;
     bool cplx = false, ok = false;
+    bool c64 = false;           // complex64 values (8 bytes: cplx stays false, so the build moves them as real words)
     CsrPart L, LT;              // L: rows sorted, diagonal last; L^T: rows sorted, diagonal first
     IcTri fw, bw;
-    double *tmp = nullptr;      // L^-1 x of the full apply (n values)
+    double *tmp = nullptr;      // L^-1 x of the full apply (n values of the factor's type)
     int *zp = nullptr;          // device: smallest row whose pivot failed (INT_MAX: none)
     int zero_pivot = -1;
     int max_merged = IC_WG;     // widest level a narrow group takes (lcg_hip_csr_ic0_schedule_for_test)
@@ -94,14 +104,29 @@ __device__ __forceinline__ double2 csqrt_principal(double2 z)
     const double t = sqrt(0.5 * (r - z.x));
     return make_double2(fabs(z.y) / (2.0 * t), copysign(t, z.y));
 }
+__device__ __forceinline__ float2 csqrt_principal_f(float2 z)     // the same branches in fp32 (std::sqrt(std::complex<float>))
+{
+    if (z.x == 0.0f && z.y == 0.0f) return make_float2(0.0f, z.y);
+    const float r = hypotf(z.x, z.y);
+    if (z.x >= 0.0f) {
+        const float t = sqrtf(0.5f * (r + z.x));
+        return make_float2(t, z.y / (2.0f * t));
+    }
+    const float t = sqrtf(0.5f * (r - z.x));
+    return make_float2(fabsf(z.y) / (2.0f * t), copysignf(t, z.y));
+}
 __device__ __forceinline__ double ic_sqrt(double d) { return sqrt(d); }
 __device__ __forceinline__ double2 ic_sqrt(double2 d) { return csqrt_principal(d); }
+__device__ __forceinline__ float2 ic_sqrt(float2 d) { return csqrt_principal_f(d); }
 __device__ __forceinline__ bool pivot_fails(double d) { return !(d > 0.0) || !isfinite(d); }
 __device__ __forceinline__ bool pivot_fails(double2 d) { return (d.x == 0.0 && d.y == 0.0) || !isfinite(d.x) || !isfinite(d.y); }
+__device__ __forceinline__ bool pivot_fails(float2 d) { return (d.x == 0.0f && d.y == 0.0f) || !isfinite(d.x) || !isfinite(d.y); }
 __device__ __forceinline__ double ic_mul(double a, double b) { return a * b; }
 __device__ __forceinline__ double2 ic_mul(double2 a, double2 b) { return cmul(a, b); }
+__device__ __forceinline__ float2 ic_mul(float2 a, float2 b) { return c64_mul(a, b); }
 __device__ __forceinline__ double ic_div(double a, double b) { return a / b; }
 __device__ __forceinline__ double2 ic_div(double2 a, double2 b) { return cdiv(a, b); }
+__device__ __forceinline__ float2 ic_div(float2 a, float2 b) { return c64_div(a, b); }
 
 // Row i of L in place (val holds A's lower triangle on entry).  L(i,j) = (A(i,j) - sum_{k<j} L(i,k) L(j,k)) / L(j,j) by a sorted
 // merge of row i's prefix with row j, then L(i,i) = sqrt(A(i,i) - sum_k L(i,k)^2).  Rows j < i are final (earlier levels).
@@ -371,21 +396,46 @@ static int arg_error(const char *fmt, long v = 0)
     return LCG_HIP_E_ARG;
 }
 
-// the apply behind the callbacks and lcg_hip_ic0_solve: checks, then two triangular solves on the library's stream
-static int ic0_call(lcg_hip_csr *A, bool cplx, int which, const double *x, double *y, long n_size)
+// the apply behind the callbacks and the solve entries: checks, then two triangular solves on the library's stream.
+// c64: the complex64 entries (a complex64 handle only); otherwise cplx picks the fp64 or the complex128 factor.
+static int ic0_call(lcg_hip_csr *A, bool cplx, bool c64, int which, const double *x, double *y, long n_size)
 {
     if (!A || !x || !y) return LCG_HIP_E_ARG;
-    TRY_C64(A, "IC(0) apply");
+    if (!c64) TRY_C64(A, "IC(0) apply");
+    else if (!A->c64) return arg_error("IC(0): a complex64 entry on a fp64 / complex128 handle (lcg_hip_ic0_solve, lcg_hip_ic0_mx, clcg_hip_ic0_mx)");
     const Ic0 *F = ic0_of(A);
-    if (!F || !F->ok) return arg_error("IC(0): the handle has no factor (lcg_hip_csr_build_ic0)");
+    if (!F || !F->ok) return arg_error(c64 ? "IC(0): the handle has no factor (lcg_hip_csr_build_ic0_c64)" : "IC(0): the handle has no factor (lcg_hip_csr_build_ic0)");
+    if (F->c64 != c64) return arg_error("IC(0): the factor's value type differs from the entry's");
     if (F->cplx != cplx) return arg_error(cplx ? "IC(0): complex callback on a real factor" : "IC(0): real callback on a complex factor");
     if (n_size >= 0 && n_size != F->n) return arg_error("IC(0): n_size differs from the factor's %ld rows", F->n);
     if (which < 0 || which > 2) return arg_error("IC(0): which = %ld (0, 1 or 2)", which);
-    const size_t bytes = sizeof(double) * (cplx ? 2 : 1) * (size_t)F->n;
+    const size_t bytes = (c64 ? sizeof(float2) : sizeof(double) * (cplx ? 2 : 1)) * (size_t)F->n;
     if ((const char *)x < (const char *)y + bytes && (const char *)y < (const char *)x + bytes)
         return arg_error("IC(0): x and y overlap");
     Ctx &c = ctx();
+    if (c64) return ic0_apply<float2>(F, which, x, y, c.stream, ax_flag(c));
     return cplx ? ic0_apply<double2>(F, which, x, y, c.stream, ax_flag(c)) : ic0_apply<double>(F, which, x, y, c.stream, ax_flag(c));
+}
+
+// the build behind lcg_hip_csr_build_ic0 and lcg_hip_csr_build_ic0_c64 (the handle's type already checked)
+static int ic0_build_entry(lcg_hip_csr *A)
+{
+    if (A->distributed) return arg_error("IC(0): not available on a sharded matrix");
+    if (A->n_cols != A->n_rows) return arg_error("IC(0): the matrix is not square");
+    int rc = ensure_init(); if (rc) return rc;
+    Ctx &c = ctx();
+    const auto t0 = std::chrono::steady_clock::now();
+    int max_merged = IC_WG;
+    if (A->ic0) { max_merged = ic0_of(A)->max_merged; ic0_free(A); }
+    Ic0 *F = new Ic0();
+    F->n = A->n_rows; F->cplx = A->is_complex; F->c64 = A->c64; F->max_merged = max_merged;
+    A->ic0 = F;
+    rc = F->c64 ? ic0_build<float2>(A, F, c.stream) : F->cplx ? ic0_build<double2>(A, F, c.stream) : ic0_build<double>(A, F, c.stream);
+    F->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (rc) { ic0_free(A); return rc; }
+    if (F->zero_pivot >= 0) return arg_error("IC(0): the pivot of row %ld is not usable (zero, negative or not finite)", F->zero_pivot);
+    F->ok = true;
+    return 0;
 }
 
 } // namespace lcgh
@@ -398,22 +448,16 @@ int lcg_hip_csr_build_ic0(lcg_hip_csr_t A)
 {
     if (!A) return LCG_HIP_E_ARG;
     TRY_C64(A, "lcg_hip_csr_build_ic0");
-    if (A->distributed) return arg_error("IC(0): not available on a sharded matrix");
-    if (A->n_cols != A->n_rows) return arg_error("IC(0): the matrix is not square");
+    return ic0_build_entry(A);
+}
+
+int lcg_hip_csr_build_ic0_c64(lcg_hip_csr_t A)
+{
     int rc = ensure_init(); if (rc) return rc;
-    Ctx &c = ctx();
-    const auto t0 = std::chrono::steady_clock::now();
-    int max_merged = IC_WG;
-    if (A->ic0) { max_merged = ic0_of(A)->max_merged; ic0_free(A); }
-    Ic0 *F = new Ic0();
-    F->n = A->n_rows; F->cplx = A->is_complex; F->max_merged = max_merged;
-    A->ic0 = F;
-    rc = F->cplx ? ic0_build<double2>(A, F, c.stream) : ic0_build<double>(A, F, c.stream);
-    F->build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (rc) { ic0_free(A); return rc; }
-    if (F->zero_pivot >= 0) return arg_error("IC(0): the pivot of row %ld is not usable (zero, negative or not finite)", F->zero_pivot);
-    F->ok = true;
-    return 0;
+    if (!A) return LCG_HIP_E_ARG;
+    if (!A->c64) return arg_error("lcg_hip_csr_build_ic0_c64: the handle is not a complex64 matrix (lcg_hip_csr_create_c64; "
+                                  "fp64 / complex128 handles: lcg_hip_csr_build_ic0)");
+    return ic0_build_entry(A);
 }
 
 int lcg_hip_csr_ic0_info(lcg_hip_csr_t A, int *levels_lower, int *levels_upper, int *launches_per_apply, int *zero_pivot,
@@ -427,7 +471,7 @@ int lcg_hip_csr_ic0_info(lcg_hip_csr_t A, int *levels_lower, int *levels_upper, 
     if (zero_pivot) *zero_pivot = F->zero_pivot;
     if (build_ms) *build_ms = F->build_ms;
     if (bytes) {
-        const int64_t vw = F->cplx ? 16 : 8;
+        const int64_t vw = F->cplx ? 16 : 8;                                     // (complex64: 8, one float pair)
         *bytes = 2 * (4 * ((int64_t)F->n + 1) + (4 + vw) * F->L.nnz)               // L and L^T
                + 2 * 4 * (int64_t)F->n + 4 * ((int64_t)F->fw.levels + F->bw.levels + 2)   // level orders
                + vw * F->n + 4;                                                  // work vector, pivot word
@@ -448,7 +492,14 @@ int lcg_hip_csr_ic0_factor(lcg_hip_csr_t A, const int **rowptr, const int **col,
 int lcg_hip_ic0_solve(lcg_hip_csr_t A, int which, const double *x, double *y)
 {
     if (!A) return LCG_HIP_E_ARG;
-    return ic0_call(A, A->is_complex, which, x, y, -1);
+    return ic0_call(A, A->is_complex, false, which, x, y, -1);
+}
+
+int lcg_hip_ic0_solve_c64(lcg_hip_csr_t A, int which, const float *x, float *y)
+{
+    int rc = ensure_init(); if (rc) return rc;
+    if (!A) return LCG_HIP_E_ARG;
+    return ic0_call(A, false, true, which, reinterpret_cast<const double *>(x), reinterpret_cast<double *>(y), -1);
 }
 
 int lcg_hip_csr_ic0_schedule_for_test(lcg_hip_csr_t A, int max_merged_rows)
@@ -464,7 +515,7 @@ int lcg_hip_csr_ic0_schedule_for_test(lcg_hip_csr_t A, int max_merged_rows)
 // The callback types return void (lcg.h:37-38, clcg.h:40-41): a failure is parked in Ctx::ax_rc (driver.hpp: checked_mx).
 void lcg_hip_ic0_mx(void *instance, const double *x, double *prod_Mx, const int n_size)
 {
-    const int rc = ic0_call(static_cast<lcg_hip_csr *>(instance), false, 2, x, prod_Mx, n_size);
+    const int rc = ic0_call(static_cast<lcg_hip_csr *>(instance), false, false, 2, x, prod_Mx, n_size);
     if (rc && !ctx().ax_rc) ctx().ax_rc = rc;
 }
 
@@ -472,7 +523,16 @@ void clcg_hip_ic0_mx(void *instance, const double *x, double *prod_Mx, const int
 {
     (void)layout;       // M = L.L^T is complex-symmetric: M^T = M
     const int rc = conjugate ? arg_error("IC(0): conjugate = 1 is not offered (M^H != M)")
-                             : ic0_call(static_cast<lcg_hip_csr *>(instance), true, 2, x, prod_Mx, n_size);
+                             : ic0_call(static_cast<lcg_hip_csr *>(instance), true, false, 2, x, prod_Mx, n_size);
+    if (rc && !ctx().ax_rc) ctx().ax_rc = rc;
+}
+
+void clcg_hip_ic0_mx_c64(void *instance, const float *x, float *prod_Mx, const int n_size, int layout, int conjugate)
+{
+    (void)layout;       // M = L.L^T is complex-symmetric: M^T = M
+    const int rc = conjugate ? arg_error("IC(0): conjugate = 1 is not offered (M^H != M)")
+                             : ic0_call(static_cast<lcg_hip_csr *>(instance), false, true, 2, reinterpret_cast<const double *>(x),
+                                        reinterpret_cast<double *>(prod_Mx), n_size);
     if (rc && !ctx().ax_rc) ctx().ax_rc = rc;
 }
 

@@ -157,6 +157,8 @@ __device__ __forceinline__ double2 vadd(double2 a, double2 b) { return make_doub
 __device__ __forceinline__ double2 vsub(double2 a, double2 b) { return make_double2(a.x - b.x, a.y - b.y); }
 __device__ __forceinline__ double vadd(double a, double b) { return a + b; }
 __device__ __forceinline__ double vsub(double a, double b) { return a - b; }
+__device__ __forceinline__ float2 vadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }     // complex64 (csr_ic0.hip)
+__device__ __forceinline__ float2 vsub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
 __device__ __forceinline__ double2 vmul(double2 a, double2 b) { return make_double2(a.x * b.x, a.y * b.y); }
 __device__ __forceinline__ double vmul(double a, double b) { return a * b; }
 __device__ __forceinline__ double2 vneg(double2 a) { return make_double2(-a.x, -a.y); }
@@ -193,6 +195,7 @@ __device__ __forceinline__ double cnorm(double2 a) { return a.x * a.x + a.y * a.
 // value ops shared by the A.x kernels (csr.hip, comm.hip)
 __device__ __forceinline__ double vzero(double) { return 0.0; }
 __device__ __forceinline__ double2 vzero(double2) { return make_double2(0.0, 0.0); }
+__device__ __forceinline__ float2 vzero(float2) { return make_float2(0.0f, 0.0f); }
 __device__ __forceinline__ double mac(double a, double x, double acc) { return fma(a, x, acc); }
 __device__ __forceinline__ double2 mac(double2 a, double2 x, double2 acc) { return cfma(a, x, acc); }
 __device__ __forceinline__ double shfl_down_v(double v, int off, int w) { return __shfl_down(v, off, w); }

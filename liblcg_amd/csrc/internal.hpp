@@ -391,7 +391,8 @@ inline int refuse_c64(const lcg_hip_csr *A, const char *entry)
 {
     if (!A || !A->c64) return 0;
     ctx().err = std::string(entry) + ": the matrix holds complex64 values; this entry serves fp64 and complex128 matrices "
-                "(complex64: lcg_hip_spmv_c64, clcg_hip_csr_ax_c64, clcg_hip_jacobi_mx_c64)";
+                "(complex64: lcg_hip_spmv_c64, clcg_hip_csr_ax_c64, clcg_hip_jacobi_mx_c64, lcg_hip_csr_build_ic0_c64, "
+                "lcg_hip_ic0_solve_c64, clcg_hip_ic0_mx_c64)";
     return LCG_HIP_E_ARG;
 }
 #define TRY_C64(A, entry) do { int rc_ = ::lcgh::refuse_c64((A), (entry)); if (rc_) return rc_; } while (0)
