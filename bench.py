@@ -17,9 +17,12 @@ The K-step solve is timed `--reps` times (default 5), each bracketed by barrier 
 not depend on K guards the number: the residual a 25-iteration solve monitored must be the residual
 of its iterate (recomputed with a second A.x), and 100 iterations must come within 1e-3 of x_true.
 
-N = 1 also reports `variants`: the same CG on the three column patterns of the synthetic family
-(constant diagonals -- the headline --, row-random band, scrambled) and on a matrix that mixes two of them by rows,
-so that the headline cannot be mistaken for the whole family.
+N = 1: a plain run does what the headline needs and no more -- set-up, warm-up, the solution check, the timed solves, the
+dump, the line (with `roofline` from the events of the timed solves and the committed counter figure).  --full adds the
+rest: live traffic counters (rocprofv3 child runs), the other CG schedule, the box's copy and read rates, `variants` (the same CG
+on the three column patterns of the synthetic family -- constant diagonals, the headline; row-random band; scrambled -- on a
+matrix that mixes two of them by rows and on a 27-point stencil, so that the headline cannot be mistaken for the whole family)
+and `cpu_baseline` (the reference's CPU loop on the same matrix, its iterate compared with the GPU path's).
 N > 1: the same 10M-row system is row-partitioned over the ranks (strong scaling).  The
 north-star exchange -- RCCL all-gather of x + RCCL all-reduce of the dots -- is measured FIRST and
 always reported (`value_rccl_allgather`); cheaper exchanges are then validated against its product
@@ -205,9 +208,13 @@ def main():
     ap.add_argument("--solver", default="cg", choices=["cg", "pcg", "cgs", "bicgstab"])
     ap.add_argument("--cg-schedule", default="auto", choices=["auto", "classic", "one-reduction"],
                     help="lcg_hip_set_cg_schedule: auto = classic on one GPU, one all-reduce per iteration when sharded")
-    ap.add_argument("--no-variants", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-live-pmc", action="store_true", help="do not collect roofline.traffic with rocprofv3 child runs (N = 1); use the committed figure")
+    ap.add_argument("--full", action="store_true",
+                    help="N = 1: after the headline also measure what it does not need -- live traffic counters, the other CG schedule, the "
+                         "box's copy and read rates, the variants and the CPU baseline (each of them can still be left out below)")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: leave the variants out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-live-pmc", action="store_true",
+                    help="with --full: do not collect roofline.traffic with rocprofv3 child runs (N = 1); use the committed figure")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--budget-seconds", type=float, default=540.0,
                     help="wall-clock budget of the whole run: optional parts (exchange configurations beyond the RCCL baseline, variants, "
@@ -516,11 +523,13 @@ def main():
         kernel = lib.lcg_hip_csr_last_kernel(S.A.h).decode()
         traffic, source = pmc_traffic(args.pattern, kernel, S.nnz_local) if world == 1 and not sharded else (None, "not collected for sharded runs")
         if world == 1 and not sharded:
-            # the same counters collected NOW, on this box, by two rocprofv3 child runs of the product alone (counters cannot be read
-            # from inside this process), each held to 75 s and started only while more than half of the budget is left: the
+            # --full: the same counters collected NOW, on this box, by two rocprofv3 child runs of the product alone (counters cannot be
+            # read from inside this process), each held to 75 s and started only while more than half of the budget is left: the
             # committed figure is the fallback, and both are always in the line under fixed keys
             out["traffic_committed"] = {"traffic": traffic, "traffic_source": source}
-            if args.no_live_pmc:
+            if not args.full:
+                live, why = None, "a plain run (--full collects them)"
+            elif args.no_live_pmc:
                 live, why = None, "--no-live-pmc"
             elif time_left(args) < 0.5 * args.budget_seconds:
                 live, why = None, f"{time_left(args):.0f} s of the budget left"
@@ -549,7 +558,7 @@ def main():
     if one_gpu:
         out["rehearsal"] = (f"{world} ranks on ONE GPU, torch side on gloo, the library's collectives from tests/fake_rccl (HIP-IPC staging buffers + host "
                             "shared memory): the code path of an N-GPU run end to end -- NO number in this line is a measurement of anything")
-    if not sharded and args.solver == "cg":
+    if args.full and not sharded and args.solver == "cg":
         # the other CG schedule on one GPU too, so that a scaling ratio can be formed schedule by schedule (N > 1 reports both as well)
         by = {"classic" if not one_red else "one_reduction": round(args.steps / med, 1)}
         other = "one_reduction" if not one_red else "classic"
@@ -562,7 +571,7 @@ def main():
             api.set_cg_schedule({"auto": api.CG_AUTO, "classic": api.CG_CLASSIC, "one-reduction": api.CG_ONE_REDUCTION}[args.cg_schedule])
         out["value_by_cg_schedule"] = by
 
-    if rank == 0 and world == 1 and "roofline" in out:
+    if args.full and rank == 0 and world == 1 and "roofline" in out:
         # what THIS box's memory system sustains on a plain device copy (1 GiB read + 1 GiB written),
         # next to the nominal 8 TB/s the fractions above are quoted against
         src = torch.empty(1 << 27, dtype=torch.float64, device="cuda").normal_()
@@ -594,10 +603,10 @@ def main():
         rf["effective_over_device_copy"] = rf["achieved"] / copy_gbs
         rf["must_move_over_device_read"] = rf["must_move_GBs"] / read_gbs if rf.get("must_move_GBs") else None
 
-    if world == 1 and not sharded and not args.no_variants:
+    if args.full and world == 1 and not sharded and not args.no_variants:
         out["variants"] = variants(args, System, S, lib, api, n, spmv_bytes, iteration_bytes)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         def gpu_iterate(k):         # the iterate the GPU path holds after k iterations of the same solve (the reference's, below, beside it)
             S.solve(k); api.synchronize()
             return S.m.cpu().numpy()

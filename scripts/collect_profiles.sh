@@ -12,12 +12,12 @@ OUT=$REPO/gpurun_out/profiles_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd "$REPO"
 # 1. the bench line itself (headline + variants + cpu baseline)
-timeout -k 10 400 python3 bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 400 python3 bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 tail -c 600 "$OUT/bench.json"; echo
 cd /tmp && export TMPDIR=/tmp
 # 2. kernel trace of the same command (the variants ride in it: one stats file covers all three patterns)
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace_bench" -o prof -- \
-    python3 "$REPO/bench.py" --no-cpu-baseline --no-live-pmc > "$OUT/trace_bench.json" 2> "$OUT/trace_bench.err"
+    python3 "$REPO/bench.py" --full --no-cpu-baseline --no-live-pmc > "$OUT/trace_bench.json" 2> "$OUT/trace_bench.err"
 echo "bench kernel trace done"
 # 3. kernel traces of the other single-GPU configurations: configs[1] (Laplacian PCG), configs[4](i) (10M non-symmetric
 #    BiCGStab / CGS), configs[0] and the complex system (latency-bound)

@@ -4,7 +4,7 @@
     python scripts/make_profile_summary.py r02
 
   profiles/<tag>_bench_n1.json             the bench line of that box
-  profiles/<tag>_kernel_stats.csv          rocprofv3 --kernel-trace --stats of `bench.py --no-cpu-baseline` (headline + variants)
+  profiles/<tag>_kernel_stats.csv          rocprofv3 --kernel-trace --stats of `bench.py --full --no-cpu-baseline` (headline + variants)
   profiles/<tag>_configs_kernel_stats.csv  the same for scripts/bench_configs.py c1 c2 c5 (configs[0], [1], [4])
   profiles/<tag>_configs.jsonl             un-profiled numbers of those configurations
   profiles/<tag>_ax_variants.jsonl         A.x on each pattern with each kernel family (plain / binned / tiled / automatic)

@@ -53,7 +53,7 @@ def test_need_ranges_match_oracle_rows(port):
 
 def _run_bench(extra_env, *args):
     env = dict(os.environ, **extra_env)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-live-pmc", "--rows", "400000",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-live-pmc", "--rows", "400000",
                         "--band", "5000", "--steps", "30", "--warmup", "3", *args],
                        capture_output=True, text=True, env=env, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
@@ -163,12 +163,35 @@ def test_a_failing_product_ends_the_solve_with_its_code():
 
 
 def test_bench_collects_its_traffic_counters_live():
-    """bench.py at N = 1 collects roofline.traffic on the box it times on: two rocprofv3 --pmc child runs of the product alone.
+    """bench.py --full at N = 1 collects roofline.traffic on the box it times on: two rocprofv3 --pmc child runs of the product alone.
     The figure must sit between what the kernel must move by construction and twice that (x re-fetched per XCD, metadata)."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--no-variants", "--rows", "2000000",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--no-variants", "--rows", "2000000",
                         "--steps", "10", "--warmup", "2", "--reps", "2"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     rf = json.loads(p.stdout.strip().splitlines()[-1])["roofline"]
     assert rf["traffic_source"].startswith("live on this box"), rf["traffic_source"]
     assert rf["must_move_bytes"] <= rf["traffic"] <= 2.0 * rf["must_move_bytes"], (rf["traffic"], rf["must_move_bytes"])
     assert 0.0 < rf["frac_traffic"] < 1.0
+
+
+def test_plain_bench_run_times_the_headline_only(tmp_path):
+    """bench.py without --full: set-up, warm-up, the solution check, the timed solves, the dump and the line -- with the headline's
+    fields and the roofline of the timed solves, and none of what only --full measures (no child runs, variants, CPU baseline)."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "400000", "--band", "5000", "--steps", "30", "--warmup", "3",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    assert "error" not in out, out["error"]
+    assert out["metric"] == "cg_iterations_per_sec" and out["unit"] == "iter/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert out["steps"] == 30 and out["warmup"] == 3 and out["timed_repetitions"] == 5
+    assert out["value"] > 0 and out["ms_per_step"] == pytest.approx(1e3 / out["value"], rel=1e-9)
+    assert out["solution_check"]["rel_err_vs_x_true_after_100_iterations"] < 1e-3
+    assert out["roofline"]["launches"] > 0 and out["roofline"]["avg_launch_us"] > 0
+    assert out["traffic_live"]["traffic"] is None and "plain run" in out["traffic_live"]["traffic_source"]
+    for key in ("variants", "cpu_baseline", "value_by_cg_schedule"):
+        assert key not in out, key
+    assert "device_copy_GBs_this_box" not in out["roofline"]
+    x, rows, info = (np.load(os.path.join(tmp_path, f"{name}.npy")) for name in ("x", "x_rows", "info"))
+    assert x.shape == rows.shape == (400000,) and tuple(info[1:2]) == (30,)
