@@ -299,13 +299,12 @@ int lcg_hip_csr_set_packed(lcg_hip_csr_t A, int mode);
  * one more than the entry in the same slot of the row above (constant diagonals, stencils away from the edges).  Such a
  * block carries row 0's columns only -- 8.06 instead of 10.3 bytes of stream per entry -- and its x gathers leave together
  * with the value stream (-22 % on the headline A.x, bit-identical y).  Returns the number of run blocks of the packed copy
- * (0 before the first product built it, or when there are none); *blocks_out (may be NULL) = all blocks of 64 rows.
- * (A LAB build's LCG_HIP_PACKED_RUNS=0 stores every block with its own columns.) */
+ * (0 before the first product built it, or when there are none); *blocks_out (may be NULL) = all blocks of 64 rows. */
 int64_t lcg_hip_csr_packed_runs(lcg_hip_csr_t A, int64_t *blocks_out);
 /* Blocks of 64 rows the packed form stores as TEMPLATE blocks: every entry on one of <= 64 diagonals (the union of the rows'), rows of
  * <= 32 entries, and a 64-bit mask per row saying which diagonals the row has -- what a stencil's blocks look like where grid boundaries pass
  * through them.  Like run blocks they stream values only and are bit-identical to the plain row-block kernel.
- * (A LAB build's LCG_HIP_PACKED_TEMPLATES=0 stores such blocks with packed columns.)  No reference counterpart. */
+ * No reference counterpart. */
 int64_t lcg_hip_csr_packed_templates(lcg_hip_csr_t A);
 /* Two-pass "binned" A.x for matrices whose columns are scattered over more of x than any cache holds (the
  * arbitrary user CSR of sample8.cu:96-103 at its worst): pass 1 expands x into entry order with a 64 KB slice

@@ -1045,9 +1045,8 @@ int dist_spmv(lcg_hip_csr *A, const double *x, double *y) { return dist_spmv_imp
 
 int dist_ax_dot(lcg_hip_csr *A, const double *x, double *y, const double *u, int yy, double *part, int *slots)
 {
-    static const bool off = [] { const char *e = lab_env("LCG_HIP_AX_DOT_SHARDED"); return e && atoi(e) == 0; }();     // A/B runs (LAB build)
     bool fused = false;
-    const int rc = dist_spmv_impl(A, x, y, (yy || off) ? nullptr : u, part, slots, &fused);
+    const int rc = dist_spmv_impl(A, x, y, yy ? nullptr : u, part, slots, &fused);
     return rc ? (rc > 0 ? -rc : rc) : (fused ? 1 : 2);
 }
 

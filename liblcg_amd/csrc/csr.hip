@@ -424,7 +424,7 @@ __global__ __launch_bounds__(64) void k_pk_meta(int n, const int *rowptr, const 
     }
     int D = 0;
     bool tplb = false;
-    if (!run && runs == 1 && e > s) {       // uniform (runs == 2: run blocks only, LCG_HIP_PACKED_TEMPLATES=0)
+    if (!run && runs == 1 && e > s) {       // uniform (runs == 2: run blocks only; packed_build never asks for that)
         bool bad;
         (void)tpl_row_mask(row0, r1, rowptr, col, tpl, &dcount, &D, &bad);
         tplb = !bad;        // (uniform)
@@ -573,7 +573,6 @@ __device__ __forceinline__ void ldsp_dot_tail(const DotPlan &dp, int bid, int j0
 // six already), 1696 (20.4 KB, eight: rows of up to 26 entries).
 constexpr int PK_CH_SMALL = 2208;
 constexpr int PK_CH_7 = 1872, PK_CH_8 = 1696;
-static DotPlan ldsp_plain_plan() { DotPlan d; d.ystore = y_store_policy(); return d; }
 static int pk_window(int max_slice)
 {
     static const int env = [] { const char *e = std::getenv("LCG_HIP_PACKED_WINDOW"); return e ? atoi(e) : 0; }();     // A/B runs: least window
@@ -700,7 +699,7 @@ __global__ __launch_bounds__(VB) void k_spmv_ldsp(int n, const int *__restrict__
                 double v = sred[0][rl];
 #pragma unroll
                 for (int j = 1; j < T; j++) v += sred[j][rl];
-                store_y(y + row0 + rl, v, dp.ystore);
+                y[row0 + rl] = v;
                 vfin = v;
             }
         };
@@ -764,7 +763,7 @@ __global__ __launch_bounds__(VB) void k_spmv_ldsp(int n, const int *__restrict__
             double v = sred[0][rl];
 #pragma unroll
             for (int j = 1; j < T; j++) v += sred[j][rl];
-            store_y(y + row0 + rl, v, dp.ystore);
+            y[row0 + rl] = v;
             vfin = v;
         }
         if (DOT) ldsp_dot_tail(dp, bid, j0, vfin, uv);
@@ -865,7 +864,7 @@ __global__ __launch_bounds__(VB) void k_spmv_ldsp(int n, const int *__restrict__
         double v = sred[0][rl];
 #pragma unroll
         for (int j = 1; j < T; j++) v += sred[j][rl];
-        store_y(y + row0 + rl, v, dp.ystore);
+        y[row0 + rl] = v;
         vfin = v;
     }
     if (DOT) ldsp_dot_tail(dp, bid, j0, vfin, uv);
@@ -1157,12 +1156,10 @@ static bool packed_build(const CsrPart &P, hipStream_t s, bool runs_only, int R 
     int *ngr = nullptr, *span = nullptr;
     long total = 0;
     int hspan[4] = {0, 0, 0, 0};
-    static const int runs = [] { const char *e = lab_env("LCG_HIP_PACKED_RUNS"); return e ? atoi(e) : 1; }();    // 0: A/B runs without run blocks
     int dof = 1;
     if (R != PK_R && !runs_only) {      // long rows: do all rows consist of groups of 2 / 3 / 4 consecutive columns?
-        static const int dof_off = [] { const char *e = lab_env("LCG_HIP_PACKED_DOF"); return e && atoi(e) == 0; }();     // (A/B runs)
         int *d = nullptr, h[3] = {1, 1, 1};
-        bool okd = !dof_off && hipMalloc(&d, sizeof h) == hipSuccess && hipMemcpyAsync(d, h, sizeof h, hipMemcpyHostToDevice, s) == hipSuccess;
+        bool okd = hipMalloc(&d, sizeof h) == hipSuccess && hipMemcpyAsync(d, h, sizeof h, hipMemcpyHostToDevice, s) == hipSuccess;
         if (okd) {
             hipLaunchKernelGGL(k_pk_dof, dim3((n + VB - 1) / VB), dim3(VB), 0, s, n, P.rowptr, P.col, d);
             okd = hipMemcpyAsync(h, d, sizeof h, hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
@@ -1176,13 +1173,11 @@ static bool packed_build(const CsrPart &P, hipStream_t s, bool runs_only, int R 
               hipMemsetAsync(span, 0, 4 * sizeof(int), s) == hipSuccess;
     if (ok) {
         // (k_pk_meta: 0 no run blocks, 1 run blocks and template blocks, 2 run blocks only)
-        static const int tpls = [] { const char *e = lab_env("LCG_HIP_PACKED_TEMPLATES"); return e ? atoi(e) : 1; }();    // 0: A/B runs without template blocks
-        hipLaunchKernelGGL(k_pk_meta, dim3(nb), dim3(64), 0, s, n, P.rowptr, P.col, P.pk_base, ngr, span, (runs && R == PK_R) ? (tpls ? 1 : 2) : 0, R);
+        hipLaunchKernelGGL(k_pk_meta, dim3(nb), dim3(64), 0, s, n, P.rowptr, P.col, P.pk_base, ngr, span, R == PK_R ? 1 : 0, R);
         ok = hipMemcpyAsync(hspan, span, 4 * sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
     }
-    if (ok) ok = runs_only ? (runs && 2L * (hspan[2] + hspan[3]) >= nb) : hspan[0] < PK_SPAN;     // runs only: worth it when most blocks are runs or templates
-    static const int force_bits = [] { const char *e = lab_env("LCG_HIP_PACKED_BITS"); return e ? atoi(e) : 0; }();   // 21: A/B runs
-    const int bits = runs_only ? 0 : ((hspan[0] < (1 << 18) && force_bits != 21) ? 18 : 21);     // seven 18-bit columns per group where the blocks are narrow enough
+    if (ok) ok = runs_only ? 2L * (hspan[2] + hspan[3]) >= nb : hspan[0] < PK_SPAN;     // runs only: worth it when most blocks are runs or templates
+    const int bits = runs_only ? 0 : (hspan[0] < (1 << 18) ? 18 : 21);     // seven 18-bit columns per group where the blocks are narrow enough
     if (ok) {
         hipLaunchKernelGGL(k_pk_groups, dim3((nb + VB - 1) / VB), dim3(VB), 0, s, nb, runs_only ? 0 : (128 / bits) * dof, ngr);
         ok = device_exclusive_scan(nb, ngr, P.pk_ofs, s, &total) == 0;
@@ -1267,12 +1262,6 @@ static int lds_shape(const CsrPart &P, int variant, double mean_row, hipStream_t
     return 0;
 }
 
-static bool long_rows_packed()
-{   // LCG_HIP_PACKED_LONG=0: long rows stay with k_spmv_lds1 (A/B runs)
-    static const bool on = [] { const char *e = lab_env("LCG_HIP_PACKED_LONG"); return !e || atoi(e) != 0; }();
-    return on;
-}
-
 // What one part's A.x runs (ax_choose below): the kernel family and its template arguments
 enum class Ax { none, long_rows, ranges, binned, tiled, run1, ldsp, ldsp_long, lds1, ldsw, wave };
 enum class AxAsk { product, dot, part_dot };        // who asks: spmv_dispatch, csr_ax_dot, csr_part_ax_dot
@@ -1322,10 +1311,6 @@ static void ldsp_launch(const AxChoice &c, const CsrPart &P, const double *x, do
     else pick<6, 9>(c.ns, go);
 }
 
-// (A/B runs) LCG_HIP_RUN1=0: no k_spmv_run1 / run1d; LCG_HIP_AX_DOT_PACKED=0: k_spmv_ldsp keeps the dot as a pass of its own
-static bool run1_off() { static const bool off = [] { const char *e = lab_env("LCG_HIP_RUN1"); return e && atoi(e) == 0; }(); return off; }
-static bool ax_dot_packed_off() { static const bool off = [] { const char *e = lab_env("LCG_HIP_AX_DOT_PACKED"); return e && atoi(e) == 0; }(); return off; }
-
 // The kernel a part's A.x takes: DESIGN 3.6's rules in order, the first that holds decides.  `push`: a shard's pushing blocks ride
 // in front.  The dot askers then map the choice to the dot forms they take (csr_ax_dot, part_dot_launch); anything else: no dot.
 // The plans below are built by the first call that consults them and are fixed from then on, so each is consulted under the same
@@ -1335,7 +1320,7 @@ static bool ax_dot_packed_off() { static const bool off = [] { const char *e = l
 //  - a part's dot consults neither lr_mode nor ranges, nor tries run1 or the long-row packed form; with pushing blocks neither it
 //    nor the product consults binned: tiled is tried directly.  The single-GPU dot does not consult lr_mode.
 //  - the dot askers leave at > 160 entries per row or misaligned arrays before binned, and where a slice exceeds the window
-//    before packed_build.  LCG_HIP_AX_DOT_PACKED=0 stops a part's dot before packed_ready, the single-GPU dot after it.
+//    before packed_build.
 //  - plain k_spmv_run1 takes rows of up to 30 entries, its dot form run1d up to 15 (csr_ax_dot).
 //  - plain k_spmv_lds1 takes a smaller window only if real, not accumulating, one-window and >= 2^22 entries; lds1d never.
 //  - long-row packed blocks, windowed, wave, binned, ranges and complex matrices never carry the dot.
@@ -1364,13 +1349,13 @@ static int ax_choose(const CsrPart &P, int variant, double mean_row, bool push, 
     c.family = c.onewin ? Ax::lds1 : Ax::ldsw;
     c.win = LdsCfg<V>::CH;
     if constexpr (sizeof(V) == 8 && !ACC) {
-        if (dot && (!c.onewin || (ask == AxAsk::part_dot && ax_dot_packed_off()))) return 0;
+        if (dot && !c.onewin) return 0;
         // short rows whose blocks of 64 are mostly runs: one wavefront per block, no staging (k_spmv_run1)
         // (its wavefront-private LDS is dynamic: 4 wavefronts x 64 rows x LP doubles must stay within the 64 KB a launch
         //  may ask for without further ado -- rows of up to 30 entries)
-        if (whole && !run1_off() && variant == -1 && (R == 256 || R == 128) && packed_build(P, s, true) && P.pk_maxrow <= 30) { c.family = Ax::run1; return 0; }
+        if (whole && variant == -1 && (R == 256 || R == 128) && packed_build(P, s, true) && P.pk_maxrow <= 30) { c.family = Ax::run1; return 0; }
         if ((R == PK_R && c.onewin && packed_ready(P, s)) ||
-            (whole && (R == 32 || R == 16) && c.onewin && long_rows_packed() && packed_ready(P, s, R))) {     // (long rows: ldsp_ns)
+            (whole && (R == 32 || R == 16) && c.onewin && packed_ready(P, s, R))) {     // (long rows: ldsp_ns)
             c.family = R == PK_R ? Ax::ldsp : Ax::ldsp_long; c.ns = ldsp_ns(P, R); c.bits = P.pk_bits;
             c.win = pk_window(P.max_slice);                 // the smallest LDS window every block fits: more workgroups per CU
             return 0;
@@ -1442,13 +1427,13 @@ static int spmv_dispatch(const CsrPart &P, int variant, double mean_row, const V
             return 0;
         }
         case Ax::ldsp:
-            ldsp_launch<PUSH, false>(c, P, xd, yd, s, done, pp, ldsp_plain_plan());
+            ldsp_launch<PUSH, false>(c, P, xd, yd, s, done, pp, DotPlan());
             HIPCHK(hipGetLastError());
             P.last_kernel = ldsp_name(P, false);
             return 0;
         case Ax::ldsp_long:
             if constexpr (!PUSH) {
-                DotPlan dp = ldsp_plain_plan(); dp.dof = P.pk_dof;
+                DotPlan dp; dp.dof = P.pk_dof;
                 (c.R == 32 ? ldsp_launch<false, false, 32> : ldsp_launch<false, false, 16>)(c, P, xd, yd, s, done, PushPlan(), dp);
                 HIPCHK(hipGetLastError());
                 P.last_kernel = P.pk_dof > 1 ? (P.pk_bits == 18 ? "k_spmv_ldsp (LDS-staged, long rows: one 18-bit packed column per group of consecutive columns)"
@@ -1534,8 +1519,6 @@ static int part_dot_launch(const CsrPart &P, const AxChoice &c, const double *x,
     int nsum = 0;
     if (c.family == Ax::tiled) {
         // the tiled product: one sum per chunk of 1024 rows (per consumer wavefront), folded like the packed kernel's per-block sums
-        static const bool tl_off = [] { const char *e = lab_env("LCG_HIP_AX_DOT_TILED"); return e && atoi(e) == 0; }();
-        if (tl_off || !tiled_dot_ok(P)) return 0;
         nsum = tiled_chunks(P);
         if (nsum <= 0 || !ensure_dot_part(P, nsum)) return 0;
         DotPlan dp; dp.u = u; dp.part = P.dot_part; dp.yy = yy; dp.stride = nsum;
@@ -1546,9 +1529,7 @@ static int part_dot_launch(const CsrPart &P, const AxChoice &c, const double *x,
     } else if (c.family == Ax::ldsp) {
         nsum = (P.n_rows + PK_R - 1) / PK_R;
         if (!ensure_dot_part(P, nsum)) return 0;
-        DotPlan dp; dp.u = u; dp.part = P.dot_part; dp.yy = yy; dp.stride = nsum; dp.ystore = y_store_policy();
-        {   static const bool ux_off = [] { const char *e = lab_env("LCG_HIP_DOT_UX"); return e && atoi(e) == 0; }();      // (A/B runs)
-            dp.ux = (u == x && !ux_off) ? 1 : 0; }
+        DotPlan dp; dp.u = u; dp.part = P.dot_part; dp.yy = yy; dp.stride = nsum; dp.ux = u == x ? 1 : 0;
         if (pp) ldsp_launch<true, true>(c, P, x, y, s, done, *pp, dp);
         else ldsp_launch<false, true>(c, P, x, y, s, done, PushPlan(), dp);
         HIPCHK(hipGetLastError());
@@ -1585,8 +1566,8 @@ int csr_ax_dot(lcg_hip_csr *A, const double *x, double *y, const double *u, int 
     AxChoice c;
     { int rc = ax_choose<double, false>(P, A->variant, A->mean_row, false, AxAsk::dot, s, c); if (rc) return rc; }
     switch (c.family) {
-    case Ax::tiled: return part_dot_launch(P, c, x, y, u, yy, part, slots, s, done, nullptr, nullptr);
-    case Ax::ldsp: return ax_dot_packed_off() ? 0 : part_dot_launch(P, c, x, y, u, yy, part, slots, s, done, nullptr, nullptr);
+    case Ax::tiled:
+    case Ax::ldsp: return part_dot_launch(P, c, x, y, u, yy, part, slots, s, done, nullptr, nullptr);
     case Ax::run1: {
         // short-row stencils (k_spmv_run1d): eight wavefronts, one partial per workgroup of 512 rows (8 x 64 x LP doubles of
         // dynamic LDS: rows of up to 15 entries; longer ones take k_spmv_lds1d below)
@@ -1611,8 +1592,8 @@ int csr_ax_dot(lcg_hip_csr *A, const double *x, double *y, const double *u, int 
     // Where it pays (measured, scripts/ax_dot_lab.py + scripts/ab_small.py): systems whose iteration is a chain of kernel
     // latencies -- the product grows by ~0.6 us, a ~3 us pass and its launch go.  At 1M rows (3907 row blocks) the product grew by
     // 3.2 us and every block of the consuming pass re-added 3907 partials: 39.2 vs 38.5 us per PCG iteration, so from
-    // LCG_HIP_AX_DOT_MAXBLK (default 2048) row blocks on the separate pass stays.
-    static const int maxblk = [] { const char *e = lab_env("LCG_HIP_AX_DOT_MAXBLK"); const int v = e ? atoi(e) : 2048; return v < 1 ? 1 : (v > AXP_CAP ? AXP_CAP : v); }();
+    // 2048 row blocks on the separate pass stays.
+    constexpr int maxblk = 2048;
     const int nblk = (n + c.R - 1) / c.R;
     if (nblk > maxblk) return 0;
     DotPlan dp; dp.u = u; dp.part = part; dp.yy = yy;

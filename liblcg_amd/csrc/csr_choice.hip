@@ -22,16 +22,12 @@ __global__ __launch_bounds__(64) void k_span_sum(int n, const int *__restrict__ 
     if (threadIdx.x == 0 && e > s) atomicAdd(sum, (unsigned long long)(hi - lo));
 }
 
-static double span_threshold()
-{   // LCG_HIP_BINNED_SPAN: mean block span (columns) from which the automatic choice takes the binned product
-    static const double v = [] { const char *e = lab_env("LCG_HIP_BINNED_SPAN"); return e ? atof(e) : (double)(1 << 20); }();
-    return v;
-}
+constexpr double BINNED_SPAN = 1 << 20;         // mean block span (columns) from which the automatic choice takes the binned product
 
 static bool diag_like_measured(const CsrPart &P, hipStream_t s);     // (below)
 static bool line_ratio_measured(const CsrPart &P, hipStream_t s);
-constexpr double TILED_OVER_BINNED = 1.35;      // in units of span_threshold(): up to this mean block span a band is the tiled product's
-static double line_ratio_threshold();
+constexpr double TILED_OVER_BINNED = 1.35;      // in units of BINNED_SPAN: up to this mean block span a band is the tiled product's
+constexpr double LINE_RATIO = 0.5;              // least share of gathers that have a line of their own for the tiled / binned products to be considered
 
 // true when P's products go through the binned format (plan built here on first use)
 // P.mean_span (measured once): false when the measurement failed
@@ -67,7 +63,7 @@ bool binned_chosen(const CsrPart &P, hipStream_t s)
         if (!mean_span_measured(P, s)) { P.bn_state = -1; return false; }
         // (columns anywhere in a matrix of 1M columns span less than the threshold and are scattered all the same: 243 us binned, 347 tiled,
         //  372 packed at 1M rows)
-        if (P.mean_span < span_threshold() && P.mean_span < 0.75 * (double)P.n_cols) {
+        if (P.mean_span < BINNED_SPAN && P.mean_span < 0.75 * (double)P.n_cols) {
             P.bn_state = -1; P.bn_why = "automatic mode: the row blocks' mean column span is below the threshold"; return false;
         }
         // between one and two million columns of span the tiled product is still the faster one where its plan accepts the matrix
@@ -77,7 +73,7 @@ bool binned_chosen(const CsrPart &P, hipStream_t s)
         //  binned product's: 226 against 328 us at 1M rows)
         // (round 5: the tiled product's time grows with the span -- 1030 us at a span of 0.79M columns, 1790 at 1.57M, N = 1e7 -- and meets the
         //  binned product's 1640-1700 at about 1.4M: the upper end of this clause went from 2 thresholds to 1.35)
-        if (P.mean_span < TILED_OVER_BINNED * span_threshold() && 4.0 * P.mean_span <= (double)P.n_cols && tiled_chosen(P, s)) {
+        if (P.mean_span < TILED_OVER_BINNED * BINNED_SPAN && 4.0 * P.mean_span <= (double)P.n_cols && tiled_chosen(P, s)) {
             P.bn_state = -1; P.bn_why = "automatic mode: the tiled product takes it (mean column span below 1.35 thresholds)"; return false;
         }
         // wide, but along diagonals (a stencil on a grid with a million points per plane): every diagonal is a contiguous stream of
@@ -85,7 +81,7 @@ bool binned_chosen(const CsrPart &P, hipStream_t s)
         if (diag_like_measured(P, s) && P.diag_like > 0.5) {
             P.bn_state = -1; P.bn_why = "automatic mode: the columns run along diagonals (the row-block kernels gather contiguously)"; return false;
         }
-        if (line_ratio_measured(P, s) && P.line_ratio < line_ratio_threshold()) {
+        if (line_ratio_measured(P, s) && P.line_ratio < LINE_RATIO) {
             P.bn_state = -1; P.bn_why = "automatic mode: neighbouring rows share their cache lines of x (block-structured)"; return false;
         }
     }
@@ -171,27 +167,15 @@ static bool line_ratio_measured(const CsrPart &P, hipStream_t s)
     P.line_ratio = h[1] > 0.0 ? h[0] / h[1] : 0.0;
     return true;
 }
-static double line_ratio_threshold()
-{   // LCG_HIP_LINE_RATIO: least share of gathers that have a line of their own for the tiled / binned products to be considered
-    static const double v = [] { const char *e = lab_env("LCG_HIP_LINE_RATIO"); return e ? atof(e) : 0.5; }();
-    return v;
-}
+// LINE_RATIO for the tiled product alone.  Measured at N = 1e7, 33 per row, columns drawn per row inside a band (round 3, one box):
+// line ratio 0.063 / 0.125 / 0.244 / 0.434 (band 2048 / 4096 / 8192 / 16384): tiled 917 / 886 / 689 / 604 us, packed row blocks
+// 728 / 808 / 900 / 1062 us; block-structured stencils sit below 0.05
+constexpr double LINE_RATIO_TILED = 0.18;
 
-static double tiled_line_ratio_threshold()
-{   // the same for the tiled product alone.  Measured at N = 1e7, 33 per row, columns drawn per row inside a band (round 3, one box):
-    // line ratio 0.063 / 0.125 / 0.244 / 0.434 (band 2048 / 4096 / 8192 / 16384): tiled 917 / 886 / 689 / 604 us, packed row blocks
-    // 728 / 808 / 900 / 1062 us; block-structured stencils sit below 0.05
-    static const double v = [] { const char *e = lab_env("LCG_HIP_LINE_RATIO_TILED"); return e ? atof(e) : 0.18; }();
-    return v;
-}
-
-static double tiled_fill_threshold()
-{   // least mean number of entries per (workgroup of 8192 rows, tile of 2048 columns) pair.  Round 3's kernel needed 700; the rewritten one
-    // (k_tile_spmv2) beats the binned product down to ~350 (W = 786432 at N = 1e7: 352 per pair, 1019 against 1669 us) and loses from
-    // ~260 (W = 1048576: 1768 against 1683)
-    static const double fill = [] { const char *e = lab_env("LCG_HIP_TILED_FILL"); return e ? atof(e) : 300.0; }();
-    return fill;
-}
+// least mean number of entries per (workgroup of 8192 rows, tile of 2048 columns) pair.  Round 3's kernel needed 700; the rewritten one
+// (k_tile_spmv2) beats the binned product down to ~350 (W = 786432 at N = 1e7: 352 per pair, 1019 against 1669 us) and loses from
+// ~260 (W = 1048576: 1768 against 1683)
+constexpr double TILED_FILL = 300.0;
 
 bool tiled_chosen(const CsrPart &P, hipStream_t s)
 {
@@ -211,7 +195,7 @@ bool tiled_chosen(const CsrPart &P, hipStream_t s)
         //  size -- band of 8192 columns, line ratio 0.24: 144 us at 1M rows against 120 packed, but 150 against 198 at 2M and 278 against 377
         //  at 4M (profiles/r05_choice_regret.txt; round 4 had drawn this line at 4M rows: 33 % and 38 % lost there).  The band of 16384,
         //  0.43, is the tiled product's from 1M rows on: 116 against 140.)
-        const double lr_least = P.n_rows < 3 * (1 << 19) ? std::max(0.3, tiled_line_ratio_threshold()) : tiled_line_ratio_threshold();
+        const double lr_least = P.n_rows < 3 * (1 << 19) ? std::max(0.3, LINE_RATIO_TILED) : LINE_RATIO_TILED;
         if (lr && P.line_ratio < lr_least) {
             P.tl_state = -1; P.tl_why = "automatic mode: neighbouring rows share their cache lines of x (block-structured: the row-block kernels fetch few lines per entry)";
             return false;
@@ -228,7 +212,7 @@ bool tiled_chosen(const CsrPart &P, hipStream_t s)
             P.tl_state = -1; P.tl_why = "automatic mode: the band is as wide as the matrix and x is small (the row-block kernels gather from the caches)";
             return false;
         }
-        min_fill = tiled_fill_threshold();
+        min_fill = TILED_FILL;
     }
     const int rc = tiled_ready(P, s, min_fill);
     if (rc <= 0) { P.tl_state = -1; return false; }
@@ -327,9 +311,9 @@ bool ranges_chosen(const CsrPart &P, hipStream_t s)
         if (ent <= 0.0 || blocks <= 0.0) return -1;
         if (only_long || dl / ent > 0.5) return 0;
         const double span = span_sum / blocks;
-        if (span >= TILED_OVER_BINNED * span_threshold()) return 2;
+        if (span >= TILED_OVER_BINNED * BINNED_SPAN) return 2;
         const double fill = 128.0 * (ent / blocks) / ((span + 8192.0) / 2048.0);
-        return fill < tiled_fill_threshold() && span >= (double)(1 << 19) ? 2 : 1;
+        return fill < TILED_FILL && span >= (double)(1 << 19) ? 2 : 1;
     };
     // class 3: a 64-row block that holds a row of more than LR_LONG entries (a dense row of an "arrow" matrix: constraints, mean values).
     // One such row makes its block's slice larger than any LDS window, the whole part falls to the window-by-window kernel and ONE

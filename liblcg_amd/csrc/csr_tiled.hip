@@ -4,7 +4,7 @@
 // On such a matrix the row-block kernels of csr.hip find x in the L2 -- and still crawl: every 8-byte gather moves a
 // 128-byte line from L2 to the CU (the 10M-row row-random band, W = 131072: 42 GB through the L2 for 4 GB of matrix,
 // 1.39 ms = 0.37 of the HBM peak; non-temporal or L1-bypassing gathers change nothing).  The two-pass binned product
-// (csr_binned.hip) would stream 28.5 B per entry.  Here x is staged the way the matrix is: a workgroup owns NW x 1024
+// (csr_binned.hip) would stream 28.5 B per entry.  Here x is staged the way the matrix is: a workgroup owns TL_NW x 1024
 // rows (their sums in LDS, one wavefront per 1024 rows as in k_bin_reduce) and walks the column tiles (2048 columns)
 // its rows touch; per tile a slice of x goes into LDS and every wavefront streams its rows' entries of that tile,
 // gathering x from LDS at word granularity and adding into its row sums with ds_add_f64.  The L2 sees whole lines
@@ -13,7 +13,7 @@
 // Round 3 (k_tile_spmv2).  The round-2 kernel copied each tile through registers between two barriers and requested a
 // tile's entries behind the previous tile's adds: 62 % of its wave cycles were parked at s_waitcnt / s_barrier
 // (profiles/r03_tiled_sq.csv), 860 us on the 10M-row row-random band.  Now
-//   * a workgroup is NW consumer wavefronts + ONE loader wavefront.  The loader copies tile j + 1 into the other half
+//   * a workgroup is TL_NW consumer wavefronts + ONE loader wavefront.  The loader copies tile j + 1 into the other half
 //     of a double buffer by LDS-DMA (global_load_lds: no registers, and -- being a wavefront of its own -- no entry in
 //     the consumers' in-order vmcnt queue) while the consumers work on tile j: one workgroup barrier per tile;
 //   * a consumer never drains its loads: its stream is ONE contiguous piece of memory across all tiles, walked in steps
@@ -42,7 +42,14 @@ namespace lcgh {
 
 
 typedef unsigned long long u64t;
-constexpr int TL_MAXNW = 8;         // most consumer wavefronts (chunks) per workgroup
+// Consumer wavefronts (chunks) per workgroup: 2 x 16 KB of x + 64 KB of sums, one workgroup of nine wavefronts per CU (four -- two
+// workgroups of five per CU, twice the tile copies -- took 841 against 756 us on the 10M-row row-random band)
+constexpr int TL_NW = 8;
+// Steps a consumer has in flight (its ring of register sets).  Measured on the 10M-row row-random band, same box: depth 2 / 3 / 4 / 6 / 8
+// = 690 / 649 / 657 / 682 / 699 us (eight consumers keep 8 x D x 2 KB in flight through a 32 KB L1: deeper rings evict their own
+// lines).  The stream is read with non-temporal loads: 670 -> 598 us at depth 3 (it no longer pushes the tiles of x out of the L2 --
+// the kernel then reads at the rate of a pure sum over 4 GiB on the same box, 6.0 TB/s).
+constexpr int TL_DEPTH = 3;
 constexpr int TL_RW = 1024;         // rows per wavefront (8 KB of sums in LDS): 10 bits
 constexpr int TL_TCL2 = 11;         // columns per tile: 2048 (16 KB of x per buffer half): 11 bits
 constexpr int TL_TC = 1 << TL_TCL2;
@@ -56,14 +63,13 @@ typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void glb_void_t;
 
 struct TiledPlan {
-    int nw = 8;                     // consumer wavefronts (chunks) per workgroup
     int n_rows = 0, nwg = 0;
     long n_cols = 0, entries = 0, steps = 0, pairs = 0;
     u64t *stream = nullptr;         // [steps + TL_SLACK][TL_BLK]
     int *ntile = nullptr, *sofs = nullptr;      // per workgroup: tiles it has entries in, offset of its lists
     int *tl = nullptr;              // [sofs[g] + j]: the j-th of those tiles
-    int *gstart = nullptr;          // [(sofs[g] + j) * nw + w]: first entry of group (wavefront w, j-th tile), relative to the chunk's bin; item ntile[g] = the bins' lengths
-    int *bstep = nullptr;           // [nw * nwg + 1] first step of each chunk's bin
+    int *gstart = nullptr;          // [(sofs[g] + j) * TL_NW + w]: first entry of group (wavefront w, j-th tile), relative to the chunk's bin; item ntile[g] = the bins' lengths
+    int *bstep = nullptr;           // [TL_NW * nwg + 1] first step of each chunk's bin
     size_t bytes = 0;
 };
 
@@ -79,14 +85,14 @@ __device__ __forceinline__ void lds_barrier()
 // neighbours (devcommon.hpp: push_block) while the rest multiply -- as in the row-block kernels of csr.hip.
 // DOT: every consumer also leaves its 1024 rows' share of y.u (and y.y) in dp.part[chunk] (dp.part[dp.stride + chunk]) -- the dot the
 // Krylov loops take right after the product (csr.hip: csr_part_ax_dot folds the per-chunk sums).
-template <int NW, int D, bool PUSH = false, bool NT = false, bool DOT = false>
-__global__ __launch_bounds__((NW + 1) * 64) void k_tile_spmv2(int n, int nwg, const int *__restrict__ ntile, const int *__restrict__ sofs,
-                                                              const int *__restrict__ tl, const int *__restrict__ gstart,
-                                                              const int *__restrict__ bstep, const u64t *__restrict__ stream,
-                                                              const double *__restrict__ x, long n_cols, double *__restrict__ y,
-                                                              const int *done, PushPlan pp, DotPlan dp = DotPlan())
+template <bool PUSH, bool DOT>
+__global__ __launch_bounds__((TL_NW + 1) * 64) void k_tile_spmv2(int n, int nwg, const int *__restrict__ ntile, const int *__restrict__ sofs,
+                                                                 const int *__restrict__ tl, const int *__restrict__ gstart,
+                                                                 const int *__restrict__ bstep, const u64t *__restrict__ stream,
+                                                                 const double *__restrict__ x, long n_cols, double *__restrict__ y,
+                                                                 const int *done, PushPlan pp, DotPlan dp)
 {
-    constexpr int TC = TL_TC;
+    constexpr int TC = TL_TC, NW = TL_NW, D = TL_DEPTH;
     if (PUSH && (int)blockIdx.x < pp.nblocks) { push_block(pp, blockIdx.x); return; }
     if (PUSH && pp.nrecv > 0 && (int)blockIdx.x >= (int)gridDim.x - pp.nrecv) { recv_block(pp, (int)blockIdx.x - ((int)gridDim.x - pp.nrecv)); return; }
     const int bid = PUSH ? blockIdx.x - pp.nblocks : blockIdx.x;
@@ -151,7 +157,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void k_tile_spmv2(int n, int nwg, co
 #define TL_LOAD(i, ss)                                                      \
     do {    /* two 16-byte loads per lane: (plane 0, plane 1) and (plane 2, packed pairs) */ \
         const v2u64_t *pb = reinterpret_cast<const v2u64_t *>(sb + (long)(ss) * TL_BLK);      \
-        const v2u64_t q01 = NT ? __builtin_nontemporal_load(pb) : pb[0], q2i = NT ? __builtin_nontemporal_load(pb + 64) : pb[64]; \
+        const v2u64_t q01 = __builtin_nontemporal_load(pb), q2i = __builtin_nontemporal_load(pb + 64); \
         v0[i] = __longlong_as_double((long long)q01.x);                     \
         v1[i] = __longlong_as_double((long long)q01.y);                     \
         v2[i] = __longlong_as_double((long long)q2i.x);                     \
@@ -218,7 +224,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void k_tile_spmv2(int n, int nwg, co
 }
 
 // ---------------------------------------------------------------------------------------------- building the plan
-// per workgroup (NW x 1024 rows): smallest and largest tile its entries touch
+// per workgroup (TL_NW x 1024 rows): smallest and largest tile its entries touch
 __global__ __launch_bounds__(256) void k_tl_span(int n, int rows_per_wg, long n_cols, const int *__restrict__ rowptr, const int *__restrict__ col,
                                                  int *tmin, int *nspan, int *flags)
 {
@@ -251,19 +257,19 @@ __global__ void k_tl_plus1(int n, const int *in, int *out) { const int i = block
 // (tl[], and cmap[] for k_tl_place); per wavefront the counts are scanned over those tiles into group starts.  gstart carries
 // ntile + 1 items per workgroup (the last one = the bins' lengths); the lists sit at the offsets the SPANS were scanned to
 // (an upper bound).  nstep[chunk] = the bin's length in steps.
-__global__ __launch_bounds__(64 * TL_MAXNW) void k_tl_count(int n, int TL_NW, const int *__restrict__ rowptr, const int *__restrict__ col,
-                                                           const int *__restrict__ tmin, const int *__restrict__ nspan,
-                                                           const int *__restrict__ sofs, int *ntile, int *tl, int *cmap, int *gstart, int *nstep,
-                                                           unsigned long long *pairs)
+__global__ __launch_bounds__(64 * TL_NW) void k_tl_count(int n, int nw, const int *__restrict__ rowptr, const int *__restrict__ col,
+                                                        const int *__restrict__ tmin, const int *__restrict__ nspan,
+                                                        const int *__restrict__ sofs, int *ntile, int *tl, int *cmap, int *gstart, int *nstep,
+                                                        unsigned long long *pairs)
 {
     extern __shared__ int hist[];       // [nw][ns] + cm[ns]
     __shared__ int nused_s;
     const int g = blockIdx.x, tid = threadIdx.x, w = tid >> 6, l = tid & 63;
     const int t0 = tmin[g], ns = nspan[g];
-    int *cm = hist + TL_NW * ns;
-    for (int i = tid; i < TL_NW * ns; i += 64 * TL_NW) hist[i] = 0;
+    int *cm = hist + nw * ns;
+    for (int i = tid; i < nw * ns; i += 64 * nw) hist[i] = 0;
     __syncthreads();
-    const long r0 = (long)(g * TL_NW + w) * TL_RW;
+    const long r0 = (long)(g * nw + w) * TL_RW;
     const int ra = (int)min((long)n, r0), rb = (int)min((long)n, r0 + TL_RW);
     const int k0 = rowptr[ra], k1 = rowptr[rb];
     for (int k = k0 + l; k < k1; k += 64) atomicAdd(&hist[w * ns + (col[k] >> TL_TCL2) - t0], 1);
@@ -275,7 +281,7 @@ __global__ __launch_bounds__(64 * TL_MAXNW) void k_tl_count(int n, int TL_NW, co
         for (int b = 0; b < ns; b += 64) {
             const int lt = b + l;
             int h = 0;
-            if (lt < ns) for (int q = 0; q < TL_NW; q++) h += hist[q * ns + lt];
+            if (lt < ns) for (int q = 0; q < nw; q++) h += hist[q * ns + lt];
             const unsigned long long m = __ballot(h > 0);
             const int j = base + __popcll(m & below);
             if (lt < ns) { cm[lt] = h > 0 ? j : -1; cmap[so + lt] = h > 0 ? j : -1; if (h > 0) tl[so + j] = t0 + lt; }
@@ -286,30 +292,30 @@ __global__ __launch_bounds__(64 * TL_MAXNW) void k_tl_count(int n, int TL_NW, co
     __syncthreads();
     const int nu = nused_s;
     // each wavefront scans its own row of the histogram (serial over chunks of 64 tiles)
-    int *out = gstart + (long)so * TL_NW;
+    int *out = gstart + (long)so * nw;
     int run = 0;
     for (int b = 0; b < ns; b += 64) {
         const int lt = b + l;
         const int c = lt < ns ? hist[w * ns + lt] : 0;
         int inc = c;
         for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(inc, off, 64); if (l >= off) inc += v; }
-        if (lt < ns && cm[lt] >= 0) out[cm[lt] * TL_NW + w] = run + inc - c;
+        if (lt < ns && cm[lt] >= 0) out[cm[lt] * nw + w] = run + inc - c;
         run += __shfl(inc, 63, 64);
     }
-    if (l == 0) { out[nu * TL_NW + w] = run; nstep[g * TL_NW + w] = (run + TL_STEP - 1) / TL_STEP; }
+    if (l == 0) { out[nu * nw + w] = run; nstep[g * nw + w] = (run + TL_STEP - 1) / TL_STEP; }
 }
 
 // one wavefront per chunk walks its entries in CSR order, 64 at a time; rank inside the group = entries of that tile
 // placed so far + lower lanes of the batch with the same tile (one ballot per distinct tile of the batch): no atomics, no sort.
 // (The three packed pairs of a word come from different lanes, or different batches: they are OR-ed into the zeroed stream.)
-__global__ __launch_bounds__(64) void k_tl_place(int n, int TL_NW, const int *__restrict__ rowptr, const int *__restrict__ col,
+__global__ __launch_bounds__(64) void k_tl_place(int n, int nw, const int *__restrict__ rowptr, const int *__restrict__ col,
                                                  const double *__restrict__ val, const int *__restrict__ tmin,
                                                  const int *__restrict__ nspan, const int *__restrict__ sofs, const int *__restrict__ cmap,
                                                  const int *__restrict__ gstart, const int *__restrict__ bstep, u64t *stream)
 {
     extern __shared__ int cur[];        // [ns]
     const int chunk = blockIdx.x, l = threadIdx.x;
-    const int g = chunk / TL_NW, w = chunk % TL_NW;
+    const int g = chunk / nw, w = chunk % nw;
     const int t0 = tmin[g], ns = nspan[g];
     for (int t = l; t < ns; t += 64) cur[t] = 0;
     const long r0l = (long)chunk * TL_RW;
@@ -317,7 +323,7 @@ __global__ __launch_bounds__(64) void k_tl_place(int n, int TL_NW, const int *__
     if (r0 >= r1) return;
     const int k0 = rowptr[r0], k1 = rowptr[r1];
     const int so = sofs[g];
-    const int *gs = gstart + (long)so * TL_NW;
+    const int *gs = gstart + (long)so * nw;
     u64t *sb = stream + (long)bstep[chunk] * TL_BLK;
     const unsigned long long below = l == 0 ? 0ull : (~0ull >> (64 - l));
     for (int kb = k0; kb < k1; kb += 64) {
@@ -339,7 +345,7 @@ __global__ __launch_bounds__(64) void k_tl_place(int n, int TL_NW, const int *__
         if (active) {
             int lo = r0, hi = r1 - 1;
             while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (rowptr[mid] <= k) lo = mid; else hi = mid - 1; }
-            const int p = gs[cmap[so + t] * TL_NW + w] + rank;          // position in the bin
+            const int p = gs[cmap[so + t] * nw + w] + rank;          // position in the bin
             const int st = p / TL_STEP, r = p - st * TL_STEP, ln = r / 3, pl = r - 3 * ln;
             u64t *blk = sb + (long)st * TL_BLK;
             // a step's block: words [2 l + k] = plane k < 2 of lane l, [128 + 2 l] = plane 2, [128 + 2 l + 1] = the packed pairs
@@ -364,14 +370,6 @@ void tiled_free(CsrPart &P)
     P.tl_plan = nullptr; P.tl_state = 0;
 }
 
-// Consumer wavefronts per workgroup.  LCG_HIP_TILED_NW (A/B runs): 8 (default: 2 x 16 KB of x + 64 KB of sums, one workgroup of
-// nine wavefronts per CU) or 4 (two workgroups of five per CU, twice the tile copies: 841 vs 756 us on the 10M-row row-random band).
-static int tiled_nw()
-{
-    static const int v = [] { const char *e = lab_env("LCG_HIP_TILED_NW"); return e && atoi(e) == 4 ? 4 : 8; }();
-    return v;
-}
-
 // min_fill: least mean number of entries per (workgroup, tile) pair for the plan to be worth building (0 = build anyway)
 static int plan_build(const CsrPart &P, hipStream_t s, double min_fill, TiledPlan **out, const char **why)
 {
@@ -380,11 +378,10 @@ static int plan_build(const CsrPart &P, hipStream_t s, double min_fill, TiledPla
     const long n_cols = P.n_cols;
     *why = "empty matrix or unknown column count";
     if (n <= 0 || n_cols <= 0 || P.nnz <= 0) return 0;
-    const int TL_NW = tiled_nw();
     const int nwg = (n + TL_RW * TL_NW - 1) / (TL_RW * TL_NW);
-    const int maxspan = 65536 / 4 / (TL_NW + 1) - 8;        // builder histogram [nw + 1][span] within the default dynamic LDS
+    const int maxspan = 65536 / 4 / (TL_NW + 1) - 8;        // builder histogram [TL_NW + 1][span] within the default dynamic LDS
     TiledPlan *T = new TiledPlan();
-    T->n_rows = n; T->nwg = nwg; T->n_cols = n_cols; T->nw = TL_NW;
+    T->n_rows = n; T->nwg = nwg; T->n_cols = n_cols;
     int *flags = nullptr, *nstep = nullptr, *tmin = nullptr, *nspan = nullptr, *span1 = nullptr, *cmap = nullptr;
     unsigned long long *pairs = nullptr;
     auto cleanup = [&](int rc) {
@@ -465,20 +462,11 @@ int tiled_ready(const CsrPart &P, hipStream_t s, double min_fill)
     return 1;
 }
 
-// dot != nullptr: the product leaves per-chunk sums of y.u (y.y) in dot->part (chunks: tiled_chunks); only the default shape carries
-// them (eight consumers, ring of three, non-temporal stream) -- tiled_dot_ok says so beforehand
+// dot != nullptr: the product leaves per-chunk sums of y.u (y.y) in dot->part (chunks: tiled_chunks; 0 without a plan)
 int tiled_chunks(const CsrPart &P)
 {
     const TiledPlan *T = static_cast<const TiledPlan *>(P.tl_plan);
-    return T ? T->nwg * T->nw : 0;
-}
-static int tiled_depth() { static const int v = [] { const char *e = lab_env("LCG_HIP_TILED_DEPTH"); return e ? atoi(e) : 3; }(); return v; }
-static int tiled_nt() { static const int v = [] { const char *e = lab_env("LCG_HIP_TILED_NT"); return e ? atoi(e) : 1; }(); return v; }
-bool tiled_dot_ok(const CsrPart &P)
-{
-    const TiledPlan *T = static_cast<const TiledPlan *>(P.tl_plan);
-    const int d = tiled_depth();
-    return T && T->nw == 8 && tiled_nt() && d != 2 && d != 4 && d != 6;
+    return T ? T->nwg * TL_NW : 0;
 }
 
 int tiled_launch(const CsrPart &P, const double *x, double *y, hipStream_t s, const int *done, const PushPlan *push, const DotPlan *dot)
@@ -487,36 +475,13 @@ int tiled_launch(const CsrPart &P, const double *x, double *y, hipStream_t s, co
     if (!T) return fail(hipErrorInvalidValue, "tiled A.x without a plan", __FILE__, __LINE__);
     const unsigned grid = 8u * (unsigned)((T->nwg + 7) / 8) + (push ? (unsigned)(push->nblocks + push->nrecv) : 0u);
     const PushPlan pp = push ? *push : PushPlan();
-    // ring depth and cache policy of the stream (A/B runs).  Measured on the 10M-row row-random band, same box: depth 2 / 3 / 4 / 6 / 8
-    // = 690 / 649 / 657 / 682 / 699 us (eight consumers keep 8 x D x 2 KB in flight through a 32 KB L1: deeper rings evict their
-    // own lines), and non-temporal loads on top 670 -> 598 us at depth 3 (the stream no longer pushes the tiles of x out of the
-    // L2 -- the kernel then reads at the rate of a pure sum over 4 GiB on the same box, 6.0 TB/s)
-    const int depth = tiled_depth(), nt = tiled_nt();
-    if (dot) {
-        if (!tiled_dot_ok(P)) return fail(hipErrorInvalidValue, "tiled A.x: this shape does not carry the dot", __FILE__, __LINE__);
-        const DotPlan dpv = *dot;
-        if (push) hipLaunchKernelGGL((k_tile_spmv2<8, 3, true, true, true>), dim3(grid), dim3(9 * 64), 0, s, T->n_rows, T->nwg, T->ntile, T->sofs, T->tl,
-                                     T->gstart, T->bstep, T->stream, x, T->n_cols, y, done, pp, dpv);
-        else hipLaunchKernelGGL((k_tile_spmv2<8, 3, false, true, true>), dim3(grid), dim3(9 * 64), 0, s, T->n_rows, T->nwg, T->ntile, T->sofs, T->tl,
-                                T->gstart, T->bstep, T->stream, x, T->n_cols, y, done, pp, dpv);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-#define TL_ARGS T->n_rows, T->nwg, T->ntile, T->sofs, T->tl, T->gstart, T->bstep, T->stream, x, T->n_cols, y, done, pp
-#define TL2(NW, DD)                                                                                                          \
-    do {                                                                                                                     \
-        if (push && nt) hipLaunchKernelGGL((k_tile_spmv2<NW, DD, true, true>), dim3(grid), dim3((NW + 1) * 64), 0, s, TL_ARGS);   \
-        else if (push) hipLaunchKernelGGL((k_tile_spmv2<NW, DD, true, false>), dim3(grid), dim3((NW + 1) * 64), 0, s, TL_ARGS);   \
-        else if (nt) hipLaunchKernelGGL((k_tile_spmv2<NW, DD, false, true>), dim3(grid), dim3((NW + 1) * 64), 0, s, TL_ARGS);     \
-        else hipLaunchKernelGGL((k_tile_spmv2<NW, DD, false, false>), dim3(grid), dim3((NW + 1) * 64), 0, s, TL_ARGS);            \
-    } while (0)
-    if (T->nw == 8) {
-        switch (depth) { case 2: TL2(8, 2); break; case 4: TL2(8, 4); break; case 6: TL2(8, 6); break; default: TL2(8, 3); }
-    } else if (T->nw == 4) {
-        TL2(4, 3);
-    } else
-        return fail(hipErrorInvalidValue, "tiled A.x: no kernel for this plan's shape", __FILE__, __LINE__);
-#undef TL2
+    const DotPlan dp = dot ? *dot : DotPlan();
+    const dim3 block((TL_NW + 1) * 64);
+#define TL_ARGS T->n_rows, T->nwg, T->ntile, T->sofs, T->tl, T->gstart, T->bstep, T->stream, x, T->n_cols, y, done, pp, dp
+    if (push && dot) hipLaunchKernelGGL((k_tile_spmv2<true, true>), dim3(grid), block, 0, s, TL_ARGS);
+    else if (dot) hipLaunchKernelGGL((k_tile_spmv2<false, true>), dim3(grid), block, 0, s, TL_ARGS);
+    else if (push) hipLaunchKernelGGL((k_tile_spmv2<true, false>), dim3(grid), block, 0, s, TL_ARGS);
+    else hipLaunchKernelGGL((k_tile_spmv2<false, false>), dim3(grid), block, 0, s, TL_ARGS);
 #undef TL_ARGS
     HIPCHK(hipGetLastError());
     return 0;
@@ -526,7 +491,7 @@ int tiled_launch(const CsrPart &P, const double *x, double *y, hipStream_t s, co
 long tiled_traffic_bytes(const CsrPart &P)
 {
     const TiledPlan *T = static_cast<const TiledPlan *>(P.tl_plan);
-    return T ? 8L * TL_BLK * T->steps + 4L * (T->nw + 1) * T->pairs + 8L * T->n_rows + 8L * T->n_cols : 0;
+    return T ? 8L * TL_BLK * T->steps + 4L * (TL_NW + 1) * T->pairs + 8L * T->n_rows + 8L * T->n_cols : 0;
 }
 long tiled_tile_copy_bytes(const CsrPart &P)
 {

@@ -138,15 +138,6 @@ template <class T> __device__ __forceinline__ T ldp(const double *p, long i, boo
 __device__ __forceinline__ void stp(double *p, long i, double v, bool nt) { if (nt) stnt(p, i, v); else st_(p, i, v); }
 __device__ __forceinline__ void stp(double *p, long i, double2 v, bool nt) { if (nt) stnt(p, i, v); else st_(p, i, v); }
 
-// y of the row-block product, by cache policy (internal.hpp: y_store_policy)
-__device__ __forceinline__ void store_y(double *p, double v, int how)
-{
-    if (how == 0) *p = v;
-    else if (how == 1) __builtin_nontemporal_store(v, p);
-    else if (how == 2) asm volatile("global_store_dwordx2 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-    else asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" ::"v"(p), "v"(v) : "memory");
-}
-
 // real helpers on 1 or 2 packed values
 __device__ __forceinline__ double dotp(double a, double b) { return a * b; }
 __device__ __forceinline__ double dotp(double2 a, double2 b) { return a.x * b.x + a.y * b.y; }
@@ -594,7 +585,7 @@ inline int grid_for(long n_items)
 {
     // 512 blocks (two per CU) keep the BLAS-1 passes at their bandwidth (measured on the 10M-row system: 2048 / 1024 / 512
     // blocks = 171 / 172 / 166 us of BLAS-1 per CG iteration) and leave a quarter of the partials to re-reduce
-    static const long cap = [] { const char *e = lab_env("LCG_HIP_MAXGRID"); long v = e ? atol(e) : 512; return v < 1 ? 1 : (v > MAXG ? (long)MAXG : v); }();
+    constexpr long cap = 512;
     long g = (n_items + VB - 1) / VB;
     if (g < 1) g = 1;
     if (g > cap) g = cap;

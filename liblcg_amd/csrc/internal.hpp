@@ -13,27 +13,7 @@
 
 namespace lcgh {
 
-// Run-time switches.  The shipped library reads the documented ones only ("Run-time switches": LCG_HIP_PACKED,
-// _TILED, _BINNED, _RANGES, _AX_DOT, _NT_VECTORS, _PACKED_WINDOW, _P2P_TIMEOUT_MS, _FORCE_COMM, _DEBUG, _PLACE,
-// _TEST_WITHHOLD_PUSH).  The knobs of the closed experiments (LAB_NOTES: thresholds, ring depths, batch sizes, A/B
-// switches of single kernels) exist in a LAB BUILD only -- `make LAB=1` compiles with -DLCG_HIP_LAB -- and read as unset
-// otherwise, so that every branch they select folds away in the shipped .so.
-inline const char *lab_env(const char *name)
-{
-#ifdef LCG_HIP_LAB
-    return std::getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
-// Cache policy of the row-block product's y stores (placement study, DESIGN 9 / profiles/r04_placement*): 0 plain, 1 non-temporal,
-// 2 write-through (sc1), 3 write-through at system scope (sc0 sc1).  LAB builds read LCG_HIP_Y_STORE.
-inline int y_store_policy()
-{
-    const char *e = lab_env("LCG_HIP_Y_STORE");      // (read at every launch: a lab program switches it between launches)
-    return e ? atoi(e) : 0;
-}
+// Run-time switches: the library reads the documented ones only ("Run-time switches").
 // LCG_HIP_DEBUG=1: the plan builders, the placement of the product's output and the direct exchange say on stderr what they chose and
 // why; 2: a solve also synchronises after every launch and names it (fault isolation)
 inline int debug_level()
@@ -117,7 +97,6 @@ struct DotPlan {
     double *part = nullptr;
     int yy = 0;
     int stride = AXP_CAP;   // distance of the y.y sums from the y.u sums in `part`
-    int ystore = 0;         // how k_spmv_ldsp stores y (devcommon.hpp: store_y; set by the host from y_store_policy())
     int ux = 0;             // u is the product's own x (CG, PCG: d.Ad): a run block that holds its diagonal takes u from its gathers
     int dof = 1;            // k_spmv_ldsp, long rows: a packed column field stands for `dof` consecutive columns (csr.hip: k_pk_dof)
 };
@@ -363,7 +342,6 @@ int tiled_ready(const CsrPart &P, hipStream_t s, double min_fill);      // 1 pla
 int tiled_launch(const CsrPart &P, const double *x, double *y, hipStream_t s, const int *done_flag, const PushPlan *push = nullptr,
                  const DotPlan *dot = nullptr);
 int tiled_chunks(const CsrPart &P);         // chunks of 1024 rows = per-chunk sums a dot-carrying tiled product leaves
-bool tiled_dot_ok(const CsrPart &P);        // the plan's shape has a dot-carrying instance
 void tiled_free(CsrPart &P);
 long tiled_traffic_bytes(const CsrPart &P);
 long tiled_tile_copy_bytes(const CsrPart &P);

@@ -435,7 +435,7 @@ struct RealSolve : Solve<false> {
     // the product honouring its verdict, and no event pair around a launch that may be empty (lcg_hip_last_ax_mean_us is about products).
     int ax_setup(const double *m0, double *y)
     {
-        if (Afp != lcg_hip_csr_ax || inst == nullptr || !zero_guess_probe()) return ax(m0, y);
+        if (Afp != lcg_hip_csr_ax || inst == nullptr) return ax(m0, y);
         int rc = drv.vec(OpZeroProbe{c.state, m0}, (uintptr_t)m0);
         if (!rc) rc = drv.scal(FinZeroGuess{});
         if (rc) return rc;
@@ -443,11 +443,6 @@ struct RealSolve : Solve<false> {
         Afp(inst, m0, y, n);
         c.ax_skip = nullptr;
         return c.ax_rc;
-    }
-    static bool zero_guess_probe()
-    {
-        static const bool on = [] { const char *e = lab_env("LCG_HIP_ZERO_GUESS"); return !e || atoi(e) != 0; }();     // (A/B runs)
-        return on;
     }
     // y = A.x followed by the sums y.u (and y.y): with the built-in product on a handle this process holds whole, the sums ride
     // in the product's epilogue (csr.hip: k_spmv_lds1d) and reach the next scalar step as its sum `row` (y.y: row + 1) -- *fused

@@ -61,21 +61,7 @@ static void probes(const char *tag, double *y) {
 }
 static void fill(double *x, unsigned seed) { k_fill<<<(unsigned)((N + 255) / 256), 256, 0, S>>>(x, N, seed); }
 
-static int FLAVORS = 0;
-static double time_pair1(const char *tag, const double *x, double *y);
 static double time_pair(const char *tag, const double *x, double *y) {
-    if (!FLAVORS) return time_pair1(tag, x, y);
-    double first = 0.0;
-    for (int f = 0; f < 4; ++f) {       // LAB library only: the y stores plain / non-temporal / sc1 / sc0 sc1, same vectors
-        char v[8], t2[96]; snprintf(v, sizeof v, "%d", f); setenv("LCG_HIP_Y_STORE", v, 1);
-        snprintf(t2, sizeof t2, "%s/ystore%d", tag, f);
-        double us = time_pair1(t2, x, y);
-        if (f == 0) first = us;
-    }
-    setenv("LCG_HIP_Y_STORE", "0", 1);
-    return first;
-}
-static double time_pair1(const char *tag, const double *x, double *y) {
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     int first = dispatch_no;
     for (int i = 0; i < 2; ++i) { lcg_hip_csr_ax(A, x, y, (int)N); ++dispatch_no; }
@@ -123,7 +109,6 @@ int main(int argc, char **argv) {
     int phases = argc > 2 ? atoi(argv[2]) : 31;       // bit mask A=1 B=2 C=4 D=8 E=16
     if (argc > 3) N = atoll(argv[3]);
     if (argc > 4) PROBES = atoi(argv[4]);
-    if (argc > 5) FLAVORS = atoi(argv[5]);
     if (lcg_hip_init(0)) { fprintf(stderr, "init: %s\n", lcg_hip_last_error()); return 2; }
     S = (hipStream_t)lcg_hip_get_stream();
     if (lcg_hip_csr_generate_ex(&A, N, 16, LCG_HIP_GEN_DIAGONALS, 131072, 1, 1, 0.01, 0, N)) { fprintf(stderr, "generate: %s\n", lcg_hip_last_error()); return 2; }
