@@ -318,9 +318,14 @@ int64_t lcg_hip_csr_packed_templates(lcg_hip_csr_t A);
  * LCG_HIP_BINNED=0/1 overrides for the whole process.  y differs from the row-block kernels' y in the last
  * bits (products are rounded before the add); on gfx950 it is bit-identical from call to call and from plan to plan
  * (lanes of one ds_add_f64 that meet in a row are serialised by the LDS in lane order: verified by test, not an ISA promise).
- * The packed, tiled and binned forms are COPIES of the matrix made at the first product: a caller who rewrites the
- * arrays of an adopted matrix (lcg_hip_csr_create with adopt != 0) afterwards drops them with set_*(A, 0) and
- * re-arms the automatic choice with set_*(A, -1). */
+ * The packed, tiled and binned forms, the row ranges and the op(A) copies of lcg_hip_spmv_op / clcg_hip_csr_ax are COPIES of
+ * the matrix made at their first use: a caller who rewrites the VALUES or COLUMNS of an adopted matrix (lcg_hip_csr_create with
+ * adopt != 0; same row pointers, columns in range) afterwards drops them with set_packed / set_tiled / set_binned /
+ * set_ranges(A, 0) -- any one of them frees the op(A) copies, each frees its own plan -- and re-arms the automatic choice with
+ * set_*(A, -1); every product then follows the new arrays.  New ROW POINTERS need a new handle (the kernel choice keeps what it
+ * read from them), and so does a rewritten complex64 matrix (lcg_hip_csr_create_c64: its set_* entries refuse, its op(A) copies
+ * are built once) and a sharded one (lcg_hip_csr_distribute: its rows' local and remote parts are copies split out of the arrays,
+ * which the setters do not rebuild). */
 int lcg_hip_csr_set_binned(lcg_hip_csr_t A, int mode);
 /* One-pass "tiled" A.x for matrices whose rows draw their columns at random from a band: the row-block kernels
  * find x in the L2 there but move a 128-byte line per 8-byte gather.  A workgroup owns 8 x 1024 rows (sums in LDS),

@@ -1690,10 +1690,24 @@ int lcg_hip_csr_set_kernel(lcg_hip_csr_t A, int variant)
     return 0;
 }
 
+} // extern "C"
+
+// set_*(A, 0) is the first half of the rewrite protocol (lcg_hip.h): the transposed / conjugated copies (op_part) are made from the
+// arrays too, so they go with the plans and are rebuilt from the new arrays at their next use
+static void op_copies_free(lcg_hip_csr *A)
+{
+    if (!A->op[1].rowptr && !A->op[2].rowptr && !A->op[3].rowptr) return;
+    if (ctx().inited) (void)hipDeviceSynchronize();
+    for (int i = 1; i < 4; i++) free_part(A->op[i]);
+}
+
+extern "C" {
+
 int lcg_hip_csr_set_packed(lcg_hip_csr_t A, int mode)
 {
     if (!A || mode < -1 || mode > 1) return LCG_HIP_E_ARG;
     TRY_C64(A, "lcg_hip_csr_set_packed");
+    if (mode == 0) op_copies_free(A);
     for (CsrPart *P : {&A->main, &A->loc}) {
         P->pk_mode = mode;
         ranges_free(*P);                    // the ranges inherit the modes: cut again at the next product
@@ -1711,6 +1725,7 @@ int lcg_hip_csr_set_binned(lcg_hip_csr_t A, int mode)
 {
     if (!A || mode < -1 || mode > 1) return LCG_HIP_E_ARG;
     TRY_C64(A, "lcg_hip_csr_set_binned");
+    if (mode == 0) op_copies_free(A);
     for (CsrPart *P : {&A->main, &A->loc}) {
         P->bn_mode = mode;
         ranges_free(*P);                    // the ranges inherit the modes: cut again at the next product
@@ -1724,6 +1739,7 @@ int lcg_hip_csr_set_tiled(lcg_hip_csr_t A, int mode)
 {
     if (!A || mode < -1 || mode > 1) return LCG_HIP_E_ARG;
     TRY_C64(A, "lcg_hip_csr_set_tiled");
+    if (mode == 0) op_copies_free(A);
     for (CsrPart *P : {&A->main, &A->loc}) {
         P->tl_mode = mode;
         ranges_free(*P);                    // the ranges inherit the modes: cut again at the next product
@@ -1737,6 +1753,7 @@ int lcg_hip_csr_set_ranges(lcg_hip_csr_t A, int mode)
 {
     if (!A || mode < -1 || mode > 1) return LCG_HIP_E_ARG;
     TRY_C64(A, "lcg_hip_csr_set_ranges");
+    if (mode == 0) op_copies_free(A);
     if (ctx().inited) (void)hipDeviceSynchronize();
     for (CsrPart *P : {&A->main, &A->loc}) { ranges_free(*P); P->rg_mode = mode; }
     return 0;

@@ -8,6 +8,8 @@ four FMA chains per row and a tree: both are within a few ulp of |A||x| per row,
 import numpy as np
 import pytest
 
+import exact_ref as X
+
 from conftest import FUZZ_SEED_OFFSET
 
 pytestmark = pytest.mark.gpu
@@ -57,6 +59,7 @@ def _check(api, lib, port, rp, col, val, x, ncols, expect_binned=True, fmt="binn
     assert torch.equal(y1, y2)                                      # call to call: same bits
     for y in (y0, y1):
         assert np.all(np.abs(y.cpu().numpy() - ref) <= 1e-13 * bound + 1e-300)
+        X.assert_rows(y.cpu().numpy(), rp, col, val, x, (fmt, n, ncols))
     if expect_binned:                                               # plan to plan: same bits
         B = api.CsrMatrix.from_csr(rp, col, val, n_cols=ncols)
         assert lib.lcg_hip_csr_set_binned(B.h, 0) == 0 and lib.lcg_hip_csr_set_tiled(B.h, 0) == 0 and setter(B.h, 1) == 0
@@ -113,6 +116,7 @@ def test_tiled_band_shapes(api, lib, port):
     assert b"k_tile_spmv" in lib.lcg_hip_csr_last_kernel(A.h)
     ref = port.csr_matvec(rp, col, val, x); bound = port.csr_matvec(rp, col, np.abs(val), np.abs(x))
     assert np.all(np.abs(y.cpu().numpy() - ref) <= 1e-13 * bound + 1e-300)
+    X.assert_rows(y.cpu().numpy(), rp, col, val, x, "unaligned x")
     A.destroy()
 
 
@@ -155,6 +159,7 @@ def test_dense_groups_and_out_of_range_columns(api, lib, port):
     A.spmv(torch.from_numpy(x).cuda(), y); api.synchronize()
     assert b"outside" in lib.lcg_hip_csr_binned_status(A.h) and b"k_bin" not in lib.lcg_hip_csr_last_kernel(A.h)
     assert np.abs(y.cpu().numpy() - port.csr_matvec(rp, col, val, x)).max() <= 1e-12 * np.abs(x).max() * 10
+    X.assert_rows(y.cpu().numpy(), rp, col, val, x, "refused plan")
 
 
 def test_automatic_choice_and_solvers(api, lib, port):

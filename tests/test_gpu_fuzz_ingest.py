@@ -5,6 +5,8 @@ A^T.x / A^H.x must equal the dense-free numpy products."""
 import numpy as np
 import pytest
 
+import exact_ref as X
+
 from conftest import FUZZ_SEED_OFFSET
 
 pytestmark = pytest.mark.gpu
@@ -33,11 +35,12 @@ def test_coo_ingest_and_transposes_fuzz():
         assert np.array_equal(ci, col[order]), case
         assert np.array_equal(v, val[order]), case
         x = rng.standard_normal(n) + (1j * rng.standard_normal(n) if cplx else 0)
-        xd = torch.from_numpy(x).cuda(); yd = torch.empty_like(xd)
+        xd = torch.from_numpy(x).cuda(); yd = torch.full_like(xd, float("nan"))
         A.spmv(xd, yd); api.synchronize()
         want = np.zeros(n, dtype=x.dtype); np.add.at(want, row, val * x[col])
         scale = max(1e-300, np.abs(want).max())
         assert np.abs(yd.cpu().numpy() - want).max() <= 1e-12 * scale + 1e-13, case
+        X.assert_rows(yd.cpu().numpy(), rp, ci, v, x, case)             # L_i counts the COO terms of row i, duplicates included
         if cplx:
             from liblcg_amd import _lib
             lib = _lib.load()
@@ -50,4 +53,8 @@ def test_coo_ingest_and_transposes_fuzz():
                 else:
                     np.add.at(w, row, f(val) * x[col])
                 assert np.abs(yd.cpu().numpy() - w).max() <= 1e-12 * max(1e-300, np.abs(w).max()) + 1e-13, (case, layout, conj)
+                orow, ocol = (col, row) if layout == 1 else (row, col)
+                oo = np.argsort(orow, kind="stable")
+                orp = np.zeros(n + 1, np.int64); np.add.at(orp, orow.astype(np.int64) + 1, 1)
+                X.assert_rows(yd.cpu().numpy(), np.cumsum(orp), ocol[oo], f(val)[oo], x, (case, layout, conj))
         A.destroy()

@@ -5,6 +5,8 @@ plain kernel must answer), sizes that are not multiples of 64, more columns than
 import numpy as np
 import pytest
 
+import exact_ref as X
+
 from conftest import FUZZ_SEED_OFFSET
 
 pytestmark = pytest.mark.gpu
@@ -105,5 +107,6 @@ def test_run_blocks_fuzz(port):
         assert torch.equal(y0, y1), (case, n, Lmain, lib.lcg_hip_csr_last_kernel(A.h))
         ref = port.csr_matvec(rp, col, val, x)
         assert np.abs(y1.cpu().numpy() - ref).max() <= 1e-12 * max(1e-300, np.abs(ref).max()), case
+        X.assert_rows(y1.cpu().numpy(), rp, col, val, x, (case, lib.lcg_hip_csr_last_kernel(A.h)))
         A.destroy()
     assert {"k_spmv_run1", "k_spmv_ldsp"} <= kernels, kernels

@@ -8,6 +8,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import exact_ref as X
+
 from conftest import FUZZ_SEED_OFFSET
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +21,7 @@ def _forms(api, lib, A, n, P, r, r0, r1, x, cplx):
     w = 2 if cplx else 1
     xd = torch.from_numpy(x).cuda()
     ys = []
-    y = torch.empty(r1 - r0, dtype=xd.dtype, device="cuda")
+    y = torch.full((r1 - r0,), float("nan"), dtype=xd.dtype, device="cuda")
     A.spmv(xd, y); api.synchronize()
     ys.append(y.cpu().numpy())
     assert lib.lcg_hip_csr_split_for_test(A.h, n, P, r) == 0, lib.lcg_hip_last_error()
@@ -31,7 +33,7 @@ def _forms(api, lib, A, n, P, r, r0, r1, x, cplx):
     rc = lib.lcg_hip_csr_direct_selfloop_for_test(A.h, P, r)
     assert rc == 0, lib.lcg_hip_last_error()
     for _ in range(3):          # both halves of the landing zone and the ticket reset get used
-        y.zero_()
+        y.fill_(float("nan"))
         A.spmv(xl, y); api.synchronize()
     ys.append(y.cpu().numpy().copy())
     return ys
@@ -68,8 +70,11 @@ def test_split_and_direct_forms_fuzz():
             val = rng.standard_normal(len(col)) + 1j * rng.standard_normal(len(col))
             A = api.CsrMatrix.from_csr(rp, col, val, n_cols=n)
             x = rng.standard_normal(n) + 1j * rng.standard_normal(n)
+        hrp, hci, hv = A.arrays_to_host()                           # the shard's rows, global columns
         y_unsplit, y_split, y_direct = _forms(api, lib, A, n, P, r, r0, r1, x, cplx)
         scale = max(1e-300, np.abs(y_unsplit).max())
         assert np.abs(y_split - y_unsplit).max() <= 1e-13 * scale, (case, P, r, n)
         assert np.abs(y_direct - y_unsplit).max() <= 1e-13 * scale, (case, P, r, n)
+        for form, yf in (("unsplit", y_unsplit), ("split", y_split), ("direct", y_direct)):
+            X.assert_rows(yf, hrp, hci, hv, x, (case, P, r, n, form))
         A.destroy()

@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import exact_ref as X
 from conftest import FUZZ_SEED_OFFSET
 
 pytestmark = pytest.mark.gpu
@@ -42,10 +43,11 @@ def test_spmv_all_variants_ragged(api, port, cplx):
     xd = torch.from_numpy(x).cuda(); yd = torch.empty_like(xd)
     scale = np.abs(ref).max()
     for var in (0, -1, -16, -32, -64, -128, -256, 1, 2, 4, 8, 16, 32, 64):
-        yd.zero_()
+        yd.fill_(float("nan"))          # (an unwritten row fails)
         A.set_kernel(var)
         A.spmv(xd, yd); api.synchronize()
         assert np.abs(yd.cpu().numpy() - ref).max() <= 1e-12 * scale, var
+        X.assert_rows(yd.cpu().numpy(), rp, col, val, x, ("variant", var))       # row by row, tests/exact_ref.py
 
 
 def test_packed_columns_are_bit_identical(api, port):
@@ -73,6 +75,7 @@ def test_packed_columns_are_bit_identical(api, port):
     A.spmv(xd, y1); api.synchronize()
     assert torch.equal(y0, y1)
     assert np.abs(y1.cpu().numpy() - ref).max() <= 1e-12 * np.abs(ref).max()
+    X.assert_rows(y1.cpu().numpy(), rp, col, val, x, "packed columns")
     # generated banded system, automatic R
     for band, eligible in ((3000, True), (0, False)):
         nn = 400000 if band else 3_000_000
@@ -126,6 +129,7 @@ def test_run_blocks_of_the_packed_form(api, port):
             assert torch.equal(y0, y1), (L, n, broken)
             ref = port.csr_matvec(rp, c.reshape(-1), val, x)
             assert np.abs(y1.cpu().numpy() - ref).max() <= 1e-12 * np.abs(ref).max()
+            X.assert_rows(y1.cpu().numpy(), rp, c.reshape(-1), val, x, (L, n, broken))
             A.destroy()
     # the generated constant-diagonal system: all blocks away from the first and last `band` rows are runs
     nn, band = 400000, 3000
@@ -213,6 +217,7 @@ def test_template_blocks_of_the_packed_form(api, port):
             ref = port.csr_matvec(rp, c, val, x)
             bound = port.csr_matvec(rp, c, np.abs(val), np.abs(x))
             assert float(np.max(np.abs(y1.cpu().numpy() - ref) / bound)) <= 1e-13, (dims, broken)
+            X.assert_rows(y1.cpu().numpy(), rp, c, val, x, (dims, broken))
             # the product the solver loops run: the dot carried by template blocks too
             u = torch.from_numpy(rng.standard_normal(n)).cuda()
             sums = (C.c_double * 2)()
@@ -221,8 +226,10 @@ def test_template_blocks_of_the_packed_form(api, port):
             assert lib.lcg_hip_spmv_dot(A.h, xd.data_ptr(), y2.data_ptr(), u.data_ptr(), sums) == 0
             # (another number of rows per block than the forced 64 above where the rows are short: other last bits)
             assert float(np.max(np.abs(y2.cpu().numpy() - ref) / bound)) <= 1e-13, (dims, broken, lib.lcg_hip_csr_last_kernel(A.h))
+            X.assert_rows(y2.cpu().numpy(), rp, c, val, x, (dims, broken, "dot"))
             yu = float(ref @ u.cpu().numpy()); yy = float(ref @ ref)
             assert abs(sums[0] - yu) <= 1e-11 * float(np.abs(ref) @ np.abs(u.cpu().numpy())) and abs(sums[1] - yy) <= 1e-12 * yy
+            X.assert_dot(sums[0], y2.cpu().numpy(), u.cpu().numpy(), (dims, broken)); X.assert_dot(sums[1], y2.cpu().numpy(), y2.cpu().numpy(), (dims, broken))
             A.destroy()
 
 
@@ -256,6 +263,7 @@ def test_template_blocks_with_several_unknowns_per_point(api, port):
         assert torch.equal(y0, y1), dims
         ref = port.csr_matvec(rp, ci, val, x)
         assert float(np.max(np.abs(y1.cpu().numpy() - ref) / port.csr_matvec(rp, ci, np.abs(val), np.abs(x)))) <= 1e-13
+        X.assert_rows(y1.cpu().numpy(), rp, ci, val, x, dims)
         A.destroy()
 
 
@@ -297,6 +305,7 @@ def test_short_row_runs_one_wavefront_per_block(api, port):
             assert torch.equal(y0, y1), (L, n)
             ref = port.csr_matvec(rp, col, val, x)
             assert np.abs(y1.cpu().numpy() - ref).max() <= 1e-12 * np.abs(ref).max()
+            X.assert_rows(y1.cpu().numpy(), rp, col, val, x, (L, n))
             # the same product carrying y.u and y.y: k_spmv_run1d up to 15 entries per row (its eight wavefronts' LDS), the
             # staged kernel's twin or two launches beyond -- y unchanged, sums to rounding
             u = rng.standard_normal(n); ud = torch.from_numpy(u).cuda()
@@ -306,6 +315,7 @@ def test_short_row_runs_one_wavefront_per_block(api, port):
             assert ("k_spmv_run1d" in kern) == (L <= 15), (L, n, kern)
             assert torch.equal(y0, y1), (L, n, kern)
             assert abs(res2[0] - float(ref @ u)) <= 1e-12 * float(np.abs(ref) @ np.abs(u)) and abs(res2[1] - float(ref @ ref)) <= 1e-12 * float(ref @ ref)
+            X.assert_dot(res2[0], y1.cpu().numpy(), u, (L, n)); X.assert_dot(res2[1], y1.cpu().numpy(), y1.cpu().numpy(), (L, n))
             A.destroy()
     # short-row stencils whose EVERY block holds boundary rows (grid lines no longer than the block): template blocks in the
     # one-wavefront-per-block kernel -- 7-point in 3D, 5-point and 9-point in 2D, 13-point (reach 2) in 3D
@@ -326,11 +336,13 @@ def test_short_row_runs_one_wavefront_per_block(api, port):
         assert torch.equal(y0, y1), dims
         ref = port.csr_matvec(rp, col, val, x)
         assert float(np.max(np.abs(y1.cpu().numpy() - ref) / port.csr_matvec(rp, col, np.abs(val), np.abs(x)))) <= 1e-13
+        X.assert_rows(y1.cpu().numpy(), rp, col, val, x, dims)
         u = rng.standard_normal(n); ud = torch.from_numpy(u).cuda()
         y1.fill_(7.0)
         assert lib.lcg_hip_spmv_dot(A.h, xd.data_ptr(), y1.data_ptr(), ud.data_ptr(), res2) == 0
         assert torch.equal(y0, y1), (dims, lib.lcg_hip_csr_last_kernel(A.h))
         assert abs(res2[0] - float(ref @ u)) <= 1e-12 * float(np.abs(ref) @ np.abs(u)) and abs(res2[1] - float(ref @ ref)) <= 1e-12 * float(ref @ ref)
+        X.assert_dot(res2[0], y1.cpu().numpy(), u, dims); X.assert_dot(res2[1], y1.cpu().numpy(), y1.cpu().numpy(), dims)
         A.destroy()
     # the Laplacian of configs[1] at a tenth of the size: mostly runs; a ragged matrix of the same density: none -> staged kernel
     A = api.CsrMatrix.laplace2d(400, 250); n = 100000
@@ -376,11 +388,14 @@ def test_spmv_transpose_and_conjugate(api, port, cplx):
                                      np.ascontiguousarray(x).ctypes.data_as(C.c_void_p), yo.ctypes.data_as(C.c_void_p),
                                      C.c_int(n), C.c_int(layout), C.c_int(conj))
                 assert np.abs(yo - ref).max() <= 1e-11 * np.abs(ref).max()
+            Mo = (M.T if layout else M).tocsr()
+            Mo = Mo.conj() if conj else Mo
             for rep in range(2):        # second call reuses the cached op(A)
-                yd.zero_()
+                yd.fill_(float("nan"))
                 assert lib.lcg_hip_spmv_op(A.h, xd.data_ptr(), yd.data_ptr(), layout, conj) == 0
                 api.synchronize()
                 assert np.abs(yd.cpu().numpy() - ref).max() <= 1e-12 * np.abs(ref).max(), (layout, conj)
+                X.assert_rows(yd.cpu().numpy(), Mo.indptr, Mo.indices, Mo.data, x, ("op", layout, conj))
     # the built transpose is deterministic: two independent builds give identical bits
     B = api.CsrMatrix.from_csr(rp, col, val)
     y2 = torch.empty_like(xd)
@@ -421,6 +436,8 @@ def test_product_carrying_its_dot(api, port):
         yr = port.csr_matvec(rp, col, val, x)
         bound = float(np.abs(yr) @ np.abs(u)) + 1e-300, float(yr @ yr) + 1e-300
         assert abs(res[0] - float(yr @ u)) <= 1e-12 * bound[0] and abs(res[1] - float(yr @ yr)) <= 1e-12 * bound[1], (n, max_len)
+        X.assert_rows(y1.cpu().numpy(), rp, col, val, x, (n, max_len))
+        X.assert_dot(res[0], y1.cpu().numpy(), u, (n, max_len)); X.assert_dot(res[1], y1.cpu().numpy(), y1.cpu().numpy(), (n, max_len))
         first = (res[0], res[1])
         assert lib.lcg_hip_spmv_dot(A.h, xd.data_ptr(), y1.data_ptr(), ud.data_ptr(), res) == 0
         assert (res[0], res[1]) == first
@@ -479,6 +496,7 @@ def test_spmv_edge_shapes(api, port):
         for var in (0, -64, 8):
             A.set_kernel(var); A.spmv(xd, yd); api.synchronize()
             assert np.allclose(yd.cpu().numpy(), port.csr_matvec(rp, col, val, x), rtol=0, atol=1e-13), (n, var)
+            X.assert_rows(yd.cpu().numpy(), rp, col, val, x, (n, var))
 
 
 def test_blas1(api, port):
@@ -562,6 +580,7 @@ def test_coo_ingest(api, port, case10k):
     xd = torch.from_numpy(x).cuda(); yd = torch.empty_like(xd)
     A.spmv(xd, yd); api.synchronize()
     assert np.allclose(yd.cpu().numpy(), port.coo_matvec(row, col, val, x), rtol=0, atol=1e-12)
+    X.assert_rows(yd.cpu().numpy(), rp3, ci3, v3, x, "coo")          # (the handle's CSR, checked above to be the stable sort)
     # duplicates of one (row, col) keep their input order too (stable), complex values included
     r2 = np.array([3, 0, 3, 3, 1, 0, 3], np.int32); c2 = np.array([1, 2, 1, 0, 1, 2, 1], np.int32)
     v2 = (np.arange(7) + 1) * (1 + 0.5j)
@@ -653,9 +672,10 @@ def test_sharded_product_on_one_gpu(api, port, nranks):
             assert lib.lcg_hip_csr_split_for_test(A.h, n, nranks, r) == 0
             xf = lib.lcg_hip_csr_xfull(A.h)
             assert lib.lcg_hip_memcpy(xf, xpad.ctypes.data, xpad.nbytes, 1) == 0
-            xl = torch.from_numpy(x[r0:r1].copy()).cuda(); yl = torch.empty_like(xl)
+            xl = torch.from_numpy(x[r0:r1].copy()).cuda(); yl = torch.full_like(xl, float("nan"))
             A.spmv(xl, yl); api.synchronize()
             assert np.abs(yl.cpu().numpy() - ref[r0:r1]).max() <= 1e-12 * np.abs(ref).max()
+            X.assert_rows(yl.cpu().numpy(), rp[r0:r1 + 1] - rp[r0], ci[rp[r0]:rp[r1]], v[rp[r0]:rp[r1]], x, ("shard", nranks, r, band))
             if band:
                 assert lib.lcg_hip_csr_local_nnz(A.h) > 0.9 * A.nnz
 
@@ -690,6 +710,23 @@ def test_full_size_properties(api):
     assert ((Ax - b).norm().item() / n) <= 1.01e-10                       # the monitored quantity, recomputed
 
 
+def _device_rows(lib, A, n):
+    """fetch(a, b) -> (rowptr from 0, col, val) of rows [a, b) of a real matrix, copied from the device window by window."""
+    pr, pc, pv = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    assert lib.lcg_hip_csr_arrays(A.h, C.byref(pr), C.byref(pc), C.byref(pv)) == 0
+    rp = np.empty(n + 1, np.int32)
+    assert lib.lcg_hip_memcpy(rp.ctypes.data, pr, rp.nbytes, 2) == 0
+
+    def fetch(a, b):
+        e0, e1 = int(rp[a]), int(rp[b])
+        col = np.empty(e1 - e0, np.int32); val = np.empty(e1 - e0, np.float64)
+        if e1 > e0:
+            assert lib.lcg_hip_memcpy(col.ctypes.data, pc.value + 4 * e0, col.nbytes, 2) == 0
+            assert lib.lcg_hip_memcpy(val.ctypes.data, pv.value + 8 * e0, val.nbytes, 2) == 0
+        return (rp[a:b + 1] - rp[a]).astype(np.int64), col, val
+    return fetch
+
+
 @pytest.mark.parametrize("pattern", ["constant_diagonals", "row_random_band", "scrambled"])
 def test_near_the_int32_limit(api, pattern):
     """The largest system the int32 CSR of the reference's interface can hold at this density: 60M rows, 1.98e9 entries
@@ -710,6 +747,7 @@ def test_near_the_int32_limit(api, pattern):
     # (scrambled: 2.1e8 (chunk, tile) groups of 9 entries -- the binned plan's granule offsets near THEIR limit too)
     want = {"constant_diagonals": "run blocks", "row_random_band": "k_tile_spmv", "scrambled": "k_bin_expand + k_bin_reduce"}[pattern]
     assert want in lib.lcg_hip_csr_last_kernel(A.h).decode(), (lib.lcg_hip_csr_last_kernel(A.h).decode(), lib.lcg_hip_csr_binned_status(A.h))
+    X.check_row_windows(Ax.cpu().numpy(), x.cpu().numpy(), n, _device_rows(lib, A, n), pattern)      # (a full reference: 24 GB)
     z = x + 2.0 * y
     A.spmv(z, Az); api.synchronize()
     assert (Az - (Ax + 2.0 * Ay)).abs().max().item() <= 1e-12 * Az.abs().max().item()
@@ -758,6 +796,7 @@ def test_block_structured_matrices_stay_with_the_row_block_kernels(api, port):
         ref = port.csr_matvec(rp, ci, val, x)
         bound = port.csr_matvec(rp, ci, np.abs(val), np.abs(x))
         assert float(np.max(np.abs(y.cpu().numpy() - ref) / bound)) <= 1e-13, (dims, dof, name)
+        X.assert_rows(y.cpu().numpy(), rp, ci, val, x, (dims, dof, name))
         A.destroy()
 
 
@@ -843,9 +882,11 @@ def test_long_rows_take_packed_columns(api, port):
         assert torch.equal(y0, y2), name
         yh = y0.cpu().numpy()
         assert abs(sums[0] - float(yh @ u)) <= 1e-12 * float(np.abs(yh) @ np.abs(u)) and abs(sums[1] - float(yh @ yh)) <= 1e-12 * float(yh @ yh), name
+        X.assert_dot(sums[0], y2.cpu().numpy(), u, name); X.assert_dot(sums[1], y2.cpu().numpy(), y2.cpu().numpy(), name)
         ref = port.csr_matvec(rp, ci, val, x)
         scale = port.csr_matvec(rp, ci, np.abs(val), np.abs(x))
         assert float(np.max(np.abs(yh - ref) / np.maximum(scale, 1e-300))) <= 1e-13, name
+        X.assert_rows(yh, rp, ci, val, x, name)
         assert 8 * len(ci) < lib.lcg_hip_csr_last_traffic_model(A.h) < 12 * len(ci) + 40 * n
         A.destroy()
 
@@ -886,6 +927,7 @@ def test_odd_shapes_against_the_oracle(api, port):
         ref = port.csr_matvec(rp, ci, v, xh)
         scale = port.csr_matvec(rp, ci, np.abs(v), np.abs(xh))
         assert float(np.max(np.abs(y.cpu().numpy() - ref) / np.maximum(scale, 1e-300))) <= 1e-13, (name, k)
+        X.assert_rows(y.cpu().numpy(), rp, ci, v, xh, (name, k))
         A.destroy()
 
 

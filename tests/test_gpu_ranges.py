@@ -14,6 +14,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import exact_ref as X
+
 from conftest import FUZZ_SEED_OFFSET, check_converged_run
 
 pytestmark = pytest.mark.gpu
@@ -96,11 +98,13 @@ def test_mixed_rows_against_the_oracle(port):
         ref = port.csr_matvec(rp, ci, v, xh)
         bound = port.csr_matvec(rp, ci, np.abs(v), np.abs(xh))
         assert float(np.max(np.abs(y.cpu().numpy() - ref) / bound)) <= 1e-13, (case, name)
+        X.assert_rows(y.cpu().numpy(), rp, ci, v, xh, (case, name))
         # one kernel family for all rows gives the same product to rounding
         assert lib.lcg_hip_csr_set_ranges(A.h, 0) == 0
         y0 = torch.empty_like(x); A.spmv(x, y0); api.synchronize()
         assert lib.lcg_hip_csr_ranges(A.h, 8, first) == 0
         assert float(np.max(np.abs(y0.cpu().numpy() - ref) / bound)) <= 1e-13, case
+        X.assert_rows(y0.cpu().numpy(), rp, ci, v, xh, case)
         assert lib.lcg_hip_csr_set_ranges(A.h, 1) == 0
         # solvers through the split product
         xt = torch.from_numpy(rng.standard_normal(n)).cuda()
@@ -151,6 +155,7 @@ def test_automatic_mode_cuts_only_where_a_cut_pays(port, grid, cuts):
     ref = port.csr_matvec(rp, ci, v, xh)
     bound = port.csr_matvec(rp, ci, np.abs(v), np.abs(xh))
     assert float(np.max(np.abs(y.cpu().numpy() - ref) / bound)) <= 1e-13, name
+    X.check_row_windows(y.cpu().numpy(), xh, n, lambda a, b: (rp[a:b + 1] - rp[a], ci[rp[a]:rp[b]], v[rp[a]:rp[b]]), (name,))
     A.destroy()
 
 
@@ -314,6 +319,7 @@ def test_random_class_layouts(port):
             nr = lib.lcg_hip_csr_ranges(A.h, 8, first)
             name = lib.lcg_hip_csr_last_kernel(A.h).decode()
             assert float(np.max(np.abs(y.cpu().numpy() - ref) / bound)) <= 1e-13, (case, mode, name)
+            X.assert_rows(y.cpu().numpy(), rp, ci, vv, xh, (case, mode, name))
             if mode == 1:
                 seen_ranges += nr
                 cuts = list(first[:nr])
@@ -368,6 +374,7 @@ def test_arrow_matrix_dense_rows_get_their_own_range(port):
     ref = port.csr_matvec(rp, ci, v, xh)
     bound = port.csr_matvec(rp, ci, np.abs(v), np.abs(xh))
     assert float(np.max(np.abs(y.cpu().numpy() - ref) / bound)) <= 1e-13, name
+    X.assert_rows(y.cpu().numpy(), rp, ci, v, xh, name)
     y2 = torch.empty_like(x); A.spmv(x, y2); api.synchronize()
     assert torch.equal(y, y2)                                       # the same bits from call to call
     t0 = time.perf_counter()
@@ -427,6 +434,7 @@ def test_small_system_with_a_dense_row(port):
     ref = port.csr_matvec(rp, ci, v, xh)
     bound = port.csr_matvec(rp, ci, np.abs(v), np.abs(xh))
     assert float(np.max(np.abs(y.cpu().numpy() - ref) / bound)) <= 1e-13, name
+    X.assert_rows(y.cpu().numpy(), rp, ci, v, xh, name)
     A.destroy()
     # the same band without the dense row: one kernel, no ranges
     M0 = (B + sp.triu(B, 1).T).tocsr(); M0.sort_indices()
