@@ -403,9 +403,22 @@ int  lcg_hip_csr_build_ic0(lcg_hip_csr_t A);
 int  lcg_hip_csr_build_ic0_c64(lcg_hip_csr_t A);
 /* Levels of L and L^T, kernel launches of one full apply, the failed pivot's row (-1 = none; what
  * cusparseXcsric02_zeroPivot reports), host milliseconds of the build, device bytes held by the factor.  Any pointer may be NULL.
+ * With sweeps set (lcg_hip_csr_ic0_set_sweeps) the launches are the sweep apply's 2k and the bytes include its two vectors.
  * This, lcg_hip_csr_ic0_factor and lcg_hip_csr_ic0_schedule_for_test serve every value type. */
 int  lcg_hip_csr_ic0_info(lcg_hip_csr_t A, int *levels_lower, int *levels_upper, int *launches_per_apply,
                           int *zero_pivot, double *build_ms, int64_t *bytes);
+/* How a factor is applied.  sweeps = 0 (the state after every build): the two triangular solves are exact, level by level.
+ * sweeps = k >= 1: every later apply on this handle -- lcg_hip_ic0_solve / _c64 for each `which`, and the three callbacks below --
+ * replaces each triangular solve T y = x (T = D + N, D its diagonal) by k Jacobi sweeps from y = 0:
+ *     y(1)_i = x_i / T(i,i),   y(j+1)_i = (x_i - sum_p T(i,c_p) y(j)_{c_p}) / T(i,i),   result y(k),
+ * each sweep one launch over all rows that reads y(j) and writes y(j+1) elsewhere (2k launches per full apply, no dependency
+ * between rows).  The operator is S^T.S with S = sum_{j<k} (-D^-1 N)^j D^-1: symmetric positive definite for a real factor
+ * and every k, complex symmetric for a complex one, and the same in every iteration, so PCG may use it.  A row is summed as
+ * the exact solve sums it, so k >= the triangle's level count returns the exact solve's bits.  which = 2 feeds L's result to
+ * L^T's sweeps.  Serves every value type.  Allocates (k >= 1) or frees (0) two vectors of the factor's type; not stream
+ * work otherwise, and may be called between solves.  LCG_HIP_E_ARG for a NULL handle, a handle without a factor, sweeps < 0. */
+int  lcg_hip_csr_ic0_set_sweeps(lcg_hip_csr_t A, int sweeps);
+int  lcg_hip_csr_ic0_get_sweeps(lcg_hip_csr_t A, int *sweeps);
 /* Device arrays of L in natural row order: rows sorted by column, the diagonal last.  For a complex64 factor `val` points to
  * interleaved float pairs (cast it to const float *, as for lcg_hip_csr_arrays). */
 int  lcg_hip_csr_ic0_factor(lcg_hip_csr_t A, const int **rowptr, const int **col, const double **val);

@@ -105,6 +105,8 @@ SIGNATURES = {
     "lcg_hip_ic0_mx": (None, [vp, vp, vp, C.c_int]),
     "clcg_hip_ic0_mx": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
     "lcg_hip_csr_ic0_schedule_for_test": (C.c_int, [vp, C.c_int]),
+    "lcg_hip_csr_ic0_set_sweeps": (C.c_int, [vp, C.c_int]),
+    "lcg_hip_csr_ic0_get_sweeps": (C.c_int, [vp, c_int_p]),
     "lcg_hip_csr_build_ic0_c64": (C.c_int, [vp]),
     "lcg_hip_ic0_solve_c64": (C.c_int, [vp, C.c_int, vp, vp]),
     "clcg_hip_ic0_mx_c64": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),

@@ -170,7 +170,8 @@ class CsrMatrix:
     # -- IC(0) preconditioner (csr_ic0.hip) -------------------------------------------------
     def build_ic0(self):
         """Factor A ~ L.L^T with zero fill on the device; pass "lcg_hip_ic0_mx" / "clcg_hip_ic0_mx" (a complex64 matrix:
-        "clcg_hip_ic0_mx_c64", factored in fp32) as Mfp afterwards."""
+        "clcg_hip_ic0_mx_c64", factored in fp32) as Mfp afterwards.  The factor is applied exactly, level by level, until
+        ic0_set_sweeps(k) asks for k Jacobi sweeps per triangle; every build resets that to 0."""
         if self.is_c64:
             _chk(L.load().lcg_hip_csr_build_ic0_c64(self.h), "build_ic0_c64")
         else:
@@ -181,8 +182,16 @@ class CsrMatrix:
         ms, nb = C.c_double(), C.c_int64()
         _chk(L.load().lcg_hip_csr_ic0_info(self.h, C.byref(ll), C.byref(lu), C.byref(la), C.byref(zp), C.byref(ms), C.byref(nb)),
              "ic0_info")
+        sw = C.c_int(0)
+        if L.load().lcg_hip_csr_ic0_get_sweeps(self.h, C.byref(sw)) != 0:      # (a failed factor has no setting)
+            sw.value = 0
         return {"levels_lower": ll.value, "levels_upper": lu.value, "launches_per_apply": la.value,
-                "zero_pivot": zp.value, "build_ms": ms.value, "bytes": nb.value}
+                "zero_pivot": zp.value, "build_ms": ms.value, "bytes": nb.value, "sweeps": sw.value}
+
+    def ic0_set_sweeps(self, k):
+        """k >= 1: apply the factor by k Jacobi sweeps per triangle (one launch each over all rows, 2k per apply) instead of the
+        exact level-scheduled solves; 0: exact again.  Holds for ic0_solve and the ic0_mx callbacks until the next build_ic0."""
+        _chk(L.load().lcg_hip_csr_ic0_set_sweeps(self.h, int(k)), "ic0_set_sweeps")
 
     def ic0_factor_to_host(self):
         """(rowptr, col, val) of L copied to numpy: natural row order, rows sorted, the diagonal last (complex64 values for

@@ -20,6 +20,12 @@
 // the build moves them with the real type's helpers as opaque 8-byte words (alloc_part / row_sort_launch / transpose_launch with
 // cplx = false).  k_row_sort breaks ties between duplicate (row, column) entries on those words: duplicates are summed in a
 // fixed order unless an imaginary part is Inf / NaN.  (L^T has no duplicate columns.)
+//
+// sweeps (lcg_hip_csr_ic0_set_sweeps, k >= 1): a triangle T = D + N is not solved but approximated by k Jacobi sweeps
+// y <- D^-1 (x - N.y) from y = 0: the first is y = x / diag (k_ic_scale), each later one a sparse triangular product over ALL
+// rows at once (k_ic_sweep: no level, no dependency between rows, one launch).  A sweep reads one vector and writes another,
+// so its result does not depend on which row runs first; a row is summed exactly as ic_solve_row sums it, so a row whose
+// inputs are final has the exact solve's bits, and after `levels` sweeps every row has.  2k launches per full apply.
 #include <chrono>
 #include <cmath>
 #include <numeric>
@@ -47,6 +53,8 @@ struct Ic0 {
     CsrPart L, LT;              // L: rows sorted, diagonal last; L^T: rows sorted, diagonal first
     IcTri fw, bw;
     double *tmp = nullptr;      // L^-1 x of the full apply (n values of the factor's type)
+    int sweeps = 0;             // 0: exact level-scheduled solves; k >= 1: k Jacobi sweeps per triangle
+    double *sw[2] = {nullptr, nullptr};     // the sweeps' two intermediate vectors (n values each, held while sweeps >= 1)
     int *zp = nullptr;          // device: smallest row whose pivot failed (INT_MAX: none)
     int zero_pivot = -1;
     int max_merged = IC_WG;     // widest level a narrow group takes (lcg_hip_csr_ic0_schedule_for_test)
@@ -198,6 +206,98 @@ __global__ __launch_bounds__(IC_WG) void k_ic_solve_narrow(const int *ord, const
     }
 }
 
+// ------------------------------------------------------------------------------------------- sweeps
+// One Jacobi sweep over a whole triangle: yout_i = (x_i - sum_p T(i,c_p) yin_{c_p}) / T(i,i) for every row i in ONE launch.
+// Row i is summed as ic_solve_row sums it (one accumulator from x_i, the products subtracted in column order, one ic_div).
+// The rows of a factor are short (half of A's row), so a thread per row straight out of CSR would read col / val at a stride
+// of the row length.  Instead (the row-block A.x kernels' shape, csr.hip) the workgroup's IC_SR consecutive rows own one
+// contiguous slice of col / val: it is loaded 16 bytes per lane into LDS, every load issued before the first LDS store, then
+// thread r walks row r out of LDS with up to four gathers of yin in flight, and yout is written coalesced.  A workgroup whose
+// slice does not fit the window (a dense row among its rows) walks its rows out of global memory: the same sums.
+constexpr int IC_SR = 256;      // rows of a sweep's workgroup = its threads
+constexpr int IC_SCH = 2048;    // its LDS window in entries (8 per row; 24 KiB with 8-byte values, 40 KiB with 16-byte ones)
+typedef int ic_v4i __attribute__((ext_vector_type(4)));
+typedef double ic_v2d __attribute__((ext_vector_type(2)));
+
+template <class V, bool UP>
+__global__ __launch_bounds__(IC_SR) void k_ic_scale(int n, const int *__restrict__ rowptr, const V *__restrict__ val,
+                                                   const V *__restrict__ x, V *__restrict__ y, const int *done)
+{   // the first sweep, from y = 0: y = x / diag
+    if (done && *done) return;
+    const int i = blockIdx.x * IC_SR + threadIdx.x;
+    if (i < n) y[i] = ic_div(x[i], val[UP ? rowptr[i] : rowptr[i + 1] - 1]);
+}
+
+template <class V, bool UP>
+__global__ __launch_bounds__(IC_SR) void k_ic_sweep(int n, const int *__restrict__ rowptr, const int *__restrict__ col,
+                                                   const V *__restrict__ val, const V *__restrict__ x, const V *__restrict__ yin,
+                                                   V *__restrict__ yout, const int *done)
+{
+    constexpr int NRND = IC_SCH / (IC_SR * 4);          // 4-entry units per lane
+    constexpr int VU = sizeof(V) / 4;                   // 16-byte pieces of val per 4 entries
+    constexpr int UNR = 4;                              // gathers of yin in flight per lane
+    __shared__ __attribute__((aligned(16))) V sval[IC_SCH];
+    __shared__ __attribute__((aligned(16))) int scol[IC_SCH];
+    if (done && *done) return;
+    const int tid = threadIdx.x;
+    const int row0 = blockIdx.x * IC_SR;
+    const int nrows = min(IC_SR, n - row0);
+    const int base = rowptr[row0] & ~3;
+    const int cnt = rowptr[row0 + nrows] - base;
+    // this lane's row bounds and x_i, requested before the slice's stream (vmcnt counts in order)
+    const int rsafe = tid < nrows ? tid : 0;
+    const int rs = rowptr[row0 + rsafe], re = rowptr[row0 + rsafe + 1];
+    V acc = x[row0 + rsafe];
+    const int b = UP ? rs + 1 : rs, f = UP ? re : re - 1, dg = UP ? rs : re - 1;
+    if (cnt > IC_SCH) {                                 // (uniform over the workgroup)
+        if (tid >= nrows) return;
+        for (int p = b; p < f; p++) acc = vsub(acc, ic_mul(val[p], yin[col[p]]));
+        yout[row0 + tid] = ic_div(acc, val[dg]);
+        return;
+    }
+    ic_v4i pc[NRND]; ic_v2d pv[NRND * VU];
+#pragma unroll
+    for (int r = 0; r < NRND; r++) {
+        const int u = tid * 4 + r * IC_SR * 4;
+        // branch-free: lanes past the slice re-read its first unit.  col / val carry 64 bytes of slack (alloc_part), so the
+        // slice's last unit may reach up to three entries past nnz.
+        const long g = (long)base + (u < cnt ? u : 0);
+        pc[r] = *reinterpret_cast<const ic_v4i *>(col + g);
+#pragma unroll
+        for (int q = 0; q < VU; q++) pv[r * VU + q] = reinterpret_cast<const ic_v2d *>(val + g)[q];
+    }
+    __builtin_amdgcn_sched_barrier(0);                  // every load above every LDS store
+#pragma unroll
+    for (int r = 0; r < NRND; r++) {
+        const int u = tid * 4 + r * IC_SR * 4;
+        if (u < cnt) {
+            *reinterpret_cast<ic_v4i *>(scol + u) = pc[r];
+#pragma unroll
+            for (int q = 0; q < VU; q++) reinterpret_cast<ic_v2d *>(sval + u)[q] = pv[r * VU + q];
+        }
+    }
+    __syncthreads();
+    if (tid >= nrows) return;
+    int p = b - base;
+    const int fe = f - base;
+    for (; p + UNR <= fe; p += UNR) {
+        V a[UNR], yv[UNR];
+#pragma unroll
+        for (int q = 0; q < UNR; q++) { a[q] = sval[p + q]; yv[q] = yin[scol[p + q]]; }
+#pragma unroll
+        for (int q = 0; q < UNR; q++) acc = vsub(acc, ic_mul(a[q], yv[q]));
+    }
+    {   // the row's last 0..3 entries, their gathers in flight together as well
+        V a[UNR - 1], yv[UNR - 1];
+        const int m = fe - p;
+#pragma unroll
+        for (int q = 0; q < UNR - 1; q++) if (q < m) { a[q] = sval[p + q]; yv[q] = yin[scol[p + q]]; }
+#pragma unroll
+        for (int q = 0; q < UNR - 1; q++) if (q < m) acc = vsub(acc, ic_mul(a[q], yv[q]));
+    }
+    yout[row0 + tid] = ic_div(acc, sval[dg - base]);
+}
+
 // --------------------------------------------------------------------------------------------- host
 static void tri_free(IcTri &t)
 {
@@ -210,6 +310,7 @@ static void ic0_release(Ic0 *F)
     free_part(F->L); free_part(F->LT);
     tri_free(F->fw); tri_free(F->bw);
     if (F->tmp) hipFree(F->tmp);
+    for (double *&p : F->sw) if (p) hipFree(p);
     if (F->zp) hipFree(F->zp);
     delete F;
 }
@@ -283,13 +384,38 @@ static int tri_solve(const Ic0 *F, const double *x, double *y, hipStream_t s, co
     return 0;
 }
 
+// k sweeps on one triangle: y(1) = x / diag, then y(j+1) from y(j) between the two intermediate vectors; the last one writes y
+template <class V, bool UP>
+static int tri_sweeps(const Ic0 *F, const double *x, double *y, hipStream_t s, const int *done)
+{
+    const CsrPart &T = UP ? F->LT : F->L;
+    const V *xv = reinterpret_cast<const V *>(x), *val = reinterpret_cast<const V *>(T.val);
+    V *const buf[2] = {reinterpret_cast<V *>(F->sw[0]), reinterpret_cast<V *>(F->sw[1])};
+    V *yv = reinterpret_cast<V *>(y);
+    const int k = F->sweeps;
+    const dim3 grid((unsigned)((F->n + IC_SR - 1) / IC_SR));
+    if (F->n == 0) return 0;
+    hipLaunchKernelGGL((k_ic_scale<V, UP>), grid, dim3(IC_SR), 0, s, F->n, T.rowptr, val, xv, k == 1 ? yv : buf[0], done);
+    for (int j = 2, cur = 0; j <= k; j++, cur ^= 1)
+        hipLaunchKernelGGL((k_ic_sweep<V, UP>), grid, dim3(IC_SR), 0, s, F->n, T.rowptr, T.col, val, xv, buf[cur], j == k ? yv : buf[cur ^ 1],
+                           done);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+template <class V, bool UP>
+static int tri_apply(const Ic0 *F, const double *x, double *y, hipStream_t s, const int *done)
+{
+    return F->sweeps > 0 ? tri_sweeps<V, UP>(F, x, y, s, done) : tri_solve<V, UP>(F, x, y, s, done);
+}
+
 template <class V>
 static int ic0_apply(const Ic0 *F, int which, const double *x, double *y, hipStream_t s, const int *done)
 {
-    if (which == 0) return tri_solve<V, false>(F, x, y, s, done);
-    if (which == 1) return tri_solve<V, true>(F, x, y, s, done);
-    int rc = tri_solve<V, false>(F, x, F->tmp, s, done);
-    return rc ? rc : tri_solve<V, true>(F, F->tmp, y, s, done);
+    if (which == 0) return tri_apply<V, false>(F, x, y, s, done);
+    if (which == 1) return tri_apply<V, true>(F, x, y, s, done);
+    int rc = tri_apply<V, false>(F, x, F->tmp, s, done);
+    return rc ? rc : tri_apply<V, true>(F, F->tmp, y, s, done);
 }
 
 // lower triangle of A, duplicates summed, one diagonal per row: into F->L (sorted rows)
@@ -467,7 +593,7 @@ int lcg_hip_csr_ic0_info(lcg_hip_csr_t A, int *levels_lower, int *levels_upper, 
     const Ic0 *F = ic0_of(A);
     if (levels_lower) *levels_lower = F->fw.levels;
     if (levels_upper) *levels_upper = F->bw.levels;
-    if (launches_per_apply) *launches_per_apply = (int)(F->fw.segs.size() + F->bw.segs.size());
+    if (launches_per_apply) *launches_per_apply = F->sweeps > 0 ? 2 * F->sweeps : (int)(F->fw.segs.size() + F->bw.segs.size());
     if (zero_pivot) *zero_pivot = F->zero_pivot;
     if (build_ms) *build_ms = F->build_ms;
     if (bytes) {
@@ -475,7 +601,38 @@ int lcg_hip_csr_ic0_info(lcg_hip_csr_t A, int *levels_lower, int *levels_upper, 
         *bytes = 2 * (4 * ((int64_t)F->n + 1) + (4 + vw) * F->L.nnz)               // L and L^T
                + 2 * 4 * (int64_t)F->n + 4 * ((int64_t)F->fw.levels + F->bw.levels + 2)   // level orders
                + vw * F->n + 4;                                                  // work vector, pivot word
+        if (F->sweeps > 0) *bytes += 2 * vw * F->n;                              // the sweeps' two intermediate vectors
     }
+    return 0;
+}
+
+int lcg_hip_csr_ic0_set_sweeps(lcg_hip_csr_t A, int sweeps)
+{
+    if (!A) return arg_error("lcg_hip_csr_ic0_set_sweeps: the handle is NULL");
+    Ic0 *F = ic0_of(A);
+    if (!F || !F->ok) return arg_error("lcg_hip_csr_ic0_set_sweeps: the handle has no factor (lcg_hip_csr_build_ic0, lcg_hip_csr_build_ic0_c64)");
+    if (sweeps < 0) return arg_error("lcg_hip_csr_ic0_set_sweeps: sweeps = %ld (0: the exact solves, k >= 1: k sweeps per triangle)", sweeps);
+    if (sweeps > 0 && !F->sw[0]) {
+        const size_t bytes = (F->c64 ? sizeof(float2) : sizeof(double) * (F->cplx ? 2 : 1)) * (size_t)std::max(F->n, 1);
+        for (double *&p : F->sw) {
+            if (hipMalloc(&p, bytes) == hipSuccess) continue;
+            for (double *&q : F->sw) { if (q) hipFree(q); q = nullptr; }
+            return fail(hipErrorOutOfMemory, "ic0 sweep vectors", __FILE__, __LINE__);
+        }
+    }
+    if (sweeps == 0)                            // (hipFree waits for the applies still on the stream)
+        for (double *&p : F->sw) { if (p) hipFree(p); p = nullptr; }
+    F->sweeps = sweeps;
+    return 0;
+}
+
+int lcg_hip_csr_ic0_get_sweeps(lcg_hip_csr_t A, int *sweeps)
+{
+    if (!A) return arg_error("lcg_hip_csr_ic0_get_sweeps: the handle is NULL");
+    const Ic0 *F = ic0_of(A);
+    if (!F || !F->ok) return arg_error("lcg_hip_csr_ic0_get_sweeps: the handle has no factor (lcg_hip_csr_build_ic0, lcg_hip_csr_build_ic0_c64)");
+    if (!sweeps) return arg_error("lcg_hip_csr_ic0_get_sweeps: sweeps is NULL");
+    *sweeps = F->sweeps;
     return 0;
 }
 
