@@ -441,6 +441,58 @@ void clcg_hip_ic0_mx_c64(void *instance, const float *x, float *prod_Mx, const i
 /* Test hook: the widest level a one-workgroup launch may take over several levels (0: one launch per level; -1: production). */
 int  lcg_hip_csr_ic0_schedule_for_test(lcg_hip_csr_t A, int max_merged_rows);
 
+/* ---------------------------------------------------------------- ILU(0) preconditioner */
+/* Incomplete LU with zero fill on the pattern of A (every entry; one explicit zero is added on every diagonal, duplicate
+ * entries are summed, columns may come in any order): A ~ L.U with a unit lower L, unconjugated for complex A,
+ *     w(i,j) = A(i,j) - sum_{k < min(i,j)} L(i,k) U(k,j),   U(i,j) = w(i,j) (j >= i),   L(i,j) = w(i,j) / U(j,j) (j < i).
+ * No square root is taken, so a symmetric indefinite or a non-symmetric matrix factors where IC(0) cannot: the only failed
+ * pivot is U(i,i) that is 0 or not finite (a negative real pivot is fine).  Factored on the device over L's forward level
+ * schedule; L and U are copies (rebuild after rewriting an adopted matrix), freed by lcg_hip_csr_destroy, held in a slot of
+ * their own: IC(0) and ILU(0) may live on one handle.  Rebuilds on repeat.  LCG_HIP_E_ARG for a non-square or sharded matrix,
+ * a complex64 handle or a failed pivot: lcg_hip_last_error() names the smallest such row.
+ * Stands in for cusparseZcsrilu02 and its analysis (sample11.cu:231-262) and for lcg_incomplete_LU / clcg_incomplete_LU of
+ * the Eigen back-end (preconditioner_eigen.h:109-119; sample7).  Serves fp64 and complex128 handles. */
+int  lcg_hip_csr_build_ilu0(lcg_hip_csr_t A);
+/* Levels of L (forward) and of U (backward, from U's own pattern), kernel launches of one full apply, the failed pivot's row
+ * (-1 = none; what cusparseXcsrilu02_zeroPivot reports), host milliseconds of the build, device bytes held by the factor.
+ * Any pointer may be NULL.  With sweeps set the launches are what the sweep apply really launches, 2k - 1 for k >= 2 and 2
+ * for k = 1 (below), and the bytes include its two vectors. */
+int  lcg_hip_csr_ilu0_info(lcg_hip_csr_t A, int *levels_L, int *levels_U, int *launches_per_apply, int *zero_pivot,
+                           double *build_ms, int64_t *bytes);
+/* How the factor is applied, with the contract of lcg_hip_csr_ic0_set_sweeps.  sweeps = 0 (the state after every build): two
+ * exact triangular solves, level by level.  sweeps = k >= 1: each solve T y = x (T = D + N) becomes k Jacobi sweeps from
+ * y = 0, y(j+1) = D^-1 (x - N y(j)), every sweep one launch over all rows; D = I for L, so L's first sweep is y = x and
+ * costs no launch of its own when k >= 2 (the second sweep reads x), one copy when k = 1.  A row is summed as the exact solve
+ * sums it, so k >= the triangle's level count returns the exact solve's bits.  The operator is the same in every iteration.
+ * For a symmetric A, U = D.L^T and the sweep operator is P^T D^-1 P with P = sum_{j<k} (-N)^j, N = L - I, D = diag U: it stays
+ * symmetric in exact arithmetic for every k, so PCG may use it (positive definite when every pivot is positive).
+ * Allocates (k >= 1) or frees (0) two vectors; LCG_HIP_E_ARG for a NULL handle, a handle without a factor, sweeps < 0. */
+int  lcg_hip_csr_ilu0_set_sweeps(lcg_hip_csr_t A, int sweeps);
+int  lcg_hip_csr_ilu0_get_sweeps(lcg_hip_csr_t A, int *sweeps);
+/* Device arrays of L (which 0: rows sorted by column, the unit diagonal not stored) or U (which 1: rows sorted, the diagonal
+ * first), in natural row order. */
+int  lcg_hip_csr_ilu0_factor(lcg_hip_csr_t A, int which, const int **rowptr, const int **col, const double **val);
+/* y = L^-1 x (which 0), U^-1 x (1) or U^-1 L^-1 x (2) on the current stream; x, y on the device and not overlapping.  Neither
+ * allocates nor synchronises; honours a running solve's stop flag (the two cusparseZcsrsv2_solve of sample11.cu:100-121). */
+int  lcg_hip_ilu0_solve(lcg_hip_csr_t A, int which, const double *x, double *y);
+/* Ready-made preconditioner callbacks, z = U^-1 L^-1 x; pass the lcg_hip_csr_t as `instance`.  A handle without a factor, the
+ * wrong value type or n_size other than the row count end the solve with LCG_HIP_E_ARG; so do layout = 1 and conjugate = 1
+ * (M = L.U is not symmetric in general; the PCG and PBiCG loops ask for (0, 0)). */
+void lcg_hip_ilu0_mx(void *instance, const double *x, double *prod_Mx, const int n_size);
+void clcg_hip_ilu0_mx(void *instance, const double *x, double *prod_Mx, const int n_size,
+                      int layout, int conjugate);                                                 /* sample11.cu:100-121 (cudaMx_ILU) */
+/* Right preconditioning for the loops that take no Mfp (lcg_hip_solver: LCG_BICGSTAB, LCG_BICGSTAB2, LCG_CGS;
+ * clcg_hip_solver: the loops that ask for (layout, conjugate) = (0, 0) only): an Afp that computes y = A.(U^-1 L^-1 x) -- the
+ * factor's apply into a vector the factor owns, then the handle's ordinary product.  Solve A.M^-1 u = b from u = 0 with it,
+ * then x = M^-1 u by lcg_hip_ilu0_solve(A, 2, u, x).  The residual b - A.M^-1 u is b - A.x, the same vector either way; the
+ * relative stop rule divides by max(u.u, 1), so it sees |u|, not |x|.  The solver treats these as callbacks of the caller's
+ * own (the product carries no dot, nothing is timed or placed).  Same failures as the Mfp callbacks above. */
+void lcg_hip_csr_ax_ilu0(void *instance, const double *x, double *prod_Ax, const int n_size);
+void clcg_hip_csr_ax_ilu0(void *instance, const double *x, double *prod_Ax, const int n_size,
+                          int layout, int conjugate);
+/* Test hook: the widest level a one-workgroup launch may take over several levels (0: one launch per level; -1: production). */
+int  lcg_hip_csr_ilu0_schedule_for_test(lcg_hip_csr_t A, int max_merged_rows);
+
 /* ---------------------------------------------------------------- kernels */
 /* Stand-alone launches of the hot-path kernels on the current stream (device pointers).
  * Scalar results are written to host memory after a stream synchronise. */

@@ -110,6 +110,17 @@ SIGNATURES = {
     "lcg_hip_csr_build_ic0_c64": (C.c_int, [vp]),
     "lcg_hip_ic0_solve_c64": (C.c_int, [vp, C.c_int, vp, vp]),
     "clcg_hip_ic0_mx_c64": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
+    "lcg_hip_csr_build_ilu0": (C.c_int, [vp]),
+    "lcg_hip_csr_ilu0_info": (C.c_int, [vp, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p, C.POINTER(C.c_int64)]),
+    "lcg_hip_csr_ilu0_set_sweeps": (C.c_int, [vp, C.c_int]),
+    "lcg_hip_csr_ilu0_get_sweeps": (C.c_int, [vp, c_int_p]),
+    "lcg_hip_csr_ilu0_factor": (C.c_int, [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "lcg_hip_ilu0_solve": (C.c_int, [vp, C.c_int, vp, vp]),
+    "lcg_hip_ilu0_mx": (None, [vp, vp, vp, C.c_int]),
+    "clcg_hip_ilu0_mx": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
+    "lcg_hip_csr_ax_ilu0": (None, [vp, vp, vp, C.c_int]),
+    "clcg_hip_csr_ax_ilu0": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
+    "lcg_hip_csr_ilu0_schedule_for_test": (C.c_int, [vp, C.c_int]),
     "lcg_hip_csr_ax": (None, [vp, vp, vp, C.c_int]),
     "lcg_hip_jacobi_mx": (None, [vp, vp, vp, C.c_int]),
     "clcg_hip_csr_ax": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),

@@ -215,6 +215,50 @@ class CsrMatrix:
         else:
             _chk(L.load().lcg_hip_ic0_solve(self.h, which, _ptr(x)[0], _ptr(y)[0]), "ic0_solve")
 
+    # -- ILU(0) preconditioner (csr_ilu0.hip) -----------------------------------------------
+    def build_ilu0(self):
+        """Factor A ~ L.U (unit lower L) with zero fill on the device, fp64 and complex128 matrices; pass "lcg_hip_ilu0_mx" /
+        "clcg_hip_ilu0_mx" as Mfp afterwards, or "lcg_hip_csr_ax_ilu0" / "clcg_hip_csr_ax_ilu0" as Afp of a loop without an
+        Mfp (right preconditioning: solve for u from u = 0, then ilu0_solve(u, x)).  Applied exactly, level by level, until
+        ilu0_set_sweeps(k); every build resets that to 0.  Lives beside an IC(0) factor on the same matrix."""
+        _chk(L.load().lcg_hip_csr_build_ilu0(self.h), "build_ilu0")
+
+    def ilu0_info(self) -> dict:
+        ll, lu, la, zp = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        ms, nb = C.c_double(), C.c_int64()
+        _chk(L.load().lcg_hip_csr_ilu0_info(self.h, C.byref(ll), C.byref(lu), C.byref(la), C.byref(zp), C.byref(ms), C.byref(nb)),
+             "ilu0_info")
+        sw = C.c_int(0)
+        if L.load().lcg_hip_csr_ilu0_get_sweeps(self.h, C.byref(sw)) != 0:     # (a failed factor has no setting)
+            sw.value = 0
+        return {"levels_L": ll.value, "levels_U": lu.value, "launches_per_apply": la.value,
+                "zero_pivot": zp.value, "build_ms": ms.value, "bytes": nb.value, "sweeps": sw.value}
+
+    def ilu0_set_sweeps(self, k):
+        """k >= 1: apply the factor by k Jacobi sweeps per triangle (L: k - 1 launches, one when k = 1; U: k) instead of the
+        exact level-scheduled solves; 0: exact again.  Holds for ilu0_solve and the four callbacks until the next build_ilu0."""
+        _chk(L.load().lcg_hip_csr_ilu0_set_sweeps(self.h, int(k)), "ilu0_set_sweeps")
+
+    def ilu0_factor_to_host(self, which):
+        """(rowptr, col, val) of L (which 0: rows sorted, unit diagonal not stored) or U (1: rows sorted, diagonal first)
+        copied to numpy."""
+        lib = L.load()
+        pr, pc, pv = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _chk(lib.lcg_hip_csr_ilu0_factor(self.h, int(which), C.byref(pr), C.byref(pc), C.byref(pv)), "ilu0_factor")
+        rowptr = np.empty(self.n + 1, np.int32)
+        _chk(lib.lcg_hip_memcpy(rowptr.ctypes.data, pr, rowptr.nbytes, 2), "memcpy d2h")
+        nnz = int(rowptr[-1])
+        col = np.empty(nnz, np.int32)
+        val = np.empty(nnz, np.complex128 if self.is_complex else np.float64)
+        for dst, src in ((col, pc), (val, pv)):
+            if nnz:
+                _chk(lib.lcg_hip_memcpy(dst.ctypes.data, src, dst.nbytes, 2), "memcpy d2h")
+        return rowptr, col, val
+
+    def ilu0_solve(self, x, y, which=2):
+        """y = L^-1 x (which 0), U^-1 x (1) or U^-1 L^-1 x (2); device tensors, on the library's stream."""
+        _chk(L.load().lcg_hip_ilu0_solve(self.h, which, _ptr(x)[0], _ptr(y)[0]), "ilu0_solve")
+
     def spmv(self, x, y):
         _chk(L.load().lcg_hip_spmv(self.h, _ptr(x)[0], _ptr(y)[0]), "spmv")
 

@@ -1667,6 +1667,7 @@ int lcg_hip_csr_destroy(lcg_hip_csr_t A)
     for (int i = 1; i < 4; i++) free_part(A->op[i]);
     if (A->invdiag) hipFree(A->invdiag);
     ic0_free(A);
+    ilu0_free(A);
     c64_free(A);
     delete A;
     return 0;

@@ -310,6 +310,7 @@ struct lcg_hip_csr {
     void *halo = nullptr;       // neighbour-exchange plan (comm.hip)
     void *direct = nullptr;     // direct (peer-mapped) exchange state (comm.hip, mode 2)
     void *ic0 = nullptr;        // incomplete-Cholesky factor and its level schedules (csr_ic0.hip), a copy: built by lcg_hip_csr_build_ic0
+    void *ilu0 = nullptr;       // incomplete-LU factor L, U and their level schedules (csr_ilu0.hip), copies: built by lcg_hip_csr_build_ilu0
     // --- complex64 values (csr_c64.hip) ---
     bool c64 = false;           // main.val holds n_nnz interleaved (re, im) floats (8 B per entry); is_complex stays false
     void *c64p = nullptr;       // the products' plans and the Jacobi reciprocals of such a matrix (csr_c64.hip: C64Data)
@@ -356,6 +357,8 @@ int transpose_launch(int n, int nt, long nnz, const int *rowptr, const int *col,
 void row_sort_launch(int n, const int *rowptr, int *col, double *val, bool cplx, hipStream_t s);    // k_row_sort: by (column, value)
 // csr_ic0.hip
 void ic0_free(lcg_hip_csr *A);
+// csr_ilu0.hip
+void ilu0_free(lcg_hip_csr *A);
 // csr.hip
 void free_part(CsrPart &P);                                          // a part's arrays and every plan built beside them
 
