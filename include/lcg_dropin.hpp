@@ -176,6 +176,29 @@ inline void clcg_csr_ax(void *instance, const lcg_complex *x, lcg_complex *prod_
                     (int)layout, (int)conjugate);
 }
 
+// ---- dense operators ---------------------------------------------------------------------------
+// lcg_matvec (algebra.h, algebra.cpp:165-193) and clcg_matvec (lcg_complex.cpp:169-234) on a matrix the library holds in
+// HBM: the first argument is the lcg_hip_dense_t (lcg_hip_dense_create / lcg_hip_dense_create_rows), x and Ax are DEVICE
+// vectors (inside a callback: the solver's own), the work is enqueued on lcg_hip_get_stream().  The reference's
+// lcg_float ** / lcg_complex ** overloads are host code and are not provided: a program that still passes host row
+// pointers does not compile, instead of silently computing on the wrong side.  Returns the C ABI's status (0 = enqueued).
+inline int lcg_matvec(lcg_hip_dense_t K, const lcg_float *x, lcg_float *Ax, lcg_matrix_e layout = MatNormal)
+{
+    return lcg_hip_dense_matvec(K, x, Ax, (int)layout);
+}
+inline int clcg_matvec(lcg_hip_dense_t K, const lcg_complex *x, lcg_complex *Ax, lcg_matrix_e layout = MatNormal,
+                       clcg_complex_e conjugate = NonConjugate)
+{
+    return clcg_hip_dense_matvec(K, reinterpret_cast<const double *>(x), reinterpret_cast<double *>(Ax), (int)layout, (int)conjugate);
+}
+// the ready-made complex dense callback with the reference's C++ signature (sample3.cpp:44-49)
+inline void clcg_dense_ax(void *instance, const lcg_complex *x, lcg_complex *prod_Ax, const int n,
+                          lcg_matrix_e layout, clcg_complex_e conjugate)
+{
+    clcg_hip_dense_ax(instance, reinterpret_cast<const double *>(x), reinterpret_cast<double *>(prod_Ax), n,
+                      (int)layout, (int)conjugate);
+}
+
 // util.cpp:53-148 (plain text; the reference's terminal colouring is not reproduced)
 inline const char *lcg_status_text(int code)
 {

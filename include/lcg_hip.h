@@ -493,6 +493,58 @@ void clcg_hip_csr_ax_ilu0(void *instance, const double *x, double *prod_Ax, cons
 /* Test hook: the widest level a one-workgroup launch may take over several levels (0: one launch per level; -1: production). */
 int  lcg_hip_csr_ilu0_schedule_for_test(lcg_hip_csr_t A, int max_merged_rows);
 
+/* ---------------------------------------------------------------- dense operators */
+/* A dense M x N matrix resident in HBM, row-major, fp64 or complex128 (interleaved): the operator of liblcg's own samples,
+ * whose products are lcg_matvec (algebra.cpp:165-193) and clcg_matvec (lcg_complex.cpp:169-234).  A handle of its own kind:
+ * both kinds of handle begin with a word that says which kind they are.  Every lcg_hip_dense_* / clcg_hip_dense_* entry returns
+ * LCG_HIP_E_ARG for a handle that is not a dense one (a CSR handle included), and EVERY entry that takes a lcg_hip_csr_t, or a
+ * CSR handle as a callback's instance, refuses a dense handle before it reads anything else of it: LCG_HIP_E_ARG from the entries
+ * that return a status or a count, "" / NULL from those that return a string or a pointer, and a callback ends the solve with
+ * LCG_HIP_E_ARG; lcg_hip_last_error() names the entry.  A handle is at least 8 readable bytes.  The library keeps ONE copy, rows padded to 16 bytes, and no second copy for the transposed or conjugated
+ * forms: 8 bytes per entry and product (16 complex) where a full CSR stores 12 (20) and gathers x. */
+typedef struct lcg_hip_dense *lcg_hip_dense_t;
+
+/* Copy an m_rows x n_cols matrix: val[i * ld + j] (ld >= n_cols, counted in entries: doubles, or complex pairs when is_complex),
+ * host (mem = LCG_HIP_MEM_HOST) or device memory.  LCG_HIP_E_ARG for a NULL pointer, m_rows or n_cols <= 0, ld < n_cols. */
+int lcg_hip_dense_create(lcg_hip_dense_t *K, int m_rows, int n_cols, const double *val, int64_t ld, int is_complex, int mem);
+/* The same from liblcg's own layout: m_rows HOST row pointers (lcg_float ** / lcg_complex **: lcg_malloc(m, n), algebra.cpp:60-98). */
+int lcg_hip_dense_create_rows(lcg_hip_dense_t *K, int m_rows, int n_cols, const double *const *rows, int is_complex);
+int lcg_hip_dense_destroy(lcg_hip_dense_t K);
+int lcg_hip_dense_rows(lcg_hip_dense_t K);
+int lcg_hip_dense_cols(lcg_hip_dense_t K);
+/* lcg_matvec: layout 0 (MatNormal) y[M] = K.x[N]; layout 1 (MatTranspose) y[N] = K^T.x[M].  x, y: device vectors, x != y; launched
+ * on the library's stream, neither allocates nor synchronises.  Every product is bit-identical from call to call. */
+int lcg_hip_dense_matvec(lcg_hip_dense_t K, const double *x, double *y, int layout);
+/* clcg_matvec's four forms.  conjugate = 1 is the reference's Conjugate (lcg_complex.cpp:184-185, 198-199): conj(K).x or K^H.x --
+ * the ENTRIES are conjugated, x is not. */
+int clcg_hip_dense_matvec(lcg_hip_dense_t K, const double *x, double *y, int layout, int conjugate);
+/* y[N] = K^T.(K.x[N]), real K: the normal-equations product of sample1.cpp:48-53.  The M-vector in between belongs to the handle. */
+int lcg_hip_dense_ata(lcg_hip_dense_t K, const double *x, double *y);
+/* Ready-made callbacks; pass the lcg_hip_dense_t as `instance`.  A handle of another kind, the wrong value type or an n_size that
+ * is not the matrix's N end the solve with LCG_HIP_E_ARG (lcg_hip_last_error() says which) and write nothing. */
+void lcg_hip_dense_ata_ax(void *instance, const double *x, double *prod_Ax, const int n_size);    /* sample1.cpp:48-53 (CalAx) */
+void lcg_hip_dense_ax(void *instance, const double *x, double *prod_Ax, const int n_size);        /* y = K.x, square K */
+void clcg_hip_dense_ax(void *instance, const double *x, double *prod_Ax, const int n_size,
+                       int layout, int conjugate);                                                 /* sample3.cpp:44-49 (CalAx) */
+/* The Jacobi preconditioner of the samples.  normal = 1 (real K): d_i = sum_j K(j,i)^2, the diagonal of K^T.K, by one more
+ * column-form pass (sample1.cpp:98-107).  normal = 0 (square K, real or complex): d_i = K(i,i).  The reciprocals are kept for the
+ * callbacks below; diag_out (device, N values; may be NULL) receives d.  LCG_HIP_E_ARG when an entry of d is zero or not finite:
+ * lcg_hip_last_error() names the smallest such index.  Synchronises. */
+int lcg_hip_dense_build_jacobi(lcg_hip_dense_t K, int normal, double *diag_out);
+void lcg_hip_dense_jacobi_mx(void *instance, const double *x, double *prod_Mx, const int n_size);  /* sample1.cpp:55-62, reciprocal form */
+void clcg_hip_dense_jacobi_mx(void *instance, const double *x, double *prod_Mx, const int n_size,
+                              int layout, int conjugate);
+/* Name of the kernel family the latest product with K used ("" before the first), and the list of all of them
+ * (index 0, 1, ...; NULL behind the last): k_dn_row, k_dn_row_split, k_dn_col, k_dn_ata_two_pass, k_dn_ata_one_pass,
+ * k_dn_ata_small. */
+const char *lcg_hip_dense_last_kernel(lcg_hip_dense_t K);
+const char *lcg_hip_dense_kernel_name(int index);
+/* Force a path: 0 automatic; 1 k_dn_row and 2 k_dn_row_split for K.x; 4 two passes, 5 one pass and 6 the one-workgroup form for
+ * K^T.K.x (5, 6: real K, N <= 2048; 6 is never chosen automatically; 2 is refused where there is nothing to split: rows of
+ * fewer than 32 16-byte packs, or M >= 8192).  K^T.x has one form (3 is accepted and changes nothing).  A forced path holds for the
+ * products it names; the others stay automatic. */
+int lcg_hip_dense_set_kernel(lcg_hip_dense_t K, int variant);
+
 /* ---------------------------------------------------------------- kernels */
 /* Stand-alone launches of the hot-path kernels on the current stream (device pointers).
  * Scalar results are written to host memory after a stream synchronise. */

@@ -121,6 +121,23 @@ SIGNATURES = {
     "lcg_hip_csr_ax_ilu0": (None, [vp, vp, vp, C.c_int]),
     "clcg_hip_csr_ax_ilu0": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
     "lcg_hip_csr_ilu0_schedule_for_test": (C.c_int, [vp, C.c_int]),
+    "lcg_hip_dense_create": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, vp, C.c_int64, C.c_int, C.c_int]),
+    "lcg_hip_dense_create_rows": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, vp, C.c_int]),
+    "lcg_hip_dense_destroy": (C.c_int, [vp]),
+    "lcg_hip_dense_rows": (C.c_int, [vp]),
+    "lcg_hip_dense_cols": (C.c_int, [vp]),
+    "lcg_hip_dense_matvec": (C.c_int, [vp, vp, vp, C.c_int]),
+    "clcg_hip_dense_matvec": (C.c_int, [vp, vp, vp, C.c_int, C.c_int]),
+    "lcg_hip_dense_ata": (C.c_int, [vp, vp, vp]),
+    "lcg_hip_dense_ata_ax": (None, [vp, vp, vp, C.c_int]),
+    "lcg_hip_dense_ax": (None, [vp, vp, vp, C.c_int]),
+    "clcg_hip_dense_ax": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
+    "lcg_hip_dense_build_jacobi": (C.c_int, [vp, C.c_int, vp]),
+    "lcg_hip_dense_jacobi_mx": (None, [vp, vp, vp, C.c_int]),
+    "clcg_hip_dense_jacobi_mx": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
+    "lcg_hip_dense_last_kernel": (C.c_char_p, [vp]),
+    "lcg_hip_dense_kernel_name": (C.c_char_p, [C.c_int]),
+    "lcg_hip_dense_set_kernel": (C.c_int, [vp, C.c_int]),
     "lcg_hip_csr_ax": (None, [vp, vp, vp, C.c_int]),
     "lcg_hip_jacobi_mx": (None, [vp, vp, vp, C.c_int]),
     "clcg_hip_csr_ax": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),

@@ -277,6 +277,91 @@ class CsrMatrix:
             pass
 
 
+class DenseMatrix:
+    """An HBM-resident dense matrix (handle ``lcg_hip_dense_t``): K.x, K^T.x, K^T.K.x and the callbacks
+    'lcg_hip_dense_ata_ax', 'lcg_hip_dense_ax', 'clcg_hip_dense_ax', 'lcg_hip_dense_jacobi_mx', 'clcg_hip_dense_jacobi_mx'."""
+    KERNEL_AUTO, KERNEL_ROW, KERNEL_ROW_SPLIT, KERNEL_COL, KERNEL_ATA_TWO_PASS, KERNEL_ATA_ONE_PASS, KERNEL_ATA_SMALL = range(7)
+
+    def __init__(self, handle: int, m: int, n: int, is_complex: bool):
+        self.h = C.c_void_p(handle)
+        self.m, self.n, self.is_complex = m, n, is_complex
+
+    @classmethod
+    def from_array(cls, K):
+        """K: a 2-d numpy array (host; copied) or torch CUDA tensor (device; copied), row-major; the last axis may be a
+        view of a wider array (its stride is the leading dimension)."""
+        lib = L.load()
+        if isinstance(K, np.ndarray):
+            is_c = bool(np.iscomplexobj(K))
+            if (K.ndim != 2 or K.strides[1] != K.itemsize or K.dtype not in (np.float64, np.complex128) or K.strides[0] % K.itemsize
+                    or (K.shape[0] > 1 and K.strides[0] < K.shape[1] * K.itemsize)):
+                K = np.ascontiguousarray(K, np.complex128 if is_c else np.float64)
+            ld, ptr, mem = K.strides[0] // K.itemsize, K.ctypes.data, MEM_HOST
+        else:
+            is_c = K.is_complex()
+            if K.dim() != 2 or K.stride(1) != 1:
+                raise ValueError("a 2-d tensor with unit stride along its rows is needed")
+            ld, ptr, mem = K.stride(0), K.data_ptr(), (MEM_DEVICE if K.is_cuda else MEM_HOST)
+        m, n = K.shape
+        if ld < n:
+            if m != 1:          # a broadcast or overlapping-rows view: never read with a pitch it does not have
+                raise ValueError(f"rows {ld} entries apart hold {n} entries: make the array contiguous first")
+            ld = n              # one row: its stride means nothing
+        h = C.c_void_p()
+        _chk(lib.lcg_hip_dense_create(C.byref(h), m, n, ptr, ld, int(is_c), mem), "dense_create")
+        return cls(h.value, m, n, is_c)
+
+    @classmethod
+    def from_rows(cls, rows, is_complex=False):
+        """rows: a sequence of 1-d numpy arrays of one length (liblcg's lcg_float ** layout)."""
+        lib = L.load()
+        rows = [np.ascontiguousarray(r, np.complex128 if is_complex else np.float64) for r in rows]
+        ptrs = (C.c_void_p * len(rows))(*[r.ctypes.data for r in rows])
+        h = C.c_void_p()
+        _chk(lib.lcg_hip_dense_create_rows(C.byref(h), len(rows), len(rows[0]), ptrs, int(is_complex)), "dense_create_rows")
+        return cls(h.value, len(rows), len(rows[0]), is_complex)
+
+    def matvec(self, x, y, layout=0, conjugate=0):
+        lib = L.load()
+        if self.is_complex:
+            return _chk(lib.clcg_hip_dense_matvec(self.h, _ptr(x)[0], _ptr(y)[0], layout, conjugate), "dense_matvec")
+        return _chk(lib.lcg_hip_dense_matvec(self.h, _ptr(x)[0], _ptr(y)[0], layout), "dense_matvec")
+
+    def ata(self, x, y):
+        return _chk(L.load().lcg_hip_dense_ata(self.h, _ptr(x)[0], _ptr(y)[0]), "dense_ata")
+
+    def build_jacobi(self, normal=True, diag_out=None):
+        p = None if diag_out is None else _ptr(diag_out)[0]
+        return _chk(L.load().lcg_hip_dense_build_jacobi(self.h, int(normal), p), "dense_build_jacobi")
+
+    def set_kernel(self, variant: int):
+        return _chk(L.load().lcg_hip_dense_set_kernel(self.h, variant), "dense_set_kernel")
+
+    @property
+    def last_kernel(self) -> str:
+        return L.load().lcg_hip_dense_last_kernel(self.h).decode()
+
+    @staticmethod
+    def kernel_names():
+        lib, out, i = L.load(), [], 0
+        while True:
+            s = lib.lcg_hip_dense_kernel_name(i)
+            if s is None:
+                return out
+            out.append(s.decode()); i += 1
+
+    def destroy(self):
+        if self.h:
+            L.load().lcg_hip_dense_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
 @dataclass
 class SolveInfo:
     ret: int
@@ -298,7 +383,7 @@ def _cb(fn, proto):
 
 
 def _instance(instance):
-    if isinstance(instance, CsrMatrix):
+    if isinstance(instance, (CsrMatrix, DenseMatrix)):
         return instance.h
     return instance
 

@@ -1119,6 +1119,7 @@ int lcg_hip_comm_size(void) { return g_comm.nranks; }
 
 int lcg_hip_csr_distribute(lcg_hip_csr_t A, int64_t n_global, int mode)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || n_global <= 0) return LCG_HIP_E_ARG;
     TRY_C64(A, "lcg_hip_csr_distribute");
     if (mode < 0 || mode > 2) return LCG_HIP_E_ARG;
@@ -1141,6 +1142,7 @@ int lcg_hip_csr_distribute(lcg_hip_csr_t A, int64_t n_global, int mode)
 // entries of x this rank receives per A.x (doubles; complex counts twice): plan volume
 int64_t lcg_hip_csr_exchange_volume(lcg_hip_csr_t A)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || !A->distributed) return 0;
     if (A->dist_mode == 1 && A->halo) return static_cast<const HaloPlan *>(A->halo)->recv_total;
     if (A->dist_mode == 2 && A->direct) return static_cast<const Direct *>(A->direct)->recv_total;
@@ -1150,6 +1152,7 @@ int64_t lcg_hip_csr_exchange_volume(lcg_hip_csr_t A)
 // test hook: the [lo,hi) column range needed from each of `nranks` owners (after split_for_test)
 int lcg_hip_csr_need_ranges_for_test(lcg_hip_csr_t A, int nranks, int64_t *lohi)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || !A->distributed || !lohi) return LCG_HIP_E_ARG;
     std::vector<long long> v;
     int rc = need_ranges(A, nranks, v);
@@ -1162,6 +1165,7 @@ int lcg_hip_csr_need_ranges_for_test(lcg_hip_csr_t A, int nranks, int64_t *lohi)
 // fills the gather buffer itself through lcg_hip_csr_xfull()
 int lcg_hip_csr_split_for_test(lcg_hip_csr_t A, int64_t n_global, int nranks, int rank)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return LCG_HIP_E_ARG;
     TRY_C64(A, "lcg_hip_csr_split_for_test");
     return dist_split(A, n_global, nranks, rank);
@@ -1174,6 +1178,7 @@ int lcg_hip_csr_split_for_test(lcg_hip_csr_t A, int64_t n_global, int nranks, in
 // buffer (lcg_hip_csr_xfull), so the product is the true one and the kernel chain is the real one.
 int lcg_hip_csr_direct_selfloop_for_test(lcg_hip_csr_t A, int nranks, int rank)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || !A->distributed) return LCG_HIP_E_ARG;
     Ctx &c = ctx();
     direct_free(A);
@@ -1235,6 +1240,7 @@ int lcg_hip_csr_direct_selfloop_for_test(lcg_hip_csr_t A, int nranks, int rank)
 // hold remote columns out of whatever the gather buffer holds, and their addition to y).  Collective for part 1.
 int lcg_hip_csr_ax_part_for_probe(lcg_hip_csr_t A, const double *x, double *y, int part)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || !A->distributed || !x || !y) return LCG_HIP_E_ARG;
     Ctx &c = ctx();
     const int *done = nullptr;
@@ -1267,8 +1273,8 @@ int lcg_hip_csr_ax_part_for_probe(lcg_hip_csr_t A, const double *x, double *y, i
     }
     return LCG_HIP_E_ARG;
 }
-double *lcg_hip_csr_xfull(lcg_hip_csr_t A) { return A ? A->xfull : nullptr; }
-int64_t lcg_hip_csr_local_nnz(lcg_hip_csr_t A) { return A ? A->loc.nnz : 0; }
+double *lcg_hip_csr_xfull(lcg_hip_csr_t A) { NOT_DENSE(A, nullptr); return A ? A->xfull : nullptr; }
+int64_t lcg_hip_csr_local_nnz(lcg_hip_csr_t A) { NOT_DENSE(A, LCG_HIP_E_ARG); return A ? A->loc.nnz : 0; }
 
 int lcg_hip_allreduce_sum(double *dev_values, int count)
 {

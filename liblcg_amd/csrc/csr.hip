@@ -1659,6 +1659,7 @@ int lcg_hip_csr_create(lcg_hip_csr_t *out, int n_rows, int n_cols, int64_t nnz, 
 
 int lcg_hip_csr_destroy(lcg_hip_csr_t A)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return 0;
     ctx().forget_places();       // (driver.hpp: Placement remembers timings by the value array's address)
     ctx().released_bytes += (size_t)A->main.nnz * (A->is_complex ? 20 : 12);     // (the plans beside it not counted: the walk's "fresh allocator" rule needs the order of magnitude)
@@ -1669,14 +1670,16 @@ int lcg_hip_csr_destroy(lcg_hip_csr_t A)
     ic0_free(A);
     ilu0_free(A);
     c64_free(A);
+    A->kind = 0;
     delete A;
     return 0;
 }
 
-int lcg_hip_csr_rows(lcg_hip_csr_t A) { return A ? A->n_rows : 0; }
-int64_t lcg_hip_csr_nnz(lcg_hip_csr_t A) { return A ? A->main.nnz : 0; }
+int lcg_hip_csr_rows(lcg_hip_csr_t A) { NOT_DENSE(A, LCG_HIP_E_ARG); return A ? A->n_rows : 0; }
+int64_t lcg_hip_csr_nnz(lcg_hip_csr_t A) { NOT_DENSE(A, LCG_HIP_E_ARG); return A ? A->main.nnz : 0; }
 int lcg_hip_csr_arrays(lcg_hip_csr_t A, const int **rowptr, const int **col, const double **val)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return LCG_HIP_E_ARG;
     if (rowptr) *rowptr = A->main.rowptr;
     if (col) *col = A->main.col;
@@ -1685,6 +1688,7 @@ int lcg_hip_csr_arrays(lcg_hip_csr_t A, const int **rowptr, const int **col, con
 }
 int lcg_hip_csr_set_kernel(lcg_hip_csr_t A, int variant)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return LCG_HIP_E_ARG;
     TRY_C64(A, "lcg_hip_csr_set_kernel");
     A->variant = variant;
@@ -1706,6 +1710,7 @@ extern "C" {
 
 int lcg_hip_csr_set_packed(lcg_hip_csr_t A, int mode)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || mode < -1 || mode > 1) return LCG_HIP_E_ARG;
     TRY_C64(A, "lcg_hip_csr_set_packed");
     if (mode == 0) op_copies_free(A);
@@ -1724,6 +1729,7 @@ int lcg_hip_csr_set_packed(lcg_hip_csr_t A, int mode)
 
 int lcg_hip_csr_set_binned(lcg_hip_csr_t A, int mode)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || mode < -1 || mode > 1) return LCG_HIP_E_ARG;
     TRY_C64(A, "lcg_hip_csr_set_binned");
     if (mode == 0) op_copies_free(A);
@@ -1738,6 +1744,7 @@ int lcg_hip_csr_set_binned(lcg_hip_csr_t A, int mode)
 
 int lcg_hip_csr_set_tiled(lcg_hip_csr_t A, int mode)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || mode < -1 || mode > 1) return LCG_HIP_E_ARG;
     TRY_C64(A, "lcg_hip_csr_set_tiled");
     if (mode == 0) op_copies_free(A);
@@ -1752,6 +1759,7 @@ int lcg_hip_csr_set_tiled(lcg_hip_csr_t A, int mode)
 
 int lcg_hip_csr_set_ranges(lcg_hip_csr_t A, int mode)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || mode < -1 || mode > 1) return LCG_HIP_E_ARG;
     TRY_C64(A, "lcg_hip_csr_set_ranges");
     if (mode == 0) op_copies_free(A);
@@ -1762,6 +1770,7 @@ int lcg_hip_csr_set_ranges(lcg_hip_csr_t A, int mode)
 
 int lcg_hip_csr_ranges(lcg_hip_csr_t A, int cap, int *first_row)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return 0;
     const CsrPart &P = A->distributed ? A->loc : A->main;
     const RangePlan *R = static_cast<const RangePlan *>(P.rg_plan);
@@ -1772,24 +1781,28 @@ int lcg_hip_csr_ranges(lcg_hip_csr_t A, int cap, int *first_row)
 
 const char *lcg_hip_csr_tiled_status(lcg_hip_csr_t A)
 {
+    NOT_DENSE(A, "");
     if (!A) return "";
     return A->distributed ? A->loc.tl_why : A->main.tl_why;
 }
 
 const char *lcg_hip_csr_last_kernel(lcg_hip_csr_t A)
 {
+    NOT_DENSE(A, "");
     if (!A) return "";
     return A->distributed ? A->loc.last_kernel : A->main.last_kernel;
 }
 
 const char *lcg_hip_csr_binned_status(lcg_hip_csr_t A)
 {
+    NOT_DENSE(A, "");
     if (!A) return "";
     return A->distributed ? A->loc.bn_why : A->main.bn_why;
 }
 
 int64_t lcg_hip_csr_packed_runs(lcg_hip_csr_t A, int64_t *blocks_out)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return 0;
     const CsrPart &P = A->distributed ? A->loc : A->main;
     if (blocks_out) *blocks_out = (P.n_rows + P.pk_R - 1) / P.pk_R;
@@ -1824,6 +1837,7 @@ static int64_t part_traffic_model(const CsrPart &P)
 
 int64_t lcg_hip_csr_packed_templates(lcg_hip_csr_t A)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return 0;
     const CsrPart &P = A->distributed ? A->loc : A->main;
     return P.pk_state > 0 ? P.pk_tpls : 0;
@@ -1831,12 +1845,14 @@ int64_t lcg_hip_csr_packed_templates(lcg_hip_csr_t A)
 
 int64_t lcg_hip_csr_last_traffic_model(lcg_hip_csr_t A)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || A->is_complex || A->c64) return 0;
     return part_traffic_model(A->distributed ? A->loc : A->main);
 }
 
 int lcg_hip_csr_plan_info(lcg_hip_csr_t A, double *build_ms, int64_t *extra_bytes)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return LCG_HIP_E_ARG;
     const CsrPart &P = A->distributed ? A->loc : A->main;
     double ms = P.plan_ms;
@@ -1861,6 +1877,7 @@ static inline void park(int rc) { if (rc && !ctx().ax_rc) ctx().ax_rc = rc; }
 
 void lcg_hip_csr_ax(void *instance, const double *x, double *y, const int n)
 {
+    NOT_DENSE_CB(instance);
     lcg_hip_csr *A = static_cast<lcg_hip_csr *>(instance);
     (void)n;
     park(lcg_hip_spmv(A, x, y));
@@ -1868,17 +1885,20 @@ void lcg_hip_csr_ax(void *instance, const double *x, double *y, const int n)
 
 void clcg_hip_csr_ax(void *instance, const double *x, double *y, const int n, int layout, int conjugate)
 {
+    NOT_DENSE_CB(instance);
     (void)n;
     park(lcg_hip_spmv_op(static_cast<lcg_hip_csr *>(instance), x, y, layout, conjugate));
 }
 
 void lcg_hip_jacobi_mx(void *instance, const double *x, double *z, const int n)
 {
+    NOT_DENSE_CB(instance);
     park(jacobi_launch(static_cast<lcg_hip_csr *>(instance), x, z, n, ctx().stream));
 }
 
 int lcg_hip_spmv_op(lcg_hip_csr_t A, const double *x, double *y, int layout, int conjugate)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || !x || !y) return LCG_HIP_E_ARG;
     TRY_C64(A, "lcg_hip_spmv_op");
     if (!layout && (!conjugate || !A->is_complex)) return lcg_hip_spmv(A, x, y);
@@ -1894,6 +1914,7 @@ int lcg_hip_spmv_op(lcg_hip_csr_t A, const double *x, double *y, int layout, int
 
 int lcg_hip_spmv(lcg_hip_csr_t A, const double *x, double *y)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || !x || !y) return LCG_HIP_E_ARG;
     TRY_C64(A, "lcg_hip_spmv");
     Ctx &c = ctx();

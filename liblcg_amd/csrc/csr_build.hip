@@ -616,6 +616,7 @@ int lcg_hip_csr_from_coo(lcg_hip_csr_t *out, int n, int64_t nnz, const int *row,
 
 int lcg_hip_csr_build_jacobi(lcg_hip_csr_t A, double *diag_out)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return LCG_HIP_E_ARG;
     if (A->c64) return c64_build_jacobi(A, diag_out);
     Ctx &c = ctx();

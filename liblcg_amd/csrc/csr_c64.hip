@@ -337,6 +337,7 @@ int lcg_hip_csr_create_c64(lcg_hip_csr_t *out, int n_rows, int n_cols, int64_t n
 
 int lcg_hip_spmv_c64(lcg_hip_csr_t A, const float *x, float *y, int layout, int conjugate)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     int rc = ensure_init(); if (rc) return rc;
     if (!A || !x || !y) return LCG_HIP_E_ARG;
     if (!A->c64) return c64_error("lcg_hip_spmv_c64: the handle is not a complex64 matrix (lcg_hip_csr_create_c64)");
@@ -347,6 +348,7 @@ int lcg_hip_spmv_c64(lcg_hip_csr_t A, const float *x, float *y, int layout, int 
 // The callback types return void: a failure is parked in Ctx::ax_rc and ends the solve (driver.hpp: timed_ax / checked_mx).
 void clcg_hip_csr_ax_c64(void *instance, const float *x, float *prod_Ax, const int n_size, int layout, int conjugate)
 {
+    NOT_DENSE_CB(instance);
     (void)n_size;
     const int rc = lcg_hip_spmv_c64(static_cast<lcg_hip_csr *>(instance), x, prod_Ax, layout, conjugate);
     if (rc && !ctx().ax_rc) ctx().ax_rc = rc;
@@ -354,6 +356,7 @@ void clcg_hip_csr_ax_c64(void *instance, const float *x, float *prod_Ax, const i
 
 void clcg_hip_jacobi_mx_c64(void *instance, const float *x, float *prod_Mx, const int n_size, int layout, int conjugate)
 {
+    NOT_DENSE_CB(instance);
     (void)layout; (void)conjugate;
     const int rc = c64_jacobi(static_cast<lcg_hip_csr *>(instance), x, prod_Mx, n_size);
     if (rc && !ctx().ax_rc) ctx().ax_rc = rc;

@@ -357,6 +357,7 @@ extern "C" {
 
 int lcg_hip_csr_build_ic0(lcg_hip_csr_t A)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return LCG_HIP_E_ARG;
     TRY_C64(A, "lcg_hip_csr_build_ic0");
     return ic0_build_entry(A);
@@ -364,6 +365,7 @@ int lcg_hip_csr_build_ic0(lcg_hip_csr_t A)
 
 int lcg_hip_csr_build_ic0_c64(lcg_hip_csr_t A)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     int rc = ensure_init(); if (rc) return rc;
     if (!A) return LCG_HIP_E_ARG;
     if (!A->c64) return arg_error("lcg_hip_csr_build_ic0_c64: the handle is not a complex64 matrix (lcg_hip_csr_create_c64; "
@@ -374,6 +376,7 @@ int lcg_hip_csr_build_ic0_c64(lcg_hip_csr_t A)
 int lcg_hip_csr_ic0_info(lcg_hip_csr_t A, int *levels_lower, int *levels_upper, int *launches_per_apply, int *zero_pivot,
                          double *build_ms, int64_t *bytes)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || !A->ic0) return LCG_HIP_E_ARG;
     const Ic0 *F = ic0_of(A);
     if (levels_lower) *levels_lower = F->fw.levels;
@@ -393,6 +396,7 @@ int lcg_hip_csr_ic0_info(lcg_hip_csr_t A, int *levels_lower, int *levels_upper, 
 
 int lcg_hip_csr_ic0_set_sweeps(lcg_hip_csr_t A, int sweeps)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return arg_error("lcg_hip_csr_ic0_set_sweeps: the handle is NULL");
     Ic0 *F = ic0_of(A);
     if (!F || !F->ok) return arg_error("lcg_hip_csr_ic0_set_sweeps: the handle has no factor (lcg_hip_csr_build_ic0, lcg_hip_csr_build_ic0_c64)");
@@ -413,6 +417,7 @@ int lcg_hip_csr_ic0_set_sweeps(lcg_hip_csr_t A, int sweeps)
 
 int lcg_hip_csr_ic0_get_sweeps(lcg_hip_csr_t A, int *sweeps)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return arg_error("lcg_hip_csr_ic0_get_sweeps: the handle is NULL");
     const Ic0 *F = ic0_of(A);
     if (!F || !F->ok) return arg_error("lcg_hip_csr_ic0_get_sweeps: the handle has no factor (lcg_hip_csr_build_ic0, lcg_hip_csr_build_ic0_c64)");
@@ -423,6 +428,7 @@ int lcg_hip_csr_ic0_get_sweeps(lcg_hip_csr_t A, int *sweeps)
 
 int lcg_hip_csr_ic0_factor(lcg_hip_csr_t A, const int **rowptr, const int **col, const double **val)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || !A->ic0) return LCG_HIP_E_ARG;
     const Ic0 *F = ic0_of(A);
     if (rowptr) *rowptr = F->L.rowptr;
@@ -433,12 +439,14 @@ int lcg_hip_csr_ic0_factor(lcg_hip_csr_t A, const int **rowptr, const int **col,
 
 int lcg_hip_ic0_solve(lcg_hip_csr_t A, int which, const double *x, double *y)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return LCG_HIP_E_ARG;
     return ic0_call(A, A->is_complex, false, which, x, y, -1);
 }
 
 int lcg_hip_ic0_solve_c64(lcg_hip_csr_t A, int which, const float *x, float *y)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     int rc = ensure_init(); if (rc) return rc;
     if (!A) return LCG_HIP_E_ARG;
     return ic0_call(A, false, true, which, reinterpret_cast<const double *>(x), reinterpret_cast<double *>(y), -1);
@@ -446,6 +454,7 @@ int lcg_hip_ic0_solve_c64(lcg_hip_csr_t A, int which, const float *x, float *y)
 
 int lcg_hip_csr_ic0_schedule_for_test(lcg_hip_csr_t A, int max_merged_rows)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || !A->ic0 || max_merged_rows < -1 || max_merged_rows > IC_WG) return LCG_HIP_E_ARG;
     Ic0 *F = ic0_of(A);
     F->max_merged = max_merged_rows < 0 ? IC_WG : max_merged_rows;
@@ -457,12 +466,14 @@ int lcg_hip_csr_ic0_schedule_for_test(lcg_hip_csr_t A, int max_merged_rows)
 // The callback types return void (lcg.h:37-38, clcg.h:40-41): a failure is parked in Ctx::ax_rc (driver.hpp: checked_mx).
 void lcg_hip_ic0_mx(void *instance, const double *x, double *prod_Mx, const int n_size)
 {
+    NOT_DENSE_CB(instance);
     const int rc = ic0_call(static_cast<lcg_hip_csr *>(instance), false, false, 2, x, prod_Mx, n_size);
     if (rc && !ctx().ax_rc) ctx().ax_rc = rc;
 }
 
 void clcg_hip_ic0_mx(void *instance, const double *x, double *prod_Mx, const int n_size, int layout, int conjugate)
 {
+    NOT_DENSE_CB(instance);
     (void)layout;       // M = L.L^T is complex-symmetric: M^T = M
     const int rc = conjugate ? arg_error("IC(0): conjugate = 1 is not offered (M^H != M)")
                              : ic0_call(static_cast<lcg_hip_csr *>(instance), true, false, 2, x, prod_Mx, n_size);
@@ -471,6 +482,7 @@ void clcg_hip_ic0_mx(void *instance, const double *x, double *prod_Mx, const int
 
 void clcg_hip_ic0_mx_c64(void *instance, const float *x, float *prod_Mx, const int n_size, int layout, int conjugate)
 {
+    NOT_DENSE_CB(instance);
     (void)layout;       // M = L.L^T is complex-symmetric: M^T = M
     const int rc = conjugate ? arg_error("IC(0): conjugate = 1 is not offered (M^H != M)")
                              : ic0_call(static_cast<lcg_hip_csr *>(instance), false, true, 2, reinterpret_cast<const double *>(x),

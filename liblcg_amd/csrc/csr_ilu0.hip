@@ -347,6 +347,7 @@ extern "C" {
 
 int lcg_hip_csr_build_ilu0(lcg_hip_csr_t A)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return LCG_HIP_E_ARG;
     TRY_C64(A, "lcg_hip_csr_build_ilu0");
     if (A->distributed) return arg_error("ILU(0): not available on a sharded matrix");
@@ -370,6 +371,7 @@ int lcg_hip_csr_build_ilu0(lcg_hip_csr_t A)
 int lcg_hip_csr_ilu0_info(lcg_hip_csr_t A, int *levels_L, int *levels_U, int *launches_per_apply, int *zero_pivot, double *build_ms,
                           int64_t *bytes)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || !A->ilu0) return LCG_HIP_E_ARG;
     const Ilu0 *F = ilu0_of(A);
     if (levels_L) *levels_L = F->fw.levels;
@@ -391,6 +393,7 @@ int lcg_hip_csr_ilu0_info(lcg_hip_csr_t A, int *levels_L, int *levels_U, int *la
 
 int lcg_hip_csr_ilu0_set_sweeps(lcg_hip_csr_t A, int sweeps)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return arg_error("lcg_hip_csr_ilu0_set_sweeps: the handle is NULL");
     Ilu0 *F = ilu0_of(A);
     if (!F || !F->ok) return arg_error("lcg_hip_csr_ilu0_set_sweeps: the handle has no factor (lcg_hip_csr_build_ilu0)");
@@ -411,6 +414,7 @@ int lcg_hip_csr_ilu0_set_sweeps(lcg_hip_csr_t A, int sweeps)
 
 int lcg_hip_csr_ilu0_get_sweeps(lcg_hip_csr_t A, int *sweeps)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return arg_error("lcg_hip_csr_ilu0_get_sweeps: the handle is NULL");
     const Ilu0 *F = ilu0_of(A);
     if (!F || !F->ok) return arg_error("lcg_hip_csr_ilu0_get_sweeps: the handle has no factor (lcg_hip_csr_build_ilu0)");
@@ -421,6 +425,7 @@ int lcg_hip_csr_ilu0_get_sweeps(lcg_hip_csr_t A, int *sweeps)
 
 int lcg_hip_csr_ilu0_factor(lcg_hip_csr_t A, int which, const int **rowptr, const int **col, const double **val)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || !A->ilu0 || which < 0 || which > 1) return LCG_HIP_E_ARG;
     const CsrPart &T = which ? ilu0_of(A)->U : ilu0_of(A)->L;
     if (!T.rowptr) return LCG_HIP_E_ARG;
@@ -432,12 +437,14 @@ int lcg_hip_csr_ilu0_factor(lcg_hip_csr_t A, int which, const int **rowptr, cons
 
 int lcg_hip_ilu0_solve(lcg_hip_csr_t A, int which, const double *x, double *y)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return LCG_HIP_E_ARG;
     return ilu0_call(A, A->is_complex, which, x, y, -1);
 }
 
 int lcg_hip_csr_ilu0_schedule_for_test(lcg_hip_csr_t A, int max_merged_rows)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || !A->ilu0 || max_merged_rows < -1 || max_merged_rows > IC_WG) return LCG_HIP_E_ARG;
     Ilu0 *F = ilu0_of(A);
     F->max_merged = max_merged_rows < 0 ? IC_WG : max_merged_rows;
@@ -451,22 +458,26 @@ static void ilu_park(int rc) { if (rc && !ctx().ax_rc) ctx().ax_rc = rc; }
 
 void lcg_hip_ilu0_mx(void *instance, const double *x, double *prod_Mx, const int n_size)
 {
+    NOT_DENSE_CB(instance);
     ilu_park(ilu0_call(static_cast<lcg_hip_csr *>(instance), false, 2, x, prod_Mx, n_size));
 }
 
 void clcg_hip_ilu0_mx(void *instance, const double *x, double *prod_Mx, const int n_size, int layout, int conjugate)
 {
+    NOT_DENSE_CB(instance);
     ilu_park(layout || conjugate ? arg_error("ILU(0): layout = 1 and conjugate = 1 are not offered (M = L.U is not symmetric)")
                                  : ilu0_call(static_cast<lcg_hip_csr *>(instance), true, 2, x, prod_Mx, n_size));
 }
 
 void lcg_hip_csr_ax_ilu0(void *instance, const double *x, double *prod_Ax, const int n_size)
 {
+    NOT_DENSE_CB(instance);
     ilu_park(ilu0_ax(static_cast<lcg_hip_csr *>(instance), false, x, prod_Ax, n_size));
 }
 
 void clcg_hip_csr_ax_ilu0(void *instance, const double *x, double *prod_Ax, const int n_size, int layout, int conjugate)
 {
+    NOT_DENSE_CB(instance);
     ilu_park(layout || conjugate ? arg_error("ILU(0): the right-preconditioned product offers (layout, conjugate) = (0, 0) only")
                                  : ilu0_ax(static_cast<lcg_hip_csr *>(instance), true, x, prod_Ax, n_size));
 }

@@ -285,7 +285,25 @@ struct CsrPart {
 
 } // namespace lcgh
 
+// Both kinds of handle begin with a word that says which kind they are (cleared when the handle is destroyed): an entry looks at
+// that word and at nothing else of a handle of the other kind.
+namespace lcgh {
+constexpr uint64_t KIND_CSR = 0x3152534347434C4Cull, KIND_DENSE = 0x534E454447434C4Cull;
+inline bool dense_handle(const void *h) { return h && *static_cast<const uint64_t *>(h) == KIND_DENSE; }
+// a CSR entry handed a dense handle: LCG_HIP_E_ARG with the entry's name; `park` also ends a running solve (void callbacks)
+inline int refuse_dense(const char *entry, bool park = false)
+{
+    ctx().err = std::string(entry) + ": the handle is a dense matrix (lcg_hip_dense_t); this entry takes a CSR matrix";
+    if (park && !ctx().ax_rc) ctx().ax_rc = LCG_HIP_E_ARG;
+    return LCG_HIP_E_ARG;
+}
+} // namespace lcgh
+// first line of every exported entry that takes a lcg_hip_csr_t; the arguments after the handle are what the entry returns then
+#define NOT_DENSE(h, ...) do { if (::lcgh::dense_handle(h)) { ::lcgh::refuse_dense(__func__); return __VA_ARGS__; } } while (0)
+#define NOT_DENSE_CB(h) do { if (::lcgh::dense_handle(h)) { ::lcgh::refuse_dense(__func__, true); return; } } while (0)
+
 struct lcg_hip_csr {
+    uint64_t kind = lcgh::KIND_CSR;
     int n_rows = 0;         // local rows
     int n_cols = 0;         // columns addressed by `main` (global when sharded)
     bool is_complex = false;

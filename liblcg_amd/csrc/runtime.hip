@@ -369,6 +369,7 @@ int lcg_hip_dot(int n, const double *a, const double *b, double *result)
 }
 int lcg_hip_spmv_dot(lcg_hip_csr_t A, const double *x, double *y, const double *u, double *result2)
 {
+    NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A || !x || !y || !u || A->is_complex) return LCG_HIP_E_ARG;
     TRY_C64(A, "lcg_hip_spmv_dot");
     int rc = ensure_init(); if (rc) return rc;

@@ -811,6 +811,7 @@ extern "C" int clcg_hip_solver_preconditioned(clcg_hip_axfunc_ptr Afp, clcg_hip_
 // clcg_vecDvecZ_element_wise as used by sample10.cu:117
 extern "C" void clcg_hip_jacobi_mx(void *instance, const double *x, double *z, const int n, int layout, int conjugate)
 {
+    NOT_DENSE_CB(instance);
     (void)layout; (void)conjugate;
     const int rc = jacobi_launch(static_cast<lcg_hip_csr *>(instance), x, z, n, ctx().stream);
     if (rc && !ctx().ax_rc) ctx().ax_rc = rc;          // void callback: parked for the loop (driver.hpp: checked_mx)
