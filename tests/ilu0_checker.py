@@ -337,3 +337,216 @@ def rhs(As, seed=3):
     """b = A x* with x* uniform in [1, 2]."""
     xs = np.random.default_rng(seed).uniform(1.0, 2.0, As.shape[0])
     return As @ xs, xs
+
+
+def convdiff3d(k, pe):
+    """3-D convection-diffusion with first-order upwinding on a k^3 grid, 7 points: convdiff's two directions and a third,
+    T3 = tridiag(-1 - pe/4, 2 + pe/4, -1), slowest.  Non-symmetric values on a symmetric pattern, an M-matrix; the forward level
+    of grid point (z, y, x) is x + y + z."""
+    T1 = sp.diags([-1.0 - pe, 2.0 + pe, -1.0], [-1, 0, 1], shape=(k, k))
+    T2 = sp.diags([-1.0 - pe / 2, 2.0 + pe / 2, -1.0], [-1, 0, 1], shape=(k, k))
+    T3 = sp.diags([-1.0 - pe / 4, 2.0 + pe / 4, -1.0], [-1, 0, 1], shape=(k, k))
+    I = sp.identity(k)
+    return _arrays(sp.kron(I, sp.kron(I, T1)) + sp.kron(I, sp.kron(T2, I)) + sp.kron(T3, sp.kron(I, I)))
+
+
+def mirror(n, lower):
+    """Strictly lower rows {j: value} turned about the anti-diagonal: entry (i, j), j < i, goes to (n-1-i, n-1-j), strictly
+    upper.  A forward level of `lower` becomes the same backward level of the result."""
+    upper = [{} for _ in range(n)]
+    for i in range(n):
+        for j, x in lower[i].items():
+            upper[n - 1 - i][n - 1 - j] = x
+    return upper
+
+
+def dominant_diagonal(rng, n, lower, upper, cplx):
+    """ic0_checker.dominant_diagonal for two independent triangles: 1 + U(0, 1) + every off-diagonal magnitude of the entry's
+    row and of its column (complex: plus i U(-0.5, 0.5)).  Strictly dominant by rows and by columns: every ILU(0) pivot usable."""
+    s = np.zeros(n)
+    for part in (lower, upper):
+        for i in range(n):
+            for j, x in part[i].items():
+                s[i] += abs(x); s[j] += abs(x)
+    d = 1.0 + rng.uniform(0.0, 1.0, n) + s
+    return d + 1j * rng.uniform(-0.5, 0.5, n) if cplx else d
+
+
+def assemble(n, lower, upper, diag):
+    """CSR (rows sorted) of strictly lower rows, strictly upper rows and a diagonal; nothing is mirrored."""
+    rows = [{**lower[i], **upper[i], i: diag[i]} for i in range(n)]
+    rp = np.zeros(n + 1, np.int32)
+    rp[1:] = np.cumsum([len(r) for r in rows])
+    cols = [sorted(r) for r in rows]
+    ci = np.fromiter((c for cs in cols for c in cs), np.int32, int(rp[-1]))
+    v = np.array([rows[i][c] for i in range(n) for c in cols[i]], np.complex128 if np.iscomplexobj(diag) else np.float64)
+    return rp, ci, v
+
+
+def layered_nonsym_parts(widths_L, widths_U, seed, cplx=False):
+    """(lower, upper, diag, starts_L, starts_U): the strictly lower pattern is ic0_checker.layered_parts(widths_L), so L's forward
+    level t is rows starts_L[t] .. starts_L[t+1]-1; the strictly upper pattern is a second, independent layered_parts(widths_U)
+    turned about the anti-diagonal (`mirror`), so U's backward level t is rows n-starts_U[t+1] .. n-starts_U[t]-1.  Every value
+    is a draw of its own; the diagonal is strictly dominant."""
+    assert sum(widths_L) == sum(widths_U)
+    lower, _, stL = IC.layered_parts(widths_L, seed, cplx)
+    low2, _, stU = IC.layered_parts(widths_U, seed + 7919, cplx)
+    n = int(stL[-1])
+    upper = mirror(n, low2)
+    diag = dominant_diagonal(np.random.default_rng(seed + 104729), n, lower, upper, cplx)
+    return lower, upper, diag, stL, stU
+
+
+def layered_nonsym(widths_L, widths_U, seed, cplx=False):
+    """(rowptr, col, val), rows sorted, of layered_nonsym_parts: forward levels of exactly widths_L rows, backward levels of
+    exactly widths_U rows (in backward level order), non-symmetric pattern and values."""
+    lower, upper, diag, _, _ = layered_nonsym_parts(widths_L, widths_U, seed, cplx)
+    return assemble(len(diag), lower, upper, diag)
+
+
+def _strict_lower(rp, ci, v):
+    n = len(rp) - 1
+    return [{int(ci[p]): v[p] for p in range(rp[i], rp[i + 1]) if ci[p] < i} for i in range(n)]
+
+
+def random_nonsym(n, seed):
+    """ic0_checker.random_spd's strictly lower pattern and values; the strictly upper part is a second, independent draw of it
+    turned about the anti-diagonal: irregular level sets in both triangles, no symmetry of pattern or values; strictly dominant."""
+    lower = _strict_lower(*IC.random_spd(n, seed))
+    upper = mirror(n, _strict_lower(*IC.random_spd(n, seed + 7919)))
+    diag = dominant_diagonal(np.random.default_rng(seed + 104729), n, lower, upper, False)
+    return assemble(n, lower, upper, diag)
+
+
+# the sweep kernel's staging window (DESIGN 11: k_ic_sweep): SWEEP_ROWS consecutive rows per workgroup; their slice of the
+# triangle, counted from the 4-entry unit that holds its first entry, is staged when it is at most SWEEP_WINDOW entries long
+SWEEP_ROWS, SWEEP_WINDOW = 256, 2048
+# entries of L / of U (diagonals included) in each 256-row workgroup of window_edges, and its short last workgroup's rows
+WINDOW_L = (0, 2048, 2049, 2048, 2047, 301)
+WINDOW_U = (2048, 2049, 2048, 2047, 1025, 100)
+WINDOW_TAIL = 100
+
+
+def sweep_windows(n, rowptr):
+    """Per workgroup of a sweep over the triangle with this rowptr: (own entries, cnt, rowptr[row0] & 3), with
+    cnt = rowptr[row0 + nrows] - (rowptr[row0] & ~3), the length the kernel compares with its window."""
+    rowptr = np.asarray(rowptr)
+    out = []
+    for row0 in range(0, n, SWEEP_ROWS):
+        s, e = int(rowptr[row0]), int(rowptr[min(row0 + SWEEP_ROWS, n)])
+        out.append((e - s, e - (s & ~3), s & 3))
+    return out
+
+
+def window_cases(n, rowptr):
+    """The window-edge situations a triangle's sweep meets, by name."""
+    wins = sweep_windows(n, rowptr)
+    found = set()
+    for own, cnt, off in wins:
+        if cnt == SWEEP_WINDOW and off == 0:
+            found.add("full_aligned")               # cnt = 2048, rowptr[row0] & 3 = 0: the largest staged slice
+        if cnt == SWEEP_WINDOW and off != 0:
+            found.add("full_by_offset")             # cnt = 2048 of which the first `off` entries are the neighbour's
+        if own == cnt == SWEEP_WINDOW + 1:
+            found.add("over_by_one")                # cnt = 2049 of its own: global memory
+        if own <= SWEEP_WINDOW < cnt:
+            found.add("over_by_offset")             # at most 2048 of its own, over only through rowptr[row0] & 3 != 0
+        if own == 0:
+            found.add("all_rows_empty")
+    own, cnt, off = wins[-1]
+    if n % SWEEP_ROWS and cnt <= SWEEP_WINDOW and int(rowptr[n]) % 4:
+        found.add("last_unit_in_slack")             # staged, and its last 16-byte unit of col ends past nnz
+    return found
+
+
+WINDOW_SET = {"full_aligned", "over_by_one", "over_by_offset", "last_unit_in_slack"}       # both triangles; L: + "all_rows_empty"
+
+
+def window_edges(seed, cplx=False):
+    """A matrix of 5 x 256 + WINDOW_TAIL rows whose ILU(0) triangles hold WINDOW_L / WINDOW_U entries in the sweep kernel's
+    successive workgroups, which puts them on both sides of its window edge (window_cases).  Every workgroup is a layer: a row's
+    strictly lower columns are drawn from the layers before it, its strictly upper ones from the layers after it, so L and U have
+    at most 6 levels each.  A workgroup's entries are spread evenly over its rows, the first rows taking the remainder."""
+    rng = np.random.default_rng(seed)
+    n = SWEEP_ROWS * (len(WINDOW_L) - 1) + WINDOW_TAIL
+    lower, upper = [{} for _ in range(n)], [{} for _ in range(n)]
+    for w in range(len(WINDOW_L)):
+        a, b = w * SWEEP_ROWS, min((w + 1) * SWEEP_ROWS, n)
+        for part, total, lo, hi in ((lower, WINDOW_L[w], 0, a), (upper, WINDOW_U[w] - (b - a), b, n)):
+            q, r = divmod(total, b - a)
+            for i in range(a, b):
+                k = q + (i - a < r)
+                if k:
+                    for j in rng.choice(hi - lo, size=k, replace=False) + lo:
+                        part[i][int(j)] = IC._offdiag(rng, cplx)
+    return assemble(n, lower, upper, dominant_diagonal(rng, n, lower, upper, cplx))
+
+
+# ------------------------------------------------------------------------------------------ scheduled systems, pivot failures
+# rows per forward level of L, rows per backward level of U (in backward level order): wide levels (> 1024 rows, a launch each)
+# next to each other, after and before runs of narrow ones, at the widths 1023 / 1024 / 1025 around the rule's edge
+LAYERS_L = [1024, 1025, 1, 1023, 3000, 1024, 5, 2048]
+LAYERS_U = [2048, 7, 1024, 1500, 1, 1025, 1023, 2522]
+PIVOT_CASES = ["two_in_wide_level", "larger_row_first_in_time", "narrow_run", "empty_row", "nan_upper", "complex_zero"]
+
+
+def _zero_pivot(rp, ci, v, r):
+    """Makes w(r,r) an exact zero whatever the rounding: A(r,r) = 0 and A(k,r) = 0 (still stored) for every k < r of row r, so
+    the pivot is 0 - sum L(r,k).0."""
+    for p in range(rp[r], rp[r + 1]):
+        k = int(ci[p])
+        if k == r:
+            v[p] = 0.0
+        elif k < r:
+            q = rp[k] + np.flatnonzero(ci[rp[k]:rp[k + 1]] == r)
+            v[q] = 0.0
+
+
+def pivot_case(case, seed):
+    """((rowptr, col, val) whose ILU(0) fails, the smallest failing row, (rowptr, col, val) repaired).  Ordinary bad matrices:
+    every one has a defined error return."""
+    if case == "larger_row_first_in_time":
+        # convdiff3d(40, 2): row 1600 = (1, 0, 0) is on forward level 1, in the narrow run of levels 0-45 (one launch); row 439 =
+        # (0, 10, 39) is on level 49, the fourth wide level after it: four launches later
+        rp, ci, good = convdiff3d(40, 2)
+        bad = good.copy()
+        for r in (1600, 439):
+            _zero_pivot(rp, ci, bad, r)
+        return (rp, ci, bad), 439, (rp, ci, good)
+    cplx = case == "complex_zero"
+    lower, upper, diag, st, _ = layered_nonsym_parts(LAYERS_L, LAYERS_U, seed, cplx)
+    n = len(diag)
+    if case == "nan_upper":                         # U(k,i) = NaN, k in row i of L: the merge of row k carries it into w(i,i)
+        want = int(st[4]) + 7
+        k = min(lower[want])
+        upper[k][want] = 0.5
+        rp, ci, good = assemble(n, lower, upper, diag)
+        bad = good.copy()
+        bad[rp[k] + np.flatnonzero(ci[rp[k]:rp[k + 1]] == want)] = np.nan
+        return (rp, ci, bad), want, (rp, ci, good)
+    if case == "complex_zero":                      # L(i,j) = 2 / 4, w(i,i) = 1 - 0.5 * 2: (0, 0) exactly; row j is on level 0
+        want, j = int(st[1]) + 3, int(st[0]) + 5
+        lower[want] = {j: 2.0 + 0j}
+        upper[j][want] = 2.0 + 0j
+        diag[j] = 4.0 + 0j
+        good = assemble(n, lower, upper, diag)
+        diag[want] = 1.0 + 0j
+        return assemble(n, lower, upper, diag), want, good
+    rp, ci, good = assemble(n, lower, upper, diag)
+    bad = good.copy()
+    if case == "two_in_wide_level":                 # level 4: 3000 rows, 12 workgroups of 256; the first and the last
+        want = int(st[4]) + 100
+        _zero_pivot(rp, ci, bad, int(st[4]) + 2950)
+        _zero_pivot(rp, ci, bad, want)
+    elif case == "narrow_run":                      # level 3 (1023 rows), in the narrow run of levels 2-3
+        want = int(st[3]) + 500
+        _zero_pivot(rp, ci, bad, want)
+    elif case == "empty_row":                       # nothing stored: its diagonal is the explicit zero the build puts there
+        want = int(st[5]) + 10
+        keep = np.ones(len(ci), bool)
+        keep[rp[want]:rp[want + 1]] = False
+        rpb = np.concatenate([rp[:want + 1], rp[want + 1:] - (rp[want + 1] - rp[want])]).astype(np.int32)
+        return (rpb, ci[keep], good[keep]), want, (rp, ci, good)
+    else:
+        raise KeyError(case)
+    return (rp, ci, bad), want, (rp, ci, good)

@@ -120,3 +120,139 @@ def test_bicgstab_counts(k, pe):
         got.append(K.right_bicgstab(As, K.SweepApply(n, L, U, s).solve, b, 1e-10)[1])
     assert got == COUNTS[(k, pe)]
     assert 2 * got[1] <= got[0] and got[4] <= got[0]         # what the GPU test asks of the device runs
+
+
+# ------------------------------------------------------------------------------------------ the scheduled systems' generators
+WG = 1024                                                    # production max_merged
+
+
+def scheduled(name, off=0):
+    """The systems of tests/test_gpu_ilu0_schedules.py by name: (rowptr, col, val)."""
+    if name == "convdiff3d40":
+        return K.convdiff3d(40, 2)
+    if name == "convdiff3d40_dropped":
+        return K.drop_upper(*K.convdiff3d(40, 2))
+    if name in ("layered_nonsym", "layered_nonsym_c"):
+        return IC.shuffle_split(*K.layered_nonsym(K.LAYERS_L, K.LAYERS_U, 41 + off, name.endswith("_c")), 42 + off)
+    if name == "fuzz20k_nonsym":
+        return K.random_nonsym(20000, 902 + off)
+    raise KeyError(name)
+
+
+SCHEDULED = ["convdiff3d40", "convdiff3d40_dropped", "layered_nonsym", "layered_nonsym_c", "fuzz20k_nonsym"]
+
+
+def test_convdiff3d_is_the_stencil():
+    k, pe = 5, 2.0
+    rp, ci, v = K.convdiff3d(k, pe)
+    A = IC.to_sparse(k ** 3, rp, ci, v).toarray()
+    want = np.zeros_like(A)
+    idx = lambda z, y, x: (z * k + y) * k + x
+    for z in range(k):
+        for y in range(k):
+            for x in range(k):
+                i = idx(z, y, x)
+                want[i, i] = 6.0 + pe + pe / 2 + pe / 4
+                for (dz, dy, dx), p in (((0, 0, 1), pe), ((0, 1, 0), pe / 2), ((1, 0, 0), pe / 4)):
+                    if min(z - dz, y - dy, x - dx) >= 0:
+                        want[i, idx(z - dz, y - dy, x - dx)] = -1.0 - p          # upwind: the convection sits on the lower side
+                    if max(z + dz, y + dy, x + dx) < k:
+                        want[i, idx(z + dz, y + dy, x + dx)] = -1.0
+    np.testing.assert_array_equal(A, want)
+    assert all(np.all(np.diff(ci[rp[i]:rp[i + 1]]) > 0) for i in range(k ** 3))     # rows sorted
+
+
+@pytest.mark.parametrize("name", SCHEDULED)
+def test_scheduled_systems_mix_wide_and_narrow(name):
+    """What the GPU tests rely on: in both triangles at least one level of more than 1024 rows, at least one of at most 1024
+    and at least two launches; the layered ones have exactly the widths asked for; the checker's own factor has the defining
+    property."""
+    rp, ci, v = scheduled(name)
+    n, L, U, zp = _factor(rp, ci, v)
+    assert zp == -1
+    fw, bw = K.levels(n, L, U)
+    wf, wb = IC.widths(fw), IC.widths(bw)
+    for w in (wf, wb):
+        assert (w > WG).any() and (w <= WG).any() and IC.segments(w, WG) >= 2, (name, list(w))
+    if name.startswith("layered"):
+        assert list(wf) == K.LAYERS_L and list(wb) == K.LAYERS_U
+        assert np.iscomplexobj(v) == name.endswith("_c")
+        cols = [ci[rp[i]:rp[i + 1]] for i in range(0, n, 97)]
+        assert any(np.any(np.diff(c) < 0) for c in cols) and any(len(set(c)) < len(c) for c in cols)       # unsorted, split
+    if name == "convdiff3d40":
+        assert (n, len(wf), len(wb), int((wf > WG).sum()), K.launches(n, L, U)) == (64000, 118, 118, 26, 56)
+    if name == "convdiff3d40_dropped":                       # U's levels are its own: not those of L's transposed pattern
+        assert list(wb) != list(IC.widths(IC.levels(n, rp, ci)[1])) and IC.segments(wb, WG) != IC.segments(wf, WG)
+    T = IC.to_sparse(n, rp, ci, v)
+    assert abs(T - T.T).max() > 0.1                          # non-symmetric
+    worst, where, tmax = K.residual_check(n, rp, ci, v, L, U)
+    print(f"{name}: {n} rows, L {len(wf)} levels / {IC.segments(wf, WG)} launches, U {len(wb)} / {IC.segments(wb, WG)}, "
+          f"checker's own |L.U - A| / bound = {worst:.3f} (most products {tmax})")
+    assert worst <= 1.0, (worst, where, tmax)
+
+
+def test_layered_nonsym_triangles_are_independent():
+    lower, upper, diag, stL, stU = K.layered_nonsym_parts(K.LAYERS_L, K.LAYERS_U, 41)
+    n = len(diag)
+    assert list(np.diff(stL)) == K.LAYERS_L and list(np.diff(stU)) == K.LAYERS_U
+    pl = {(i, j) for i in range(n) for j in lower[i]}
+    pu = {(j, i) for i in range(n) for j in upper[i]}
+    assert all(j < i for i, j in pl) and all(j < i for i, j in pu)
+    assert len(pl & pu) < 0.01 * len(pl)                     # the upper pattern mirrors (next to) nothing of the lower one
+    rp, ci, v = K.assemble(n, lower, upper, diag)
+    A = IC.to_sparse(n, rp, ci, v)
+    off = abs(A).sum(axis=1).A1 - abs(A.diagonal())
+    offc = abs(A).sum(axis=0).A1 - abs(A.diagonal())
+    assert np.all(abs(A.diagonal()) > off) and np.all(abs(A.diagonal()) > offc)
+
+
+@pytest.mark.parametrize("cplx", [False, True])
+def test_window_edges_reach_every_case(cplx):
+    rp, ci, v = K.window_edges(5, cplx)
+    n, L, U, zp = _factor(rp, ci, v)
+    assert zp == -1 and n % K.SWEEP_ROWS and np.iscomplexobj(v) == cplx
+    assert [w[0] for w in K.sweep_windows(n, L[0])] == list(K.WINDOW_L)
+    assert [w[0] for w in K.sweep_windows(n, U[0])] == list(K.WINDOW_U)
+    # per workgroup, from the checker's factor: cnt and rowptr[row0] & 3 put it on the side of the edge it was built for
+    assert K.window_cases(n, L[0]) >= K.WINDOW_SET | {"all_rows_empty", "full_by_offset"}
+    assert K.window_cases(n, U[0]) >= K.WINDOW_SET | {"full_by_offset"}
+    TL, TU = K.triangles(n, L, U)
+    assert TL.levels <= 8 and TU.levels <= 8
+    assert K.residual_check(n, rp, ci, v, L, U)[0] <= 1.0
+    # window_cases itself, on row pointers written by hand (one workgroup of 256 rows and a tail of 4)
+    rows = lambda counts: np.concatenate([[0], np.cumsum(counts)])
+    assert K.window_cases(260, rows([8] * 256 + [1] * 4)) == {"full_aligned"}
+    assert K.window_cases(260, rows([8] * 255 + [9] + [1, 1, 0, 0])) == {"over_by_one", "last_unit_in_slack"}
+    assert K.window_cases(260, rows([0] * 256 + [1] * 3 + [0])) == {"all_rows_empty", "last_unit_in_slack"}
+    assert K.window_cases(516, rows([1] + [0] * 255 + [8] * 256 + [0, 0, 0, 3])) == {"over_by_offset"}
+    assert K.window_cases(516, rows([1] + [0] * 255 + [8] * 255 + [7] + [0, 0, 0, 4])) == {"full_by_offset"}
+
+
+@pytest.mark.parametrize("case", K.PIVOT_CASES)
+def test_pivot_cases_name_their_row(case):
+    bad, want, good = K.pivot_case(case, 45)
+    n = len(bad[0]) - 1
+    assert K.ilu0(n, *bad)[2] == want
+    assert K.ilu0(n, *good)[2] == -1 and len(good[0]) - 1 == n
+    L, U, _ = K.ilu0(n, *good)
+    fw, _ = K.levels(n, L, U)
+    wf = IC.widths(fw)
+    if case == "two_in_wide_level":                          # both failing rows on the 3000-row level, 2850 positions apart
+        other = want + 2850
+        assert fw[want] == fw[other] == 4 and wf[4] == 3000
+        first = int(np.flatnonzero(fw == 4)[0])
+        assert (want - first) // 256 == 0 and (other - first) // 256 == 11 == (3000 - 1) // 256
+        d = np.asarray(bad[2])[[bad[0][r] + np.flatnonzero(bad[1][bad[0][r]:bad[0][r + 1]] == r)[0] for r in (want, other)]]
+        assert np.all(d == 0.0)
+    elif case == "larger_row_first_in_time":
+        assert (fw[1600], fw[want]) == (1, 49) and np.all(wf[:46] <= WG) and np.all(wf[46:50] > WG)     # the first launch; the fifth
+    elif case == "narrow_run":
+        assert fw[want] == 3 and wf[2] <= WG and wf[3] <= WG
+    elif case == "empty_row":
+        assert bad[0][want + 1] == bad[0][want]
+    elif case == "nan_upper":
+        r, c = np.repeat(np.arange(n), np.diff(bad[0])), bad[1]
+        at = np.flatnonzero(np.isnan(bad[2]))
+        assert len(at) == 1 and c[at[0]] == want > r[at[0]] and wf[fw[want]] > WG
+    elif case == "complex_zero":
+        assert np.iscomplexobj(bad[2]) and fw[want] == 1
