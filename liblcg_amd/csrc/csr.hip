@@ -1667,8 +1667,8 @@ int lcg_hip_csr_destroy(lcg_hip_csr_t A)
     free_part(A->main);
     for (int i = 1; i < 4; i++) free_part(A->op[i]);
     if (A->invdiag) hipFree(A->invdiag);
-    ic0_free(A);
-    ilu0_free(A);
+    tri_factor_free(A->ic0);
+    tri_factor_free(A->ilu0);
     c64_free(A);
     A->kind = 0;
     delete A;

@@ -1,7 +1,9 @@
-// csr_tri.hpp -- what the incomplete factorisations share (csr_ic0.hip: IC(0), csr_ilu0.hip: ILU(0)): the
-// device-side extraction of a factor's pattern from A (count, scan, fill, row sort, then a second count / scan / fill that sums
-// duplicate columns), a triangle's level schedule (rows level by level, wide / narrow launch segments) and the element
-// arithmetic of the three value types.  The kernels and host helpers are `static`: each translation unit has its own copy.
+// csr_tri.hpp -- what the incomplete factorisations share (csr_ic0.hip: IC(0), csr_ilu0.hip: ILU(0)).  Here, compiled
+// into both: the factor's struct, the device-side extraction of a factor's pattern from A (count, scan, fill, row sort, then a
+// second count / scan / fill that sums duplicate columns), the element arithmetic of the three value types and the level
+// walker -- a triangle's schedule turned into launches over a row functor (each build's factor row, the solve's row).  In
+// csr_tri.hip, compiled once and declared below: the schedule itself, the two triangular applies (exact solves and Jacobi
+// sweeps), the pivot word, and the host surface behind both factors' exported entries.
 #pragma once
 
 #include <algorithm>
@@ -16,8 +18,6 @@ constexpr int IC_WG = 1024;     // threads of a narrow-group launch = widest lev
 constexpr int IC_WB = 256;      // threads per block of a wide-level launch
 constexpr int IC_SR = 256;      // rows of a sweep's workgroup = its threads
 constexpr int IC_SCH = 2048;    // its LDS window in entries (8 per row; 24 KiB with 8-byte values, 40 KiB with 16-byte ones)
-typedef int ic_v4i __attribute__((ext_vector_type(4)));
-typedef double ic_v2d __attribute__((ext_vector_type(2)));
 
 struct IcSeg { int l0, l1; bool narrow; };      // levels [l0, l1): one launch
 struct IcTri {                                  // one triangle's schedule
@@ -27,6 +27,27 @@ struct IcTri {                                  // one triangle's schedule
     std::vector<IcSeg> segs;
     int levels = 0;
 };
+
+// An incomplete factor of A as two triangles with sorted rows.  IC(0): lo = L (diagonal last), up = L^T (diagonal first).
+// ILU(0): lo = L (unit diagonal, not stored), up = U (diagonal first).
+struct TriFactor {
+    const char *name = "";      // "IC(0)" / "ILU(0)": how messages call it
+    int dg[2] = {0, 1};         // where a row of lo / up keeps its diagonal: 0 last, 1 first, 2 nowhere (unit) -- the DG of the kernels
+    int n = 0;
+    bool cplx = false, ok = false;
+    bool c64 = false;           // complex64 values (8 bytes: cplx stays false, so the build moves them as real words)
+    CsrPart lo, up;
+    IcTri fw, bw;               // lo's schedule (forward), up's (backward)
+    double *tmp = nullptr;      // lo^-1 x of the full apply (n values of the factor's type)
+    double *w = nullptr;        // ILU(0) only: U^-1 L^-1 x of the right-preconditioned product (lcg_hip_csr_ax_ilu0)
+    int sweeps = 0;             // 0: exact level-scheduled solves; k >= 1: k Jacobi sweeps per triangle
+    double *sw[2] = {nullptr, nullptr};     // the sweeps' two intermediate vectors (n values each, held while sweeps >= 1)
+    int *zp = nullptr;          // device: smallest row whose pivot failed (INT_MAX: none)
+    int zero_pivot = -1;
+    int max_merged = IC_WG;     // widest level a narrow group takes (lcg_hip_csr_{ic0,ilu0}_schedule_for_test)
+    double build_ms = 0.0;
+};
+typedef TriFactor *lcg_hip_csr::*TriSlot;       // which of a handle's two factors: &lcg_hip_csr::ic0 or &lcg_hip_csr::ilu0
 
 __device__ __forceinline__ double ic_mul(double a, double b) { return a * b; }
 __device__ __forceinline__ double2 ic_mul(double2 a, double2 b) { return cmul(a, b); }
@@ -117,131 +138,71 @@ static int extract_rows(const lcg_hip_csr *A, CsrPart &out, bool cplx, hipStream
     return bail(0);
 }
 
-// ------------------------------------------------------------------------------------------- sweeps
-// One Jacobi sweep over a whole triangle: yout_i = (x_i - sum_p T(i,c_p) yin_{c_p}) / T(i,i) for every row i in ONE launch.
-// Row i is summed as the exact solve's row sums it (one accumulator from x_i, the products subtracted in column order, one
-// ic_div).  DG says where the row keeps its diagonal: 0 last (IC(0)'s L), 1 first (IC(0)'s L^T, ILU(0)'s U), 2 nowhere -- a
-// unit diagonal that is not stored and not divided by (ILU(0)'s L).
-// The rows of a factor are short (half of A's row), so a thread per row straight out of CSR would read col / val at a stride
-// of the row length.  Instead (the row-block A.x kernels' shape, csr.hip) the workgroup's IC_SR consecutive rows own one
-// contiguous slice of col / val: it is loaded 16 bytes per lane into LDS, every load issued before the first LDS store, then
-// thread r walks row r out of LDS with up to four gathers of yin in flight, and yout is written coalesced.  A workgroup whose
-// slice does not fit the window (a dense row among its rows) walks its rows out of global memory: the same sums.
-template <class V, int DG>
-static __global__ __launch_bounds__(IC_SR) void k_ic_scale(int n, const int *__restrict__ rowptr, const V *__restrict__ val,
-                                                          const V *__restrict__ x, V *__restrict__ y, const int *done)
-{   // the first sweep, from y = 0: y = x / diag
-    if (done && *done) return;
-    const int i = blockIdx.x * IC_SR + threadIdx.x;
-    if (i < n) y[i] = DG == 2 ? x[i] : ic_div(x[i], val[DG == 1 ? rowptr[i] : rowptr[i + 1] - 1]);
-}
-
-template <class V, int DG>
-static __global__ __launch_bounds__(IC_SR) void k_ic_sweep(int n, const int *__restrict__ rowptr, const int *__restrict__ col,
-                                                          const V *__restrict__ val, const V *__restrict__ x, const V *__restrict__ yin,
-                                                          V *__restrict__ yout, const int *done)
+// ------------------------------------------------------------------------------------- level walker
+// A schedule's launches over `row`, a small functor passed by value whose operator()(i) computes row i from rows of earlier
+// levels.  A level wider than max_merged is one grid launch (k_lvl_wide); a run of narrower ones is ONE launch of one workgroup
+// that walks them with a barrier between levels (k_lvl_narrow: workgroup-scope visibility only, no flag, no wait on another
+// workgroup).  done: the solver's flag (a finished solve's launches fall through); the factor passes nullptr.
+template <class Row>
+__global__ __launch_bounds__(IC_WB) void k_lvl_wide(const int *ord, int b, int e, Row row, const int *done)
 {
-    constexpr int NRND = IC_SCH / (IC_SR * 4);          // 4-entry units per lane
-    constexpr int VU = sizeof(V) / 4;                   // 16-byte pieces of val per 4 entries
-    constexpr int UNR = 4;                              // gathers of yin in flight per lane
-    __shared__ __attribute__((aligned(16))) V sval[IC_SCH];
-    __shared__ __attribute__((aligned(16))) int scol[IC_SCH];
     if (done && *done) return;
-    const int tid = threadIdx.x;
-    const int row0 = blockIdx.x * IC_SR;
-    const int nrows = min(IC_SR, n - row0);
-    const int base = rowptr[row0] & ~3;
-    const int cnt = rowptr[row0 + nrows] - base;
-    // this lane's row bounds and x_i, requested before the slice's stream (vmcnt counts in order)
-    const int rsafe = tid < nrows ? tid : 0;
-    const int rs = rowptr[row0 + rsafe], re = rowptr[row0 + rsafe + 1];
-    V acc = x[row0 + rsafe];
-    const int b = DG == 1 ? rs + 1 : rs, f = DG == 0 ? re - 1 : re, dg = DG == 1 ? rs : re - 1;     // (dg is not read when DG == 2)
-    if (cnt > IC_SCH) {                                 // (uniform over the workgroup)
-        if (tid >= nrows) return;
-        for (int p = b; p < f; p++) acc = vsub(acc, ic_mul(val[p], yin[col[p]]));
-        yout[row0 + tid] = DG == 2 ? acc : ic_div(acc, val[dg]);
-        return;
+    const int pos = b + blockIdx.x * blockDim.x + threadIdx.x;
+    if (pos < e) row(ord[pos]);
+}
+template <class Row>
+__global__ __launch_bounds__(IC_WG) void k_lvl_narrow(const int *ord, const int *lvl, int l0, int l1, Row row, const int *done)
+{
+    if (done && *done) return;
+    for (int l = l0; l < l1; l++) {
+        for (int pos = lvl[l] + threadIdx.x; pos < lvl[l + 1]; pos += blockDim.x) row(ord[pos]);
+        __syncthreads();
     }
-    ic_v4i pc[NRND]; ic_v2d pv[NRND * VU];
-#pragma unroll
-    for (int r = 0; r < NRND; r++) {
-        const int u = tid * 4 + r * IC_SR * 4;
-        // branch-free: lanes past the slice re-read its first unit.  col / val carry 64 bytes of slack (alloc_part), so the
-        // slice's last unit may reach up to three entries past nnz.
-        const long g = (long)base + (u < cnt ? u : 0);
-        pc[r] = *reinterpret_cast<const ic_v4i *>(col + g);
-#pragma unroll
-        for (int q = 0; q < VU; q++) pv[r * VU + q] = reinterpret_cast<const ic_v2d *>(val + g)[q];
-    }
-    __builtin_amdgcn_sched_barrier(0);                  // every load above every LDS store
-#pragma unroll
-    for (int r = 0; r < NRND; r++) {
-        const int u = tid * 4 + r * IC_SR * 4;
-        if (u < cnt) {
-            *reinterpret_cast<ic_v4i *>(scol + u) = pc[r];
-#pragma unroll
-            for (int q = 0; q < VU; q++) reinterpret_cast<ic_v2d *>(sval + u)[q] = pv[r * VU + q];
+}
+template <class Row>
+static int run_levels(const IcTri &t, Row row, const int *done, hipStream_t s)
+{
+    for (const IcSeg &g : t.segs) {
+        if (g.narrow)
+            hipLaunchKernelGGL((k_lvl_narrow<Row>), dim3(1), dim3(IC_WG), 0, s, t.ord, t.lvl, g.l0, g.l1, row, done);
+        else {
+            const int b = t.lvl_h[(size_t)g.l0], e = t.lvl_h[(size_t)g.l1];
+            hipLaunchKernelGGL((k_lvl_wide<Row>), dim3((unsigned)((e - b + IC_WB - 1) / IC_WB)), dim3(IC_WB), 0, s, t.ord, b, e, row, done);
         }
     }
-    __syncthreads();
-    if (tid >= nrows) return;
-    int p = b - base;
-    const int fe = f - base;
-    for (; p + UNR <= fe; p += UNR) {
-        V a[UNR], yv[UNR];
-#pragma unroll
-        for (int q = 0; q < UNR; q++) { a[q] = sval[p + q]; yv[q] = yin[scol[p + q]]; }
-#pragma unroll
-        for (int q = 0; q < UNR; q++) acc = vsub(acc, ic_mul(a[q], yv[q]));
-    }
-    {   // the row's last 0..3 entries, their gathers in flight together as well
-        V a[UNR - 1], yv[UNR - 1];
-        const int m = fe - p;
-#pragma unroll
-        for (int q = 0; q < UNR - 1; q++) if (q < m) { a[q] = sval[p + q]; yv[q] = yin[scol[p + q]]; }
-#pragma unroll
-        for (int q = 0; q < UNR - 1; q++) if (q < m) acc = vsub(acc, ic_mul(a[q], yv[q]));
-    }
-    yout[row0 + tid] = DG == 2 ? acc : ic_div(acc, sval[dg - base]);
-}
-
-// ---------------------------------------------------------------------------------------- schedule
-static void tri_free(IcTri &t)
-{
-    if (t.ord) hipFree(t.ord);
-    if (t.lvl) hipFree(t.lvl);
-    t = IcTri();
-}
-
-// level sets -> rows level by level (a counting sort by level: rows ascend inside a level)
-static int tri_levels(IcTri &t, const std::vector<int> &level, int nlev)
-{
-    const int n = (int)level.size();
-    t.levels = nlev;
-    t.lvl_h.assign((size_t)nlev + 1, 0);
-    for (int i = 0; i < n; i++) t.lvl_h[(size_t)level[i] + 1]++;
-    for (int l = 0; l < nlev; l++) t.lvl_h[(size_t)l + 1] += t.lvl_h[(size_t)l];
-    std::vector<int> ord((size_t)n), next(t.lvl_h.begin(), t.lvl_h.end() - 1);
-    for (int i = 0; i < n; i++) ord[(size_t)next[(size_t)level[i]]++] = i;
-    HIPCHK(hipMalloc(&t.ord, sizeof(int) * (size_t)n));
-    HIPCHK(hipMalloc(&t.lvl, sizeof(int) * ((size_t)nlev + 1)));
-    HIPCHK(hipMemcpy(t.ord, ord.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(t.lvl, t.lvl_h.data(), sizeof(int) * ((size_t)nlev + 1), hipMemcpyHostToDevice));
+    HIPCHK(hipGetLastError());
     return 0;
 }
-// launches: every level wider than max_merged alone, every run of narrower ones together
-static void tri_segments(IcTri &t, int max_merged)
-{
-    t.segs.clear();
-    for (int l = 0; l < t.levels;) {
-        const int w = t.lvl_h[(size_t)l + 1] - t.lvl_h[(size_t)l];
-        if (w > max_merged) { t.segs.push_back({l, l + 1, false}); l++; continue; }
-        int m = l + 1;
-        while (m < t.levels && t.lvl_h[(size_t)m + 1] - t.lvl_h[(size_t)m] <= max_merged) m++;
-        t.segs.push_back({l, m, true});
-        l = m;
-    }
-}
+
+// --------------------------------------------------------------------------------------- csr_tri.hip
+// build side.  tri_build: the body of the build entries once the handle's type is checked -- a fresh factor in A's slot (the
+// grouping set for test survives a rebuild), `build` run on the library's stream, the pivot's verdict (`pivot_rule`: what the
+// message says a usable pivot is not).  tri_schedule: both triangles' level sets into their schedules.  pivot_arm / pivot_read:
+// the pivot word before the factor's launches, and F->zero_pivot after them (drains the stream).
+int arg_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));     // LCG_HIP_E_ARG, the text into the error string
+int tri_build(lcg_hip_csr *A, TriSlot slot, const char *name, int dg_lo, const char *pivot_rule,
+              int (*build)(lcg_hip_csr *, TriFactor *, hipStream_t));
+int tri_schedule(TriFactor *F, const std::vector<int> &level_fw, int nfw, const std::vector<int> &level_bw, int nbw);
+int pivot_arm(TriFactor *F, hipStream_t s);
+int pivot_read(TriFactor *F, hipStream_t s);
+// apply side.  tri_check: what every apply checks, in this order -- complex64 handle against entry, the factor's presence
+// (`builder`: the entry the message names), its type, n_size (< 0: not given), which, x against y (y == nullptr: the result goes
+// to a vector of the factor's own).  tri_apply: which = 0 lo^-1 x, 1 up^-1 x, 2 both, by exact solves or F->sweeps sweeps.
+// tri_call: x, y, tri_check, tri_apply on the library's stream.  park: a void callback's failure into Ctx::ax_rc (driver.hpp:
+// checked_mx).
+int tri_check(lcg_hip_csr *A, TriSlot slot, const char *name, const char *builder, bool cplx, bool c64, long n_size, int which,
+              const double *x, const double *y, const TriFactor **out);
+int tri_apply(const TriFactor *F, int which, const double *x, double *y, hipStream_t s, const int *done);
+int tri_call(lcg_hip_csr *A, TriSlot slot, const char *name, const char *builder, bool cplx, bool c64, int which, const double *x,
+             double *y, long n_size);
+void park(int rc);
+// the bodies of lcg_hip_csr_{ic0,ilu0}_info / _set_sweeps / _get_sweeps / _schedule_for_test / _factor (`entry`: the exported
+// name, `builders`: the build entries a "no factor" message names)
+int tri_info(lcg_hip_csr *A, TriSlot slot, int *levels_lo, int *levels_up, int *launches_per_apply, int *zero_pivot, double *build_ms,
+             int64_t *bytes);
+int tri_set_sweeps(lcg_hip_csr *A, TriSlot slot, const char *entry, const char *builders, int sweeps);
+int tri_get_sweeps(lcg_hip_csr *A, TriSlot slot, const char *entry, const char *builders, int *sweeps);
+int tri_schedule_for_test(lcg_hip_csr *A, TriSlot slot, int max_merged_rows);
+int tri_arrays(lcg_hip_csr *A, TriSlot slot, int which, const int **rowptr, const int **col, const double **val);
 
 } // namespace lcgh

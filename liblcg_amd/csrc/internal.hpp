@@ -302,6 +302,7 @@ inline int refuse_dense(const char *entry, bool park = false)
 #define NOT_DENSE(h, ...) do { if (::lcgh::dense_handle(h)) { ::lcgh::refuse_dense(__func__); return __VA_ARGS__; } } while (0)
 #define NOT_DENSE_CB(h) do { if (::lcgh::dense_handle(h)) { ::lcgh::refuse_dense(__func__, true); return; } } while (0)
 
+namespace lcgh { struct TriFactor; }    // csr_tri.hpp
 struct lcg_hip_csr {
     uint64_t kind = lcgh::KIND_CSR;
     int n_rows = 0;         // local rows
@@ -327,8 +328,8 @@ struct lcg_hip_csr {
     double *op_z = nullptr;     // (A_r)^T . x_r over the padded global height, and one rows-per-rank block behind it (dist_spmv_op)
     void *halo = nullptr;       // neighbour-exchange plan (comm.hip)
     void *direct = nullptr;     // direct (peer-mapped) exchange state (comm.hip, mode 2)
-    void *ic0 = nullptr;        // incomplete-Cholesky factor and its level schedules (csr_ic0.hip), a copy: built by lcg_hip_csr_build_ic0
-    void *ilu0 = nullptr;       // incomplete-LU factor L, U and their level schedules (csr_ilu0.hip), copies: built by lcg_hip_csr_build_ilu0
+    lcgh::TriFactor *ic0 = nullptr;     // incomplete-Cholesky factor L, L^T and their level schedules (csr_tri.hpp), copies: built by lcg_hip_csr_build_ic0
+    lcgh::TriFactor *ilu0 = nullptr;    // incomplete-LU factor L, U and their level schedules (csr_tri.hpp), copies: built by lcg_hip_csr_build_ilu0
     // --- complex64 values (csr_c64.hip) ---
     bool c64 = false;           // main.val holds n_nnz interleaved (re, im) floats (8 B per entry); is_complex stays false
     void *c64p = nullptr;       // the products' plans and the Jacobi reciprocals of such a matrix (csr_c64.hip: C64Data)
@@ -373,10 +374,8 @@ int device_exclusive_scan(int n, const int *counts, int *rowptr, hipStream_t s, 
 int transpose_launch(int n, int nt, long nnz, const int *rowptr, const int *col, const double *val, int *rpT, int *colT, double *valT,
                      bool cplx, int conj, int *cnt, hipStream_t s);
 void row_sort_launch(int n, const int *rowptr, int *col, double *val, bool cplx, hipStream_t s);    // k_row_sort: by (column, value)
-// csr_ic0.hip
-void ic0_free(lcg_hip_csr *A);
-// csr_ilu0.hip
-void ilu0_free(lcg_hip_csr *A);
+// csr_tri.hip
+void tri_factor_free(TriFactor *&F);                                 // an IC(0) / ILU(0) factor and everything it holds; F = nullptr
 // csr.hip
 void free_part(CsrPart &P);                                          // a part's arrays and every plan built beside them
 

@@ -1,4 +1,4 @@
-"""IC(0) applied by Jacobi sweeps on the MI355X (csr_ic0.hip: k_ic_scale, k_ic_sweep): `levels` sweeps return the exact solves'
+"""IC(0) applied by Jacobi sweeps on the MI355X (csr_tri.hip: k_ic_scale, k_ic_sweep): `levels` sweeps return the exact solves'
 bits; k sweeps lie within the rounding bound of the sweep checker (tests/ic0_sweeps_checker.py) run on the device's own factor;
 PCG with the k-sweep operator walks the checker's loops; the setting, its errors, the done flag, and the C++ sample."""
 import os

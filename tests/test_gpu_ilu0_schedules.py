@@ -428,7 +428,7 @@ def test_right_bicgstab_whole_run(api, name, eps):
 @pytest.mark.parametrize("sweeps", [0, 4])
 def test_early_convergence_with_and_without_progress_callback(api, case10k, sweeps):
     """A solve that converges leaves the same iterate and count whether or not a progress callback forces a synchronisation in
-    every iteration: the solves (k_ilu_solve_wide / _narrow) and sweeps launched after the stop see the done flag and write
+    every iteration: the solves (k_lvl_wide / _narrow over TriSolveRow) and sweeps launched after the stop see the done flag and write
     nothing."""
     n, rp, ci, v, b, xs = case10k
     A = api.CsrMatrix.from_csr(rp, ci, v)
