@@ -70,6 +70,9 @@ def test_random_systems_against_the_oracle(port):
         A.destroy()
 
 
+CAPPED_ITERATES_RTOL = 1e-13     # a handful of capped iterations walk the oracle's iterates to rounding, whatever the system
+
+
 def test_short_row_systems_against_the_oracle(port):
     """The same on systems with 5 and 11 entries per row (2 and 5 offset pairs + the diagonal): the one-wavefront-per-block
     product with one and with two partial sums per row (k_spmv_run1 / k_spmv_run1d<1>, <2>) under CG (two launches per
@@ -123,6 +126,6 @@ def test_short_row_systems_against_the_oracle(port):
                 i6 = api.lcg_solver("lcg_hip_csr_ax", None, m, b, n, p6, A, sid)
             r6 = port.solve(sid, rp, ci, v, bh, para=po.default_para(epsilon=eps, abs_diff=abs_diff, max_iterations=6), jacobi=(sid == api.LCG_PCG))
             assert i6.ret == r6["ret"] == -1019 and i6.iterations == 6, tag
-            assert np.linalg.norm(m.cpu().numpy() - r6["x"]) <= 1e-13 * np.linalg.norm(r6["x"]), tag
+            assert np.linalg.norm(m.cpu().numpy() - r6["x"]) <= CAPPED_ITERATES_RTOL * np.linalg.norm(r6["x"]), tag
         A.destroy()
     assert {"k_spmv_run1d", "k_spmv_lds1d"} <= seen, seen
