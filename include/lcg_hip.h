@@ -560,6 +560,31 @@ int lcg_hip_spmv_op(lcg_hip_csr_t A, const double *x, double *y, int layout, int
  * allows, the sums ride in the product's epilogue (what the built-in solvers use on one GPU: lcg_hip_csr_last_kernel says
  * "carrying the dot"); otherwise product and reduction run as two launches.  Real matrices. */
 int lcg_hip_spmv_dot(lcg_hip_csr_t A, const double *x, double *y, const double *u, double *result2);
+/* Y = A.X for k = 2, 4 or 8 vectors in ONE launch: col / val are read once for all of them.  A block of k vectors is one array
+ * of rows x k doubles, row-major (X[i * k + j] = row i of column j; X: n_cols rows, Y: n_rows), its base 16-byte aligned; other
+ * counts are padded with zero columns.  Any other k, a null pointer or a misaligned base: LCG_HIP_E_ARG before the device is
+ * touched.  Real fp64 CSR handles on one GPU: complex, complex64, dense and sharded handles return LCG_HIP_E_ARG
+ * (lcg_hip_last_error() says why).  Column j's sums are added in an order fixed by the matrix alone: the same bits whatever the
+ * other columns hold, whatever k is, from call to call.  Reads the plain CSR arrays: no single-vector plan is built or used. */
+int lcg_hip_spmm(lcg_hip_csr_t A, int k, const double *X, double *Y);
+/* The same product carrying, per column, the sum the batched loops take right after it (d.Ad): dots[j] = (A.X)_j . U_j, j < k
+ * (host, after a stream synchronise).  The sums ride in the product's epilogue as per-workgroup partial sums added in a fixed order. */
+int lcg_hip_spmm_dot(lcg_hip_csr_t A, int k, const double *X, double *Y, const double *U, double *dots);
+/* Batched CG (lcg.cpp:143-274) and PCG with the built-in Jacobi (lcg.cpp:293-434; needs lcg_hip_csr_build_jacobi(A)) over
+ * k = 2, 4 or 8 right-hand sides against one real fp64 CSR matrix on one GPU: M (in/out) and B are blocks of k vectors in
+ * lcg_hip_spmm's layout and live where `mem` says.  Each column runs the reference's recurrence as if it were alone -- its own
+ * alpha, beta, stop test, "already optimised" test, NaN scan, count and code -- while one multi-vector product per iteration reads
+ * the matrix once for all of them.  A column that has stopped is final: its column of M is not written again.  ret, iterations,
+ * residual: host arrays of k (or NULL) receiving each column's liblcg code (LCG_CONVERGENCE, LCG_REACHED_MAX_ITERATIONS,
+ * LCG_ALREADY_OPTIMIZIED, LCG_NAN_VALUE), iteration count and residual; lcg_hip_last_iterations / _residual report the column
+ * that ran longest.  Returns 0 when the loop ran, whatever the columns' verdicts; LCG_HIP_E_ARG (k, null or misaligned M / B, a
+ * complex / complex64 / dense / sharded / non-square handle; before the device is touched), LCG_INVILAD_MAX_ITERATIONS,
+ * LCG_INVILAD_EPSILON, LCG_NULL_PRECONDITION_MATRIX (no Jacobi diagonal), or a runtime failure.  No progress callback, no caller
+ * workspaces; column j's results depend on A, column j of B and M and param alone, bit for bit. */
+int lcg_hip_lcg_multi(lcg_hip_csr_t A, int k, double *M, const double *B, const lcg_para *param,
+                      int *ret, int *iterations, double *residual, int mem);
+int lcg_hip_lpcg_multi(lcg_hip_csr_t A, int k, double *M, const double *B, const lcg_para *param,
+                       int *ret, int *iterations, double *residual, int mem);
 /* y = op(A).x for a complex64 handle (layout / conjugate as lcg_hip_spmv_op: A, A^T, conj(A), A^H), summed in fp32 as cuSPARSE's
  * CUDA_C_32F (clcg_cudaf.cu's Afp), each row in one fixed order: bit-identical from call to call.  k_c64_rows (W lanes per row,
  * each pair of entries one 16-byte value load and one 8-byte column load, row ends masked by selects) and, for rows of more than max(256, 64 W) entries, k_c64_long (one workgroup per row);

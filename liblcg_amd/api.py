@@ -262,6 +262,12 @@ class CsrMatrix:
     def spmv(self, x, y):
         _chk(L.load().lcg_hip_spmv(self.h, _ptr(x)[0], _ptr(y)[0]), "spmv")
 
+    def spmm(self, X, Y):
+        """Y = A.X for the k = 2, 4 or 8 columns of X in one launch (lcg_hip_spmm): X (n_cols, k) and Y (n_rows, k) are C-contiguous
+        float64 CUDA tensors, 16-byte aligned.  Real fp64 matrices on one GPU."""
+        k = _block_k(X, Y)
+        _chk(L.load().lcg_hip_spmm(self.h, k, _ptr(X)[0], _ptr(Y)[0]), "spmm")
+
     def distribute(self, n_global: int, mode: int = 0):
         _chk(L.load().lcg_hip_csr_distribute(self.h, n_global, mode), "csr_distribute")
 
@@ -434,6 +440,50 @@ def lcg(Afp, Pfp, m, B, n_size, param, instance, Gk=None, Dk=None, ADk=None) -> 
                          ws[0], ws[1], ws[2], mem)
     _chk(rc, "lcg")
     return SolveInfo(rc, lib.lcg_hip_last_iterations(), lib.lcg_hip_last_residual())
+
+
+def _block_k(*blocks):
+    """k of 2-D (n, k) C-contiguous float64 blocks of vectors (numpy arrays or torch tensors), all alike."""
+    k = None
+    for X in blocks:
+        if isinstance(X, np.ndarray):
+            ok = X.ndim == 2 and X.dtype == np.float64 and X.flags["C_CONTIGUOUS"]
+        else:
+            import torch
+            ok = isinstance(X, torch.Tensor) and X.dim() == 2 and X.dtype == torch.float64 and X.is_contiguous()
+        if not ok:
+            raise ValueError("a block of vectors is a 2-D (n, k) C-contiguous float64 array or tensor")
+        if k is not None and X.shape[1] != k:
+            raise ValueError("blocks of vectors with different k")
+        k = int(X.shape[1])
+    return k
+
+
+def _multi(name, A, M, B, param):
+    lib = L.load()
+    k = _block_k(M, B)
+    if tuple(M.shape) != tuple(B.shape):
+        raise ValueError("M and B must have the same shape")
+    (pm, mem), (pb, mem_b) = _ptr(M), _ptr(B)
+    if mem != mem_b:
+        raise ValueError("M and B must live in the same memory space")
+    ret = (C.c_int * k)(); its = (C.c_int * k)(); res = (C.c_double * k)()
+    rc = getattr(lib, name)(_instance(A), k, pm, pb, C.byref(param) if param is not None else None, ret, its, res, mem)
+    _chk(rc, name)
+    if rc:
+        raise LcgHipError(f"{name}: rc={rc}")
+    return [SolveInfo(ret[j], its[j], res[j]) for j in range(k)]
+
+
+def lcg_multi(A, M, B, param) -> list:
+    """Batched CG (lcg_hip_lcg_multi): M (in/out) and B are (n, k) blocks of k = 2, 4 or 8 columns, every column solved as if it
+    were alone while the matrix is read once per iteration for all of them.  Returns one SolveInfo per column."""
+    return _multi("lcg_hip_lcg_multi", A, M, B, param)
+
+
+def lpcg_multi(A, M, B, param) -> list:
+    """Batched PCG with the built-in Jacobi (lcg_hip_lpcg_multi; A.build_jacobi() first).  As lcg_multi."""
+    return _multi("lcg_hip_lpcg_multi", A, M, B, param)
 
 
 def lcgs(Afp, Pfp, m, B, n_size, param, instance, *workspaces) -> SolveInfo:

@@ -1,0 +1,61 @@
+// multi.hpp -- what the multi-vector product (csr_multi.hip) and the batched loops (solvers_multi.hip) share.  Not installed.
+//
+// A block of k vectors is ONE array of n * k doubles, row-major: X[i * k + j] is row i of column j (k = 2, 4, 8; the base
+// 16-byte aligned, so a row is k / 2 aligned 16-byte pieces).  DESIGN.md section 15.
+#pragma once
+
+#include "driver.hpp"
+
+namespace lcgh {
+
+constexpr int MM_MG = 512;      // most partial sums per running sum a consumer adds up = stride of the k-wide tables
+constexpr int MM_MAXK = 8;
+
+typedef double m2d __attribute__((ext_vector_type(2)));
+
+// k in {2, 4, 8}, no null pointer, every base 16-byte aligned: decided BEFORE the device is touched (0, or LCG_HIP_E_ARG with
+// lcg_hip_last_error() naming the entry and the reason)
+int multi_args(const char *entry, int k, const void *a, const void *b, const void *c = (const void *)16);
+// a CSR handle this path serves: real fp64, whole (not sharded), not dense (0, or LCG_HIP_E_ARG with the text)
+int multi_handle(const char *entry, const lcg_hip_csr *A);
+
+// Y = A.X for the k columns in one launch (P's plain CSR arrays: no plan is built or used).  With U: column j's sum
+// (A.X)_j . U_j is left as *slots <= MM_MG partial sums at dots[j * MM_MG ...], to be added in index order.  `big` holds the
+// per-workgroup sums of a matrix with more than MM_MG row blocks on their way there (spmm_big_doubles(P, k) doubles; may be
+// null where that is 0).
+int spmm_launch(const CsrPart &P, int k, const double *X, double *Y, hipStream_t s, const int *done, const double *U = nullptr,
+                double *big = nullptr, double *dots = nullptr, int *slots = nullptr);
+size_t spmm_big_doubles(const CsrPart &P, int k);
+
+// Sum the g <= MM_MG partials of each of NS running sums (table row r = pin + r * MM_MG) into sums[r] (LDS), the whole block taking
+// part: per lane its partials in index order, the lanes by wave_sum, the wavefronts in order -- the same bits wherever and
+// however often this runs.  Ends with a barrier.
+template <int NS>
+__device__ __forceinline__ void msum(const double *pin, int g, double *sums)
+{
+    constexpr int PER = MM_MG / VB;
+    __shared__ double sh[NS][VB / 64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll 8
+    for (int r = 0; r < NS; r++) {
+        double t = 0.0;
+#pragma unroll
+        for (int q = 0; q < PER; q++) {
+            const int j = threadIdx.x + q * VB;
+            const double x = pin[r * MM_MG + (j < g ? j : 0)];      // branch-free: select after the load
+            t += j < g ? x : 0.0;
+        }
+        t = wave_sum(t);
+        if (lane == WSUM_LANE) sh[r][w] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x < NS) {
+        double t = 0.0;
+#pragma unroll
+        for (int q = 0; q < VB / 64; q++) t += sh[threadIdx.x][q];
+        sums[threadIdx.x] = t;
+    }
+    __syncthreads();
+}
+
+} // namespace lcgh

@@ -1,0 +1,441 @@
+// solvers_multi.hip -- batched CG and PCG (built-in Jacobi) over k = 2, 4, 8 right-hand sides: lcg_hip_lcg_multi, lcg_hip_lpcg_multi.
+//
+// Each column runs the reference's own recurrence as if it were alone (lcg.cpp:143-274, 293-434): its own alpha, beta, rho, its own
+// residual under the same stop rule, its own "already optimised" test, NaN scan, count and return code.  What the columns share is
+// the matrix: one multi-vector product (csr_multi.hip) per iteration reads col / val once for all of them.
+//
+// The classic three-pass schedule of solvers_real.hip, k wide (vectors: multi.hpp's row-major blocks):
+//     A.d carrying d.Ad  |  [alpha] m += a d, g += a Ad (PCG: r -= a Ad, z = r / diag) + m.m, g.g (r.r, z.r), NaN  |  [close] d = b d - g (z + b d)
+// All scalars live on the device in MState, k wide.  A scalar step rides in the prologue of the pass that consumes it, as in
+// k_vecf (devcommon.hpp): every block adds the previous pass's partial sums in msum's fixed order, runs the step for all columns on
+// a copy of MState in LDS, and block 0 commits the copy to the other buffer of a pair.
+//
+// Frozen columns: once a column has stopped (converged, NaN, already optimised) its column of the iterate and of g / r, z, d is never
+// written again -- a SELECT on the column's stop word, not a multiplication by zero, so a stopped NaN column leaks into nothing
+// (its sums are computed apart and never read).  The product still forms such a column's A.d, which nothing reads.  When every column
+// has stopped, MState::all_done makes every later kernel fall through, like DevState::done, so the host enqueues ahead.
+//
+// A thread of a vector pass handles 16-byte pieces e, e + stride, ...; the stride is a multiple of k / 2, so its two columns never
+// change: their coefficients and stop words sit in registers, their sums are two accumulators per running sum.  A column's partial
+// sums are added in a fixed order (lane's own in index order, lanes of a wavefront by xor-butterfly, wavefronts in order, blocks in
+// order): the same bits whatever the other columns hold, from call to call.
+#include "multi.hpp"
+
+namespace lcgh {
+namespace {
+
+struct MState {
+    double ak[MM_MAXK], bk[MM_MAXK], rho[MM_MAXK], m2[MM_MAXK], g2[MM_MAXK], residual[MM_MAXK];
+    double eps, n_global;
+    int t[MM_MAXK];         // completed iterations (the reference's t), per column
+    int stop[MM_MAXK];      // ST_RUNNING, or why the column stopped (ST_CONVERGED, ST_NAN, ST_ALREADY)
+    int abs_diff;
+    int it;                 // iteration bodies started
+    int all_done;           // every column has stopped: every later kernel is a no-op
+    int pub_mask;           // HostStatus is refreshed when (it & pub_mask) == 0, and when all columns have stopped
+    HostStatus *host;
+};
+static_assert(sizeof(MState) % 8 == 0, "MState is copied in 8-byte words");
+
+__global__ void k_minit(MState *st, double eps, double n_global, int abs_diff, int pub_mask, HostStatus *host)
+{
+    double *w = reinterpret_cast<double *>(st);
+    for (int i = threadIdx.x; i < (int)(sizeof(MState) / 8); i += blockDim.x) w[i] = 0.0;
+    __syncthreads();
+    if (threadIdx.x == 0) { st->eps = eps; st->n_global = n_global; st->abs_diff = abs_diff; st->pub_mask = pub_mask; st->host = host; }
+}
+
+__device__ __forceinline__ void mpublish(MState *st)
+{
+    HostStatus *h = st->host;
+    if (!h) return;         // a block's private copy: only block 0 mirrors to the host
+    if (!st->all_done && (st->it & st->pub_mask)) return;
+    h->done = st->all_done;
+    h->it = st->it;         // (posted writes: the host paces itself on them and reads MState with a real copy before it returns)
+}
+template <int K> __device__ __forceinline__ void all_stopped(MState *st)
+{
+    int all = 1;
+#pragma unroll
+    for (int j = 0; j < K; j++) all &= st->stop[j] != ST_RUNNING;
+    st->all_done = all;
+}
+
+// ---- scalar steps: sums[s * K + j] = running sum s of column j ------------------------------------------------------------------
+template <int K> struct MFinNone {
+    static constexpr int NS = 0;
+    __device__ void operator()(MState *, const double *) const {}
+};
+// setup: |m|^2 (clamped), the residual's numerator, rho; "already optimised" per column (lcg.cpp:178-203, 341-359: in abs_diff mode
+// BOTH criteria are tried, in this order).  PCG: sums m.m, r.r, z.r; CG: m.m, g.g (rho = g.g)
+template <int K, bool PCG> struct MFinInit {
+    static constexpr int NS = PCG ? 3 : 2;
+    __device__ void operator()(MState *st, const double *sum) const
+    {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            const double m2 = clamp1(sum[j]), g2 = sum[K + j];
+            st->m2[j] = m2; st->g2[j] = g2; st->rho[j] = PCG ? sum[2 * K + j] : g2;
+            double r;
+            bool already = false;
+            if (st->abs_diff && sqrt(g2) / st->n_global <= st->eps) { r = sqrt(g2) / st->n_global; already = true; }
+            else if (g2 / m2 <= st->eps) { r = g2 / m2; already = true; }
+            else r = st->abs_diff ? sqrt(g2) / st->n_global : g2 / m2;
+            st->residual[j] = r;
+            st->stop[j] = already ? ST_ALREADY : ST_RUNNING;
+        }
+        all_stopped<K>(st);
+        mpublish(st);
+    }
+};
+// first step of a body: counts it; alpha = rho / d.Ad per running column (lcg.cpp:235, 390)
+template <int K> struct MFinAlpha {
+    static constexpr int NS = 1;
+    __device__ void operator()(MState *st, const double *sum) const
+    {
+        st->it++;
+        if (st->all_done) return;
+#pragma unroll
+        for (int j = 0; j < K; j++) if (st->stop[j] == ST_RUNNING) st->ak[j] = st->rho[j] / sum[j];
+    }
+};
+// closing step of a body, per running column (lcg.cpp:244-257, 401-416).  CG sums: m.m, g.g, NaN count; PCG: m.m, r.r, z.r, NaN count
+template <int K, bool PCG> struct MFinClose {
+    static constexpr int NS = PCG ? 4 : 3;
+    __device__ void operator()(MState *st, const double *sum) const
+    {
+        if (!st->all_done) {
+#pragma unroll
+            for (int j = 0; j < K; j++) {
+                if (st->stop[j] != ST_RUNNING) continue;
+                const double mm = sum[j], g2 = sum[K + j], nan = sum[(NS - 1) * K + j];
+                const double rho_new = PCG ? sum[2 * K + j] : g2;
+                st->m2[j] = clamp1(mm);
+                st->t[j]++;
+                if (nan > 0.0 || mm != mm) { st->stop[j] = ST_NAN; continue; }
+                st->bk[j] = rho_new / st->rho[j];
+                st->rho[j] = rho_new;
+                st->g2[j] = g2;
+                const double r = st->abs_diff ? sqrt(g2) / st->n_global : g2 / st->m2[j];      // the next loop head's test (lcg.cpp:208-222)
+                st->residual[j] = r;
+                if (r <= st->eps) st->stop[j] = ST_CONVERGED;
+            }
+            all_stopped<K>(st);
+        }
+        mpublish(st);
+    }
+};
+
+// ---- vector passes ----------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ m2d ld2(const double *p, long e) { return reinterpret_cast<const m2d *>(p)[e]; }
+// only the running halves of a piece are written: a stopped column's bytes are never stored to again
+__device__ __forceinline__ void st2(double *p, long e, m2d v, bool r0, bool r1)
+{
+    if (r0 && r1) reinterpret_cast<m2d *>(p)[e] = v;
+    else if (r0) p[2 * e] = v.x;
+    else if (r1) p[2 * e + 1] = v.y;
+}
+__device__ __forceinline__ m2d nan2(m2d v) { m2d f; f.x = v.x != v.x ? 1.0 : 0.0; f.y = v.y != v.y ? 1.0 : 0.0; return f; }
+
+// Op provides: static constexpr int NS;  void prep(const MState &, int c0) (the coefficients of columns c0, c0 + 1);
+//              void apply(long e, long row, bool r0, bool r1, m2d *acc)
+struct MOpNone {
+    static constexpr int NS = 0;
+    __device__ void prep(const MState &, int) {}
+    __device__ void apply(long, long, bool, bool, m2d *) {}
+};
+struct MOpCgInit {      // g = Ad - B; d = -g; m.m, g.g                   lcg.cpp:171-183
+    static constexpr int NS = 2;
+    const double *Ad, *B, *m; double *g, *d;
+    __device__ void prep(const MState &, int) {}
+    __device__ void apply(long e, long, bool r0, bool r1, m2d *acc)
+    {
+        const m2d gv = ld2(Ad, e) - ld2(B, e), mv = ld2(m, e);
+        st2(g, e, gv, r0, r1); st2(d, e, -gv, r0, r1);
+        acc[0] += mv * mv; acc[1] += gv * gv;
+    }
+};
+struct MOpPcgInit {     // r = B - Ad; z = r / diag; d = z; m.m, r.r, z.r  lcg.cpp:317-339
+    static constexpr int NS = 3;
+    const double *Ad, *B, *m, *invdiag; double *r, *z, *d;
+    __device__ void prep(const MState &, int) {}
+    __device__ void apply(long e, long row, bool r0, bool r1, m2d *acc)
+    {
+        const m2d rv = ld2(B, e) - ld2(Ad, e), mv = ld2(m, e);
+        const m2d zv = invdiag[row] * rv;
+        st2(r, e, rv, r0, r1); st2(z, e, zv, r0, r1); st2(d, e, zv, r0, r1);
+        acc[0] += mv * mv; acc[1] += rv * rv; acc[2] += zv * rv;
+    }
+};
+struct MOpCgUpdate {    // m += a d; g += a Ad; m.m, g.g, NaN              lcg.cpp:237-255
+    static constexpr int NS = 3;
+    double *m, *g; const double *d, *Ad; m2d ak;
+    __device__ void prep(const MState &L, int c0) { ak.x = L.ak[c0]; ak.y = L.ak[c0 + 1]; }
+    __device__ void apply(long e, long, bool r0, bool r1, m2d *acc)
+    {
+        const m2d mv = ld2(m, e) + ak * ld2(d, e);
+        const m2d gv = ld2(g, e) + ak * ld2(Ad, e);
+        st2(m, e, mv, r0, r1); st2(g, e, gv, r0, r1);
+        acc[0] += mv * mv; acc[1] += gv * gv; acc[2] += nan2(mv);
+    }
+};
+struct MOpPcgUpdate {   // m += a d; r -= a Ad; z = r / diag; m.m, r.r, z.r, NaN   lcg.cpp:392-414
+    static constexpr int NS = 4;
+    double *m, *r, *z; const double *d, *Ad, *invdiag; m2d ak;
+    __device__ void prep(const MState &L, int c0) { ak.x = L.ak[c0]; ak.y = L.ak[c0 + 1]; }
+    __device__ void apply(long e, long row, bool r0, bool r1, m2d *acc)
+    {
+        const m2d mv = ld2(m, e) + ak * ld2(d, e);
+        const m2d rv = ld2(r, e) - ak * ld2(Ad, e);
+        const m2d zv = invdiag[row] * rv;
+        st2(m, e, mv, r0, r1); st2(r, e, rv, r0, r1); st2(z, e, zv, r0, r1);
+        acc[0] += mv * mv; acc[1] += rv * rv; acc[2] += zv * rv; acc[3] += nan2(mv);
+    }
+};
+struct MOpCgDir {       // d = b d - g                                     lcg.cpp:259-263
+    static constexpr int NS = 0;
+    double *d; const double *g; m2d bk;
+    __device__ void prep(const MState &L, int c0) { bk.x = L.bk[c0]; bk.y = L.bk[c0 + 1]; }
+    __device__ void apply(long e, long, bool r0, bool r1, m2d *) { st2(d, e, bk * ld2(d, e) - ld2(g, e), r0, r1); }
+};
+struct MOpPcgDir {      // d = z + b d                                     lcg.cpp:418-422
+    static constexpr int NS = 0;
+    double *d; const double *z; m2d bk;
+    __device__ void prep(const MState &L, int c0) { bk.x = L.bk[c0]; bk.y = L.bk[c0 + 1]; }
+    __device__ void apply(long e, long, bool r0, bool r1, m2d *) { st2(d, e, ld2(z, e) + bk * ld2(d, e), r0, r1); }
+};
+
+// One fused pass over n2 = n * K / 2 pieces with the scalar step `fin` in its prologue.  ALL: every column is worked on whatever its
+// stop word says (the setup passes, before the words mean anything).
+template <int K, class Fin, class Op, bool ALL>
+__global__ __launch_bounds__(VB) void k_mvecf(Fin fin, Op op, long n2, const double *pin, int gin, double *pout, const MState *cur, MState *next)
+{
+    constexpr int K2 = K / 2;
+    constexpr int NSF = Fin::NS > 0 ? Fin::NS * K : 1, NSO = Op::NS > 0 ? Op::NS : 1;
+    __shared__ MState L;
+    __shared__ double sums[NSF];
+    __shared__ double wsh[VB / 64][NSO][K];
+    {
+        const double *src = reinterpret_cast<const double *>(cur);
+        double *dst = reinterpret_cast<double *>(&L);
+        for (int i = threadIdx.x; i < (int)(sizeof(MState) / 8); i += VB) dst[i] = src[i];
+    }
+    if (Fin::NS > 0) msum<NSF>(pin, gin, sums);     // ends with a barrier: L and sums are complete
+    else __syncthreads();
+    if (threadIdx.x == 0) {
+        if (blockIdx.x != 0) L.host = nullptr;
+        fin(&L, sums);
+    }
+    __syncthreads();
+    if (blockIdx.x == 0) {
+        const double *src = reinterpret_cast<const double *>(&L);
+        double *dst = reinterpret_cast<double *>(next);
+        for (int i = threadIdx.x; i < (int)(sizeof(MState) / 8); i += VB) dst[i] = src[i];
+    }
+    if (L.all_done && !ALL) return;
+    // (gridDim.x * VB and VB are multiples of K2: this thread's pieces all belong to columns c0, c0 + 1)
+    const int c0 = 2 * ((int)threadIdx.x % K2);
+    const bool r0 = ALL || L.stop[c0] == ST_RUNNING, r1 = ALL || L.stop[c0 + 1] == ST_RUNNING;
+    op.prep(L, c0);
+    m2d acc[NSO];
+#pragma unroll
+    for (int s = 0; s < NSO; s++) acc[s] = (m2d)(0.0);
+    if (r0 || r1) {
+        const long stride = (long)gridDim.x * VB;
+        for (long e = (long)blockIdx.x * VB + threadIdx.x; e < n2; e += stride) op.apply(e, e / K2, r0, r1, acc);
+    }
+    if (Op::NS > 0) {
+        // lanes l, l + K2, l + 2 K2, ... of a wavefront hold the same two columns: xor-butterfly over them, then the wavefronts in order
+        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+        for (int s = 0; s < NSO; s++) {
+            double x = acc[s].x, y = acc[s].y;
+#pragma unroll
+            for (int off = 32; off >= K2; off >>= 1) { x += __shfl_xor(x, off, 64); y += __shfl_xor(y, off, 64); }
+            if (lane < K2) { wsh[w][s][2 * lane] = x; wsh[w][s][2 * lane + 1] = y; }
+        }
+        __syncthreads();
+        if (threadIdx.x < NSO * K) {
+            const int s = threadIdx.x / K, j = threadIdx.x % K;
+            double v = 0.0;
+#pragma unroll
+            for (int q = 0; q < VB / 64; q++) v += wsh[q][s][j];
+            pout[(s * K + j) * MM_MG + blockIdx.x] = v;
+        }
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------------
+struct SolveGuard {     // what ~Driver does for the single-vector loops
+    Ctx &c;
+    explicit SolveGuard(Ctx &c_) : c(c_) { c.in_solve = true; c.ax_rc = 0; c.cnt_vec = c.cnt_scal = c.cnt_allreduce = c.cnt_ax = 0; }
+    ~SolveGuard() { c.in_solve = false; }
+};
+
+template <int K, bool PCG>
+struct MultiSolve {
+    Ctx &c;
+    const CsrPart &P;
+    long n2;
+    int grid;
+    MState *cur, *next;
+    double *tab_dot, *tab_sum;      // the k-wide tables: d.Ad's partial sums (the product's), the update pass's
+    int g_dot = 0;
+
+    template <class Fin, class Op, bool ALL = false> int pass(Fin fin, Op op, const double *pin, int gin, int g = 0)
+    {
+        c.cnt_vec++;
+        hipLaunchKernelGGL((k_mvecf<K, Fin, Op, ALL>), dim3(g ? g : grid), dim3(VB), 0, c.stream, fin, op, n2, pin, gin, tab_sum, cur, next);
+        HIPCHK(hipGetLastError());
+        std::swap(cur, next);
+        return 0;
+    }
+};
+
+static int lcg_code(int stop)
+{
+    switch (stop) {
+    case ST_ALREADY: return LCG_ALREADY_OPTIMIZIED;
+    case ST_NAN: return LCG_NAN_VALUE;
+    case ST_CONVERGED: return LCG_CONVERGENCE;
+    default: return LCG_REACHED_MAX_ITERATIONS;
+    }
+}
+
+template <int K, bool PCG>
+static int run_multi(lcg_hip_csr *A, double *M, const double *B, const lcg_para &p, int *ret, int *iterations, double *residual, int mem)
+{
+    Ctx &c = ctx();
+    const int n = A->n_rows;
+    const size_t nb = sizeof(double) * (size_t)n * K;
+    HostBridge hb;
+    Workspace ws;
+    SolveGuard guard(c);
+    TRY(hb.open(mem, M, B, nb, c.stream));
+    double *g = nullptr, *z = nullptr, *d = nullptr, *Ad = nullptr, *big = nullptr, *stmem = nullptr;
+    TRY(ws.get(g, nullptr, nb));        // (PCG: r)
+    if (PCG) TRY(ws.get(z, nullptr, nb));
+    TRY(ws.get(d, nullptr, nb));
+    TRY(ws.get(Ad, nullptr, nb));
+    const size_t nbig = spmm_big_doubles(A->main, K);
+    if (nbig) TRY(ws.get(big, nullptr, sizeof(double) * nbig));
+    TRY(ws.get(stmem, nullptr, 2 * 512));
+    static_assert(sizeof(MState) <= 512, "two states share one small pool vector");
+
+    MultiSolve<K, PCG> k{c, A->main, (long)n * (K / 2), 0, reinterpret_cast<MState *>(stmem),
+                         reinterpret_cast<MState *>(reinterpret_cast<char *>(stmem) + 512), c.partials_pair[0], c.partials_pair[1]};
+    k.grid = grid_for(k.n2);
+    const long work = (long)n * K;
+    c.hstat->it = 0; c.hstat->done = 0; c.hstat->status = 0; c.hstat->t = 0; c.hstat->residual = 0.0;
+    hipLaunchKernelGGL(k_minit, dim3(1), dim3(64), 0, c.stream, k.cur, p.epsilon, (double)n, p.abs_diff, work >= (1 << 20) ? 0 : 3, c.hstat_dev);
+    HIPCHK(hipGetLastError());
+
+    // setup (lcg.cpp:168-203, 314-359): A.m for the guess, the first residual and direction, the verdict "already optimised"
+    c.cnt_ax++;
+    TRY(spmm_launch(k.P, K, M, Ad, c.stream, nullptr));
+    if (PCG) TRY((k.template pass<MFinNone<K>, MOpPcgInit, true>(MFinNone<K>{}, MOpPcgInit{Ad, B, M, A->invdiag, g, z, d}, nullptr, 0)));
+    else TRY((k.template pass<MFinNone<K>, MOpCgInit, true>(MFinNone<K>{}, MOpCgInit{Ad, B, M, g, d}, nullptr, 0)));
+    TRY((k.template pass<MFinInit<K, PCG>, MOpNone, true>(MFinInit<K, PCG>{}, MOpNone{}, k.tab_sum, k.grid, 1)));
+
+    auto body = [&]() -> int {
+        c.cnt_ax++;
+        TRY(spmm_launch(k.P, K, d, Ad, c.stream, &k.cur->all_done, d, big, k.tab_dot, &k.g_dot));          // :232-234, :387-389
+        if (PCG) {
+            TRY(k.pass(MFinAlpha<K>{}, MOpPcgUpdate{M, g, z, d, Ad, A->invdiag, m2d()}, k.tab_dot, k.g_dot));  // :390-414
+            TRY(k.pass(MFinClose<K, true>{}, MOpPcgDir{d, z, m2d()}, k.tab_sum, k.grid));                      // :415-422
+        } else {
+            TRY(k.pass(MFinAlpha<K>{}, MOpCgUpdate{M, g, d, Ad, m2d()}, k.tab_dot, k.g_dot));                  // :235-255
+            TRY(k.pass(MFinClose<K, false>{}, MOpCgDir{d, g, m2d()}, k.tab_sum, k.grid));                      // :256-263
+        }
+        return 0;
+    };
+
+    // the asynchronous loop of driver.hpp: the host only enqueues, at most `inflight` bodies ahead of the device
+    MState h;
+    auto read_state = [&]() -> int {
+        HIPCHK(hipMemcpyAsync(&h, k.cur, sizeof h, hipMemcpyDeviceToHost, c.stream));
+        HIPCHK(hipStreamSynchronize(c.stream));
+        return 0;
+    };
+    const int inflight = work >= (1 << 20) ? 6 : 24;
+    int enq = 0, rc = 0;
+    for (;;) {
+        if (p.max_iterations > 0 && enq >= p.max_iterations) break;
+        rc = body(); if (rc) break;
+        enq++;
+        if (c.hstat->done) break;
+        int spins = 0;
+        while (c.hstat->it < enq - inflight && !c.hstat->done) {
+            if (++spins > 2000) std::this_thread::sleep_for(std::chrono::microseconds(20));
+            if (spins > 200000) {   // backstop: the mapped mirror is not advancing
+                rc = read_state(); if (rc) break;
+                if (h.all_done || h.it >= enq - inflight) break;
+                spins = 0;
+            }
+        }
+        if (rc) break;
+        if ((enq & 255) == 0) {     // authoritative check now and then
+            rc = read_state(); if (rc) break;
+            if (h.all_done) break;
+        }
+    }
+    if (!rc) rc = read_state();
+    if (!rc) {
+        int longest = 0;
+        for (int j = 0; j < K; j++) {
+            if (ret) ret[j] = lcg_code(h.stop[j]);
+            if (iterations) iterations[j] = h.t[j];
+            if (residual) residual[j] = h.residual[j];
+            if (h.t[j] > h.t[longest]) longest = j;
+        }
+        c.last_iters = h.t[longest];
+        c.last_residual = h.residual[longest];
+        c.last_ax_calls = 0; c.last_ax_mean_us = 0.0; c.prof_pending = 0;
+    } else {
+        (void)hipStreamSynchronize(c.stream);       // nothing of this solve may still run on vectors that go back to the pool
+        (void)hipGetLastError();
+    }
+    const int rc2 = hb.close(c.stream);
+    return rc ? rc : rc2;
+}
+
+template <bool PCG>
+static int solve_multi(const char *entry, lcg_hip_csr *A, int k, double *M, const double *B, const lcg_para *param, int *ret, int *iterations,
+                       double *residual, int mem)
+{
+    TRY(multi_args(entry, k, M, B));
+    TRY(multi_handle(entry, A));
+    if (A->n_rows != A->n_cols) { ctx().err = std::string(entry) + ": the matrix is not square"; return LCG_HIP_E_ARG; }
+    if (mem != LCG_HIP_MEM_HOST && mem != LCG_HIP_MEM_DEVICE) { ctx().err = std::string(entry) + ": mem is neither LCG_HIP_MEM_HOST nor LCG_HIP_MEM_DEVICE"; return LCG_HIP_E_ARG; }
+    const lcg_para p = param ? *param : lcg_hip_default_parameters();
+    if (p.max_iterations < 0) return LCG_INVILAD_MAX_ITERATIONS;            // lcg.cpp:150-155
+    if (p.epsilon <= 0.0 || p.epsilon >= 1.0) return LCG_INVILAD_EPSILON;
+    if (PCG && A->invdiag == nullptr) return LCG_NULL_PRECONDITION_MATRIX;  // lcg_hip_csr_build_jacobi has not run
+    TRY(ensure_init());
+    if (k == 2) return run_multi<2, PCG>(A, M, B, p, ret, iterations, residual, mem);
+    if (k == 4) return run_multi<4, PCG>(A, M, B, p, ret, iterations, residual, mem);
+    return run_multi<8, PCG>(A, M, B, p, ret, iterations, residual, mem);
+}
+
+} // namespace
+} // namespace lcgh
+
+using namespace lcgh;
+
+extern "C" {
+
+int lcg_hip_lcg_multi(lcg_hip_csr_t A, int k, double *M, const double *B, const lcg_para *param, int *ret, int *iterations,
+                      double *residual, int mem)
+{
+    NOT_DENSE(A, LCG_HIP_E_ARG);
+    return solve_multi<false>("lcg_hip_lcg_multi", A, k, M, B, param, ret, iterations, residual, mem);
+}
+
+int lcg_hip_lpcg_multi(lcg_hip_csr_t A, int k, double *M, const double *B, const lcg_para *param, int *ret, int *iterations,
+                       double *residual, int mem)
+{
+    NOT_DENSE(A, LCG_HIP_E_ARG);
+    return solve_multi<true>("lcg_hip_lpcg_multi", A, k, M, B, param, ret, iterations, residual, mem);
+}
+
+} // extern "C"
