@@ -4,7 +4,14 @@ against the exact sums and per-row rounding bounds of tests/exact_ref.py.
 Shapes: the smallest at which the mapping can go wrong -- rows around the 64-row block, a second LDS window (one row of 3000
 entries among rows of 3), empty rows (the first and the last among them), rectangular matrices, and mean row lengths of 100 and
 300 entries, where the kernel gives a row 16 and 64 lanes instead of 4.  Y is filled with NaN before every call (an unwritten row
-fails)."""
+fails).
+
+The edges of the MM_CH = 2304-entry LDS window are pinned by the shapes of window_shapes(): a block slice of exactly 2304 and
+2304 +- 1 entries, a slice that starts at rowptr % 4 = 1, 2, 3 with a row ending exactly at the window's end, a row over three
+windows at R = 16 and at R = 64, a single-row matrix (R = 4, one row in the block), partial last blocks at R = 16 and R = 4.
+NaN and +-Inf in a few rows of X: test_nonfinite_x_stays_in_its_rows_of_every_column; the folded dots at R = 16 and R = 4:
+test_the_dot_carrying_form[band30_8197 / band140_2051]; adopted arrays with poison behind them: test_arrays_the_caller_keeps.  The
+batched loops' branches are pinned by tests/test_gpu_multi_edges.py."""
 import ctypes as C
 import zlib
 
@@ -13,6 +20,7 @@ import pytest
 import scipy.sparse as sp
 
 import exact_ref as X
+import multi_cases as mc
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -73,6 +81,41 @@ def shapes():
     out["rect_77x200"] = (77, 200) + _random_rows(rng, 77, 200, rng.integers(0, 12, 77))
     out["mean100"] = (70, 500) + _random_rows(rng, 70, 500, rng.integers(60, 141, 70))        # 16 lanes per row
     out["mean300"] = (37, 5000) + _random_rows(rng, 37, 5000, rng.integers(1, 600, 37) + 150)  # 64 lanes per row, rows over two windows
+    out.update(window_shapes(rng))
+    return out
+
+
+MM_CH = 2304        # csr_multi.hip: entries per LDS window
+# the class of rows_per_block each window shape is there for (the product sets no kernel name: the mean row length is the statement)
+WINDOW_CLASS = {"win_exact": 64, "win_plus1": 64, "win_minus1": 64, "win_row_end_1": 64, "win_row_end_2": 64, "win_row_end_3": 64,
+                "three_windows": 16, "three_windows_r64": 64, "one_row": 4, "r4_partial": 4, "r16_partial": 16}
+
+
+def window_shapes(rng):
+    """Shapes at the edges of the LDS window (a block's slice of col / val is staged from base = rowptr[row0] & ~3, MM_CH entries at
+    a time)."""
+    out = {}
+    for name, mid in (("win_exact", 36), ("win_plus1", 37), ("win_minus1", 35)):
+        lens = np.full(64, 36); lens[31] = mid                  # one block whose slice is MM_CH, MM_CH + 1, MM_CH - 1 entries
+        out[name] = (64, 200) + _random_rows(rng, 64, 200, lens)
+    for r in (1, 2, 3):
+        # block 1 starts at rowptr = 256 + r (base = 256); its row 47 ends exactly at base + MM_CH, sixteen more rows follow
+        lens = np.concatenate([[4 + r], np.full(63, 4), np.full(47, 48), [48 - r], np.full(16, 40)])
+        rp, col = _random_rows(rng, 128, 300, lens)
+        assert rp[64] % 4 == r and rp[64 + 48] == (rp[64] & ~3) + MM_CH and rp[-1] > rp[64 + 48]
+        out[f"win_row_end_{r}"] = (128, 300, rp, col)
+    lens = np.full(64, 2); lens[21] = 5000                      # mean 80: R = 16, the long row's 16 lanes walk three windows
+    out["three_windows"] = (64, 6000) + _random_rows(rng, 64, 6000, lens)
+    lens = np.full(128, 2); lens[85] = 5000                     # mean 41: R = 64, T = 4
+    out["three_windows_r64"] = (128, 6000) + _random_rows(rng, 128, 6000, lens)
+    out["one_row"] = (1, 6000) + _random_rows(rng, 1, 6000, np.array([5000]))       # R = 4, nrows = 1, three windows
+    lens = rng.integers(100, 400, 21); lens[8:12] = (700, 650, 720, 690)            # 4 q + 1 rows; one block's slice is 2760 entries
+    out["r4_partial"] = (21, 3000) + _random_rows(rng, 21, 3000, lens)
+    out["r16_partial"] = (37, 500) + _random_rows(rng, 37, 500, rng.integers(60, 141, 37))     # 16 q + 5 rows
+    for name, R in WINDOW_CLASS.items():
+        n, _, rp, _ = out[name]
+        assert mc.rows_per_block(rp[-1] / n) == R, (name, rp[-1] / n)
+    assert any(out["r4_partial"][2][min(21, r0 + 4)] - out["r4_partial"][2][r0] > MM_CH for r0 in range(0, 21, 4))
     return out
 
 
@@ -139,9 +182,20 @@ def _laplace_many_blocks():
     return 190 * 190, 190 * 190, rp, col
 
 
-@pytest.mark.parametrize("name", ["n1", "n65", "n1000", "empty_rows", "arrow", "mean100", "mean300", "many_blocks"])
+def _band_many_blocks(n, h, R):
+    """The dense band of multi_cases at the smallest size with 513 row blocks of R rows: the fold at R = 16 and R = 4."""
+    rp, col, _ = mc.band_pattern(n, h)
+    assert mc.rows_per_block(rp[-1] / n) == R and -(-n // R) == mc.MM_MG + 1
+    return n, n, rp, col
+
+
+MANY_BLOCKS = {"many_blocks": _laplace_many_blocks, "band30_8197": lambda: _band_many_blocks(8197, 30, 16),
+               "band140_2051": lambda: _band_many_blocks(2051, 140, 4)}
+
+
+@pytest.mark.parametrize("name", ["n1", "n65", "n1000", "empty_rows", "arrow", "mean100", "mean300", "many_blocks", "band30_8197", "band140_2051"])
 def test_the_dot_carrying_form(api, lib, name):
-    n, nc, rp, col = _laplace_many_blocks() if name == "many_blocks" else SHAPES[name]
+    n, nc, rp, col = MANY_BLOCKS[name]() if name in MANY_BLOCKS else SHAPES[name]
     rng = np.random.default_rng(11)
     val = rng.standard_normal(int(rp[-1]))
     A = api.CsrMatrix.from_csr(rp, col, val, n_cols=nc)
@@ -164,26 +218,65 @@ def test_the_dot_carrying_form(api, lib, name):
 
 
 def test_arrays_the_caller_keeps(api, lib):
-    """Adopted device arrays without slack behind them and with an 8-byte-aligned base: read entry by entry, never past the end."""
-    n, nc, rp, col = SHAPES["n257"]
-    rng = np.random.default_rng(3)
-    nnz = int(rp[-1])
-    val = rng.standard_normal(nnz)
-    rpd = dev(rp)
-    cold = dev(np.concatenate([[0], col]).astype(np.int32))[1:]         # base 4 mod 16
-    vald = dev(np.concatenate([[0.0], val]))[1:]                        # base 8 mod 16
-    h = C.c_void_p()
-    assert lib.lcg_hip_csr_create(C.byref(h), n, nc, nnz, rpd.data_ptr(), cold.data_ptr(), vald.data_ptr(), 0, 1, 1) == 0
+    """Adopted device arrays with an 8-byte-aligned base: read entry by entry, never past the slice.  The arrays are views into
+    longer tensors of the test's own: behind col lie zeros, behind val NaN, so an entry read past a slice and used shows as NaN in Y
+    (row 0 of X is finite) while no address outside the allocation is touched.  And Y is the copied matrix's Y bit for bit: the
+    order of a sum is the matrix's alone."""
+    for name in ("n257", "arrow", "three_windows", "three_windows_r64", "r16_partial", "r4_partial"):
+        n, nc, rp, col = SHAPES[name]
+        rng = np.random.default_rng(3)
+        nnz = int(rp[-1])
+        val = rng.standard_normal(nnz)
+        tail = 64 if name != "n257" else 0          # (n257: no slack at all behind the arrays, as before)
+        rpd = dev(rp)
+        cold = dev(np.concatenate([[0], col, np.zeros(tail)]).astype(np.int32))[1:1 + nnz]       # base 4 mod 16
+        vald = dev(np.concatenate([[0.0], val, np.full(tail, np.nan)]))[1:1 + nnz]              # base 8 mod 16
+        assert cold.data_ptr() % 16 == 4 and vald.data_ptr() % 16 == 8
+        h = C.c_void_p()
+        assert lib.lcg_hip_csr_create(C.byref(h), n, nc, nnz, rpd.data_ptr(), cold.data_ptr(), vald.data_ptr(), 0, 1, 1) == 0
+        A = api.CsrMatrix.from_csr(rp, col, val, n_cols=nc)
+        for k in KS:
+            Xh = rng.standard_normal((nc, k))
+            Xd = dev(Xh)
+            Y = torch.full((n, k), np.nan, dtype=torch.float64, device="cuda")
+            assert lib.lcg_hip_spmm(h, k, Xd.data_ptr(), Y.data_ptr()) == 0
+            torch.cuda.synchronize()
+            Yh = Y.cpu().numpy()
+            for j in range(k):
+                X.assert_rows(np.ascontiguousarray(Yh[:, j]), rp, col, val, Xh[:, j], ("adopted", name, k, j))
+            assert np.array_equal(bits(Yh), bits(spmm(lib, A, k, Xh, n))), (name, k)
+        lib.lcg_hip_csr_destroy(h)
+        A.destroy()
+
+
+@pytest.mark.parametrize("name", ["n1000", "r16_partial", "r4_partial", "three_windows", "three_windows_r64", "one_row"])
+def test_nonfinite_x_stays_in_its_rows_of_every_column(api, lib, name):
+    """NaN, +Inf and -Inf in X at row 0, the last row and a few referenced rows (explicitly stored zeros in val), in one column and
+    in all of them: a row of Y that references none of them is, bit for bit, the row of the run with those entries 0 -- no lane past
+    the window (which re-reads its first unit), no lane past nrows and no reuse of the staging buffer leaks them -- and a row that
+    does has the category of an ordered sum.  One shape per R class, the rows over three windows and the single row."""
+    from test_gpu_exact_products import _nonfinite_check, _specials
+    n, nc, rp, col = SHAPES[name]
+    rng = np.random.default_rng(zlib.crc32(name.encode()) + 1)
+    val = rng.standard_normal(int(rp[-1]))
+    val[rng.random(len(val)) < 0.05] = 0.0
+    A = api.CsrMatrix.from_csr(rp, col, val, n_cols=nc)
+    cs, kinds = _specials(rng, col, nc)
     for k in KS:
         Xh = rng.standard_normal((nc, k))
-        Xd = dev(Xh)
-        Y = torch.full((n, k), np.nan, dtype=torch.float64, device="cuda")
-        assert lib.lcg_hip_spmm(h, k, Xd.data_ptr(), Y.data_ptr()) == 0
-        torch.cuda.synchronize()
-        Yh = Y.cpu().numpy()
+        X0 = Xh.copy(); X0[cs, :] = 0.0
+        Y0 = spmm(lib, A, k, X0, n)
+        jc = k - 1
+        X1 = X0.copy(); X1[cs, jc] = kinds              # one column
+        Xa = X0.copy(); Xa[cs, :] = kinds[:, None]      # all columns
+        Y1, Ya = spmm(lib, A, k, X1, n), spmm(lib, A, k, Xa, n)
         for j in range(k):
-            X.assert_rows(np.ascontiguousarray(Yh[:, j]), rp, col, val, Xh[:, j], ("adopted", k, j))
-    lib.lcg_hip_csr_destroy(h)
+            _nonfinite_check(np.ascontiguousarray(Ya[:, j]), np.ascontiguousarray(Y0[:, j]), rp, col, val, Xa[:, j], cs, (name, k, j, "all"))
+            if j == jc:
+                _nonfinite_check(np.ascontiguousarray(Y1[:, j]), np.ascontiguousarray(Y0[:, j]), rp, col, val, X1[:, j], cs, (name, k, j, "one"))
+            else:
+                assert np.array_equal(bits(Y1[:, j]), bits(Y0[:, j])), (name, k, j)     # the untouched columns: the clean run's bits
+    A.destroy()
 
 
 def test_handles_this_path_does_not_serve(api, lib):

@@ -5,12 +5,17 @@ stays in its column, stopped columns that are final, columns that do not depend 
 Bands.  Capped at 25 iterations: conftest.check_converged_run's band for a capped iterate of a recurrence that IS the oracle's
 (max(floor 1e-9, 50 x the oracle's own response to 1-ulp changes of b at that count)), without its third term (a quarter of the
 error left), which 25 iterations into a solve would allow anything.  Converged (abs_diff = 1, epsilon = 1e-10): SURVEY section 8c's
-parity statement per column -- count within 3 of the oracle's, |x - x_oracle| <= 1e-9 |x_oracle|, reported residual <= epsilon."""
-import ctypes as C
+parity statement per column -- count within 3 of the oracle's, |x - x_oracle| <= 1e-9 |x_oracle|, reported residual <= epsilon.
 
+These two systems run the loops at R = 64 rows per block, without the fold, in one stride of a vector pass and under abs_diff = 1
+only.  The other branches -- the relative rule and m.m, the folded d.Ad, R = 16 and R = 4, a second stride, n.k >= 2^20, n = 1, 2, 3,
+non-zero guesses, both "already optimised" criteria -- are pinned by tests/test_gpu_multi_edges.py on the systems of
+tests/multi_cases.py, which also holds the driver multi()."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
+
+from multi_cases import multi
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -59,26 +64,6 @@ def columns(n, b, k):
     if k == 2:
         cols = [cols[0], cols[2]]
     return np.ascontiguousarray(np.stack(cols[:k], axis=1))
-
-
-def multi(lib, api, sid, A, M, B, mem="device", **para):
-    """One batched solve: (rc, ret[k], iterations[k], residual[k], M afterwards).  M, B: (n, k) numpy arrays."""
-    k = B.shape[1]
-    p = api.lcg_default_parameters(**para)
-    ret = (C.c_int * k)(*([99] * k)); its = (C.c_int * k)(*([-1] * k)); res = (C.c_double * k)()
-    fn = lib.lcg_hip_lpcg_multi if sid == PCG else lib.lcg_hip_lcg_multi
-    if mem == "device":
-        Md, Bd = torch.from_numpy(M.copy()).cuda(), torch.from_numpy(B).cuda()
-        rc = fn(A.h, k, Md.data_ptr(), Bd.data_ptr(), C.byref(p), ret, its, res, 1)
-        torch.cuda.synchronize()
-        out = Md.cpu().numpy()
-    else:
-        raw = np.zeros(M.size + 2); off = 0 if raw.ctypes.data % 16 == 0 else 1
-        out = raw[off:off + M.size].reshape(M.shape); out[:] = M
-        rawb = np.zeros(B.size + 2); offb = 0 if rawb.ctypes.data % 16 == 0 else 1
-        Bh = rawb[offb:offb + B.size].reshape(B.shape); Bh[:] = B
-        rc = fn(A.h, k, out.ctypes.data, Bh.ctypes.data, C.byref(p), ret, its, res, 0)
-    return rc, list(ret), list(its), list(res), out
 
 
 _ORACLE = {}
