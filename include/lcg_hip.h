@@ -585,6 +585,23 @@ int lcg_hip_lcg_multi(lcg_hip_csr_t A, int k, double *M, const double *B, const 
                       int *ret, int *iterations, double *residual, int mem);
 int lcg_hip_lpcg_multi(lcg_hip_csr_t A, int k, double *M, const double *B, const lcg_para *param,
                        int *ret, int *iterations, double *residual, int mem);
+/* The handle's IC(0) / ILU(0) factor applied to a block of k = 2, 4 or 8 vectors (lcg_hip_spmm's layout): which = 0 L^-1,
+ * 1 L^-T (IC) / U^-1 (ILU), 2 both.  The apply follows lcg_hip_csr_{ic0,ilu0}_set_sweeps: exact level-scheduled solves, or s
+ * Jacobi sweeps per triangle, each sweep ONE launch that reads the triangle once for all k columns.  Column j has the bits of
+ * lcg_hip_ic0_solve / lcg_hip_ilu0_solve on column j alone, whatever the other columns hold (NaN and Inf included), whatever k
+ * is, from call to call.  The k-wide work vectors belong to the factor: the first call at a k larger than any before may
+ * allocate and wait, later ones only launch; lcg_hip_csr_{ic0,ilu0}_info's byte count includes them.  LCG_HIP_E_ARG (bad k, null
+ * or misaligned block, complex / complex64 / dense / sharded handle, no factor, which outside 0..2, X and Y overlapping) before
+ * the device is touched, Y untouched. */
+int lcg_hip_ic0_solve_multi (lcg_hip_csr_t A, int k, int which, const double *X, double *Y);
+int lcg_hip_ilu0_solve_multi(lcg_hip_csr_t A, int k, int which, const double *X, double *Y);
+enum { LCG_HIP_M_JACOBI = 0, LCG_HIP_M_IC0 = 1, LCG_HIP_M_ILU0 = 2 };
+/* lcg_hip_lpcg_multi with the preconditioner named: LCG_HIP_M_JACOBI is lcg_hip_lpcg_multi itself, bit for bit; LCG_HIP_M_IC0 /
+ * LCG_HIP_M_ILU0 apply the handle's factor k wide at its sweeps setting, between the update pass and the pass of the sums (one
+ * apply per iteration for all columns; its launches count as vector passes in lcg_hip_last_launches).  Any other precond:
+ * LCG_HIP_E_ARG; no factor (or no Jacobi diagonal): LCG_NULL_PRECONDITION_MATRIX.  Everything else as lcg_hip_lpcg_multi. */
+int lcg_hip_lpcg_multi_m(lcg_hip_csr_t A, int k, int precond, double *M, const double *B, const lcg_para *param,
+                         int *ret, int *iterations, double *residual, int mem);
 /* y = op(A).x for a complex64 handle (layout / conjugate as lcg_hip_spmv_op: A, A^T, conj(A), A^H), summed in fp32 as cuSPARSE's
  * CUDA_C_32F (clcg_cudaf.cu's Afp), each row in one fixed order: bit-identical from call to call.  k_c64_rows (W lanes per row,
  * each pair of entries one 16-byte value load and one 8-byte column load, row ends masked by selects) and, for rows of more than max(256, 64 W) entries, k_c64_long (one workgroup per row);

@@ -215,6 +215,12 @@ class CsrMatrix:
         else:
             _chk(L.load().lcg_hip_ic0_solve(self.h, which, _ptr(x)[0], _ptr(y)[0]), "ic0_solve")
 
+    def ic0_solve_multi(self, X, Y, which=2):
+        """ic0_solve for the k = 2, 4 or 8 columns of X at once (lcg_hip_ic0_solve_multi): X, Y (n, k) C-contiguous float64 CUDA
+        tensors, 16-byte aligned.  Column j has the bits of ic0_solve on column j; the factor is read once for all of them."""
+        k = _block_k(X, Y)
+        _chk(L.load().lcg_hip_ic0_solve_multi(self.h, k, which, _ptr(X)[0], _ptr(Y)[0]), "ic0_solve_multi")
+
     # -- ILU(0) preconditioner (csr_ilu0.hip) -----------------------------------------------
     def build_ilu0(self):
         """Factor A ~ L.U (unit lower L) with zero fill on the device, fp64 and complex128 matrices; pass "lcg_hip_ilu0_mx" /
@@ -258,6 +264,11 @@ class CsrMatrix:
     def ilu0_solve(self, x, y, which=2):
         """y = L^-1 x (which 0), U^-1 x (1) or U^-1 L^-1 x (2); device tensors, on the library's stream."""
         _chk(L.load().lcg_hip_ilu0_solve(self.h, which, _ptr(x)[0], _ptr(y)[0]), "ilu0_solve")
+
+    def ilu0_solve_multi(self, X, Y, which=2):
+        """ilu0_solve for the k = 2, 4 or 8 columns of X at once (lcg_hip_ilu0_solve_multi); as ic0_solve_multi."""
+        k = _block_k(X, Y)
+        _chk(L.load().lcg_hip_ilu0_solve_multi(self.h, k, which, _ptr(X)[0], _ptr(Y)[0]), "ilu0_solve_multi")
 
     def spmv(self, x, y):
         _chk(L.load().lcg_hip_spmv(self.h, _ptr(x)[0], _ptr(y)[0]), "spmv")
@@ -459,7 +470,10 @@ def _block_k(*blocks):
     return k
 
 
-def _multi(name, A, M, B, param):
+PRECONDS = {"jacobi": 0, "ic0": 1, "ilu0": 2}       # LCG_HIP_M_JACOBI, LCG_HIP_M_IC0, LCG_HIP_M_ILU0
+
+
+def _multi(name, A, M, B, param, precond=None):
     lib = L.load()
     k = _block_k(M, B)
     if tuple(M.shape) != tuple(B.shape):
@@ -468,7 +482,8 @@ def _multi(name, A, M, B, param):
     if mem != mem_b:
         raise ValueError("M and B must live in the same memory space")
     ret = (C.c_int * k)(); its = (C.c_int * k)(); res = (C.c_double * k)()
-    rc = getattr(lib, name)(_instance(A), k, pm, pb, C.byref(param) if param is not None else None, ret, its, res, mem)
+    lead = (_instance(A), k) if precond is None else (_instance(A), k, precond)
+    rc = getattr(lib, name)(*lead, pm, pb, C.byref(param) if param is not None else None, ret, its, res, mem)
     _chk(rc, name)
     if rc:
         raise LcgHipError(f"{name}: rc={rc}")
@@ -481,9 +496,15 @@ def lcg_multi(A, M, B, param) -> list:
     return _multi("lcg_hip_lcg_multi", A, M, B, param)
 
 
-def lpcg_multi(A, M, B, param) -> list:
-    """Batched PCG with the built-in Jacobi (lcg_hip_lpcg_multi; A.build_jacobi() first).  As lcg_multi."""
-    return _multi("lcg_hip_lpcg_multi", A, M, B, param)
+def lpcg_multi(A, M, B, param, precond="jacobi") -> list:
+    """Batched PCG.  precond "jacobi": the built-in Jacobi (lcg_hip_lpcg_multi; A.build_jacobi() first); "ic0" / "ilu0": the
+    handle's factor (A.build_ic0() / A.build_ilu0() first) applied to all columns at once at its sweeps setting
+    (lcg_hip_lpcg_multi_m).  As lcg_multi."""
+    if precond not in PRECONDS:
+        raise ValueError('precond is "jacobi", "ic0" or "ilu0"')
+    if precond == "jacobi":
+        return _multi("lcg_hip_lpcg_multi", A, M, B, param)
+    return _multi("lcg_hip_lpcg_multi_m", A, M, B, param, PRECONDS[precond])
 
 
 def lcgs(Afp, Pfp, m, B, n_size, param, instance, *workspaces) -> SolveInfo:

@@ -251,6 +251,7 @@ void tri_factor_free(TriFactor *&F)
     if (F->tmp) hipFree(F->tmp);
     if (F->w) hipFree(F->w);
     for (double *&p : F->sw) if (p) hipFree(p);
+    for (double *&p : F->mw) if (p) hipFree(p);
     if (F->zp) hipFree(F->zp);
     delete F;
     F = nullptr;
@@ -318,6 +319,14 @@ int tri_call(lcg_hip_csr *A, TriSlot slot, const char *name, const char *builder
     return rc ? rc : tri_apply(F, which, x, y, ctx().stream, ax_flag(ctx()));
 }
 
+int tri_apply_launches(const TriFactor *F, int which)
+{
+    int l = 0;
+    if (which != 1) l += F->sweeps > 0 ? tri_sweep_launches(F->dg[0], F->sweeps) : (int)F->fw.segs.size();
+    if (which != 0) l += F->sweeps > 0 ? tri_sweep_launches(F->dg[1], F->sweeps) : (int)F->bw.segs.size();
+    return l;
+}
+
 int tri_info(lcg_hip_csr *A, TriSlot slot, int *levels_lo, int *levels_up, int *launches_per_apply, int *zero_pivot, double *build_ms,
              int64_t *bytes)
 {
@@ -325,14 +334,13 @@ int tri_info(lcg_hip_csr *A, TriSlot slot, int *levels_lo, int *levels_up, int *
     const TriFactor *F = A->*slot;
     if (levels_lo) *levels_lo = F->fw.levels;
     if (levels_up) *levels_up = F->bw.levels;
-    if (launches_per_apply)
-        *launches_per_apply = F->sweeps > 0 ? tri_sweep_launches(F->dg[0], F->sweeps) + tri_sweep_launches(F->dg[1], F->sweeps)
-                                            : (int)(F->fw.segs.size() + F->bw.segs.size());
+    if (launches_per_apply) *launches_per_apply = tri_apply_launches(F, 2);
     if (zero_pivot) *zero_pivot = F->zero_pivot;
     if (build_ms) *build_ms = F->build_ms;
     if (bytes) {
         const int64_t vw = (int64_t)value_bytes(F), n = F->n;
-        const int vectors = (F->tmp != nullptr) + (F->w != nullptr) + (F->sw[0] != nullptr) + (F->sw[1] != nullptr);
+        const int vectors = (F->tmp != nullptr) + (F->w != nullptr) + (F->sw[0] != nullptr) + (F->sw[1] != nullptr)
+                          + F->mk * ((F->mw[0] != nullptr) + (F->mw[1] != nullptr) + (F->mw[2] != nullptr));      // (a k-wide one counts k)
         *bytes = 2 * 4 * (n + 1) + (4 + vw) * ((int64_t)F->lo.nnz + (int64_t)F->up.nnz)      // the two triangles
                + 2 * 4 * n + 4 * ((int64_t)F->fw.levels + F->bw.levels + 2)                   // level orders
                + vectors * vw * n + 4;                                                        // work and sweep vectors held, pivot word

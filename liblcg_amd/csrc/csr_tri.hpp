@@ -18,6 +18,9 @@ constexpr int IC_WG = 1024;     // threads of a narrow-group launch = widest lev
 constexpr int IC_WB = 256;      // threads per block of a wide-level launch
 constexpr int IC_SR = 256;      // rows of a sweep's workgroup = its threads
 constexpr int IC_SCH = 2048;    // its LDS window in entries (8 per row; 24 KiB with 8-byte values, 40 KiB with 16-byte ones)
+constexpr int IC_MT = 256;      // threads of a batched sweep's workgroup (csr_tri_multi.hip): k / 2 neighbouring lanes per row
+constexpr int IC_MCH = 2048;    // its LDS window in entries (24 KiB: six workgroups per CU; 8, 16, 32 per row for k = 2, 4, 8)
+constexpr int ic_mrows(int k) { return IC_MT * 2 / k; }    // rows of its workgroup: 256, 128, 64 for k = 2, 4, 8
 
 struct IcSeg { int l0, l1; bool narrow; };      // levels [l0, l1): one launch
 struct IcTri {                                  // one triangle's schedule
@@ -42,6 +45,8 @@ struct TriFactor {
     double *w = nullptr;        // ILU(0) only: U^-1 L^-1 x of the right-preconditioned product (lcg_hip_csr_ax_ilu0)
     int sweeps = 0;             // 0: exact level-scheduled solves; k >= 1: k Jacobi sweeps per triangle
     double *sw[2] = {nullptr, nullptr};     // the sweeps' two intermediate vectors (n values each, held while sweeps >= 1)
+    double *mw[3] = {nullptr, nullptr, nullptr};    // batched applies: lo^-1 X and the two sweep vectors, n * mk doubles each (tri_multi_reserve)
+    int mk = 0;                 // the largest k a batched apply has asked for so far
     int *zp = nullptr;          // device: smallest row whose pivot failed (INT_MAX: none)
     int zero_pivot = -1;
     int max_merged = IC_WG;     // widest level a narrow group takes (lcg_hip_csr_{ic0,ilu0}_schedule_for_test)
@@ -196,6 +201,12 @@ int tri_apply(const TriFactor *F, int which, const double *x, double *y, hipStre
 int tri_call(lcg_hip_csr *A, TriSlot slot, const char *name, const char *builder, bool cplx, bool c64, int which, const double *x,
              double *y, long n_size);
 void park(int rc);
+// batched apply (csr_tri_multi.hip): a block of k = 2, 4, 8 vectors in multi.hpp's layout, column j with the bits of tri_apply on
+// column j alone.  tri_multi_reserve: the factor's k-wide work vectors for such an apply (may allocate and wait; a call that finds
+// them does neither) -- before tri_apply_multi, which only launches.  tri_apply_launches: launches of one apply of `which`.
+int tri_multi_reserve(TriFactor *F, int k, int which);
+int tri_apply_multi(const TriFactor *F, int k, int which, const double *X, double *Y, hipStream_t s, const int *done);
+int tri_apply_launches(const TriFactor *F, int which);
 // the bodies of lcg_hip_csr_{ic0,ilu0}_info / _set_sweeps / _get_sweeps / _schedule_for_test / _factor (`entry`: the exported
 // name, `builders`: the build entries a "no factor" message names)
 int tri_info(lcg_hip_csr *A, TriSlot slot, int *levels_lo, int *levels_up, int *launches_per_apply, int *zero_pivot, double *build_ms,

@@ -1,4 +1,5 @@
-// solvers_multi.hip -- batched CG and PCG (built-in Jacobi) over k = 2, 4, 8 right-hand sides: lcg_hip_lcg_multi, lcg_hip_lpcg_multi.
+// solvers_multi.hip -- batched CG and PCG over k = 2, 4, 8 right-hand sides: lcg_hip_lcg_multi, lcg_hip_lpcg_multi (the built-in
+// Jacobi), lcg_hip_lpcg_multi_m (Jacobi, or the handle's IC(0) / ILU(0) factor applied k wide: csr_tri_multi.hip).
 //
 // Each column runs the reference's own recurrence as if it were alone (lcg.cpp:143-274, 293-434): its own alpha, beta, rho, its own
 // residual under the same stop rule, its own "already optimised" test, NaN scan, count and return code.  What the columns share is
@@ -10,6 +11,10 @@
 // k_vecf (devcommon.hpp): every block adds the previous pass's partial sums in msum's fixed order, runs the step for all columns on
 // a copy of MState in LDS, and block 0 commits the copy to the other buffer of a pair.
 //
+// With a factor as M the multiply leaves the update pass:
+//     A.d carrying d.Ad  |  [alpha] m += a d, r -= a Ad  |  z = M^-1 r (the apply's launches)  |  m.m, r.r, z.r, NaN  |  [close] d = z + b d
+// The apply forms z for every column, stopped ones too (nothing reads theirs); every one of its launches honours all_done.
+//
 // Frozen columns: once a column has stopped (converged, NaN, already optimised) its column of the iterate and of g / r, z, d is never
 // written again -- a SELECT on the column's stop word, not a multiplication by zero, so a stopped NaN column leaks into nothing
 // (its sums are computed apart and never read).  The product still forms such a column's A.d, which nothing reads.  When every column
@@ -20,6 +25,7 @@
 // sums are added in a fixed order (lane's own in index order, lanes of a wavefront by xor-butterfly, wavefronts in order, blocks in
 // order): the same bits whatever the other columns hold, from call to call.
 #include "multi.hpp"
+#include "csr_tri.hpp"
 
 namespace lcgh {
 namespace {
@@ -192,6 +198,44 @@ struct MOpPcgUpdate {   // m += a d; r -= a Ad; z = r / diag; m.m, r.r, z.r, NaN
         acc[0] += mv * mv; acc[1] += rv * rv; acc[2] += zv * rv; acc[3] += nan2(mv);
     }
 };
+// a factor as M: the update and the sums are two passes with the apply's launches between them
+struct MOpFRes {        // r = B - Ad                                      lcg.cpp:317-321
+    static constexpr int NS = 0;
+    const double *Ad, *B; double *r;
+    __device__ void prep(const MState &, int) {}
+    __device__ void apply(long e, long, bool r0, bool r1, m2d *) { st2(r, e, ld2(B, e) - ld2(Ad, e), r0, r1); }
+};
+struct MOpFInit {       // d = z; m.m, r.r, z.r                            lcg.cpp:322-339
+    static constexpr int NS = 3;
+    const double *m, *r, *z; double *d;
+    __device__ void prep(const MState &, int) {}
+    __device__ void apply(long e, long, bool r0, bool r1, m2d *acc)
+    {
+        const m2d mv = ld2(m, e), rv = ld2(r, e), zv = ld2(z, e);
+        st2(d, e, zv, r0, r1);
+        acc[0] += mv * mv; acc[1] += rv * rv; acc[2] += zv * rv;
+    }
+};
+struct MOpFUpdate {     // m += a d; r -= a Ad                             lcg.cpp:392-399
+    static constexpr int NS = 0;
+    double *m, *r; const double *d, *Ad; m2d ak;
+    __device__ void prep(const MState &L, int c0) { ak.x = L.ak[c0]; ak.y = L.ak[c0 + 1]; }
+    __device__ void apply(long e, long, bool r0, bool r1, m2d *)
+    {
+        st2(m, e, ld2(m, e) + ak * ld2(d, e), r0, r1);
+        st2(r, e, ld2(r, e) - ak * ld2(Ad, e), r0, r1);
+    }
+};
+struct MOpFSums {       // m.m, r.r, z.r, NaN                              lcg.cpp:401-414
+    static constexpr int NS = 4;
+    const double *m, *r, *z;
+    __device__ void prep(const MState &, int) {}
+    __device__ void apply(long e, long, bool, bool, m2d *acc)
+    {
+        const m2d mv = ld2(m, e), rv = ld2(r, e), zv = ld2(z, e);
+        acc[0] += mv * mv; acc[1] += rv * rv; acc[2] += zv * rv; acc[3] += nan2(mv);
+    }
+};
 struct MOpCgDir {       // d = b d - g                                     lcg.cpp:259-263
     static constexpr int NS = 0;
     double *d; const double *g; m2d bk;
@@ -303,8 +347,9 @@ static int lcg_code(int stop)
 }
 
 template <int K, bool PCG>
-static int run_multi(lcg_hip_csr *A, double *M, const double *B, const lcg_para &p, int *ret, int *iterations, double *residual, int mem)
-{
+static int run_multi(lcg_hip_csr *A, const TriFactor *F, double *M, const double *B, const lcg_para &p, int *ret, int *iterations,
+                     double *residual, int mem)
+{   // F: the factor that is M (PCG only; its k-wide work vectors reserved by the caller), nullptr: the built-in Jacobi
     Ctx &c = ctx();
     const int n = A->n_rows;
     const size_t nb = sizeof(double) * (size_t)n * K;
@@ -333,14 +378,26 @@ static int run_multi(lcg_hip_csr *A, double *M, const double *B, const lcg_para 
     // setup (lcg.cpp:168-203, 314-359): A.m for the guess, the first residual and direction, the verdict "already optimised"
     c.cnt_ax++;
     TRY(spmm_launch(k.P, K, M, Ad, c.stream, nullptr));
-    if (PCG) TRY((k.template pass<MFinNone<K>, MOpPcgInit, true>(MFinNone<K>{}, MOpPcgInit{Ad, B, M, A->invdiag, g, z, d}, nullptr, 0)));
+    const int m_launches = PCG && F ? tri_apply_launches(F, 2) : 0;        // counted as vector passes (lcg_hip_last_launches)
+    if (PCG && F) {
+        TRY((k.template pass<MFinNone<K>, MOpFRes, true>(MFinNone<K>{}, MOpFRes{Ad, B, g}, nullptr, 0)));
+        c.cnt_vec += m_launches;
+        TRY(tri_apply_multi(F, K, 2, g, z, c.stream, nullptr));
+        TRY((k.template pass<MFinNone<K>, MOpFInit, true>(MFinNone<K>{}, MOpFInit{M, g, z, d}, nullptr, 0)));
+    } else if (PCG) TRY((k.template pass<MFinNone<K>, MOpPcgInit, true>(MFinNone<K>{}, MOpPcgInit{Ad, B, M, A->invdiag, g, z, d}, nullptr, 0)));
     else TRY((k.template pass<MFinNone<K>, MOpCgInit, true>(MFinNone<K>{}, MOpCgInit{Ad, B, M, g, d}, nullptr, 0)));
     TRY((k.template pass<MFinInit<K, PCG>, MOpNone, true>(MFinInit<K, PCG>{}, MOpNone{}, k.tab_sum, k.grid, 1)));
 
     auto body = [&]() -> int {
         c.cnt_ax++;
         TRY(spmm_launch(k.P, K, d, Ad, c.stream, &k.cur->all_done, d, big, k.tab_dot, &k.g_dot));          // :232-234, :387-389
-        if (PCG) {
+        if (PCG && F) {
+            TRY(k.pass(MFinAlpha<K>{}, MOpFUpdate{M, g, d, Ad, m2d()}, k.tab_dot, k.g_dot));                   // :390-399
+            c.cnt_vec += m_launches;
+            TRY(tri_apply_multi(F, K, 2, g, z, c.stream, &k.cur->all_done));                                   // :400
+            TRY(k.pass(MFinNone<K>{}, MOpFSums{M, g, z}, nullptr, 0));                                         // :401-414
+            TRY(k.pass(MFinClose<K, true>{}, MOpPcgDir{d, z, m2d()}, k.tab_sum, k.grid));                      // :415-422
+        } else if (PCG) {
             TRY(k.pass(MFinAlpha<K>{}, MOpPcgUpdate{M, g, z, d, Ad, A->invdiag, m2d()}, k.tab_dot, k.g_dot));  // :390-414
             TRY(k.pass(MFinClose<K, true>{}, MOpPcgDir{d, z, m2d()}, k.tab_sum, k.grid));                      // :415-422
         } else {
@@ -399,22 +456,34 @@ static int run_multi(lcg_hip_csr *A, double *M, const double *B, const lcg_para 
     return rc ? rc : rc2;
 }
 
+// precond: LCG_HIP_M_JACOBI (CG: not looked at), LCG_HIP_M_IC0, LCG_HIP_M_ILU0
 template <bool PCG>
-static int solve_multi(const char *entry, lcg_hip_csr *A, int k, double *M, const double *B, const lcg_para *param, int *ret, int *iterations,
+static int solve_multi(const char *entry, lcg_hip_csr *A, int k, int precond, double *M, const double *B, const lcg_para *param, int *ret, int *iterations,
                        double *residual, int mem)
 {
     TRY(multi_args(entry, k, M, B));
     TRY(multi_handle(entry, A));
     if (A->n_rows != A->n_cols) { ctx().err = std::string(entry) + ": the matrix is not square"; return LCG_HIP_E_ARG; }
     if (mem != LCG_HIP_MEM_HOST && mem != LCG_HIP_MEM_DEVICE) { ctx().err = std::string(entry) + ": mem is neither LCG_HIP_MEM_HOST nor LCG_HIP_MEM_DEVICE"; return LCG_HIP_E_ARG; }
+    if (precond != LCG_HIP_M_JACOBI && precond != LCG_HIP_M_IC0 && precond != LCG_HIP_M_ILU0) {
+        ctx().err = std::string(entry) + ": precond is none of LCG_HIP_M_JACOBI, LCG_HIP_M_IC0, LCG_HIP_M_ILU0";
+        return LCG_HIP_E_ARG;
+    }
     const lcg_para p = param ? *param : lcg_hip_default_parameters();
     if (p.max_iterations < 0) return LCG_INVILAD_MAX_ITERATIONS;            // lcg.cpp:150-155
     if (p.epsilon <= 0.0 || p.epsilon >= 1.0) return LCG_INVILAD_EPSILON;
-    if (PCG && A->invdiag == nullptr) return LCG_NULL_PRECONDITION_MATRIX;  // lcg_hip_csr_build_jacobi has not run
+    TriFactor *F = nullptr;
+    if (precond == LCG_HIP_M_JACOBI) {
+        if (PCG && A->invdiag == nullptr) return LCG_NULL_PRECONDITION_MATRIX;      // lcg_hip_csr_build_jacobi has not run
+    } else {
+        F = precond == LCG_HIP_M_IC0 ? A->ic0 : A->ilu0;
+        if (!F || !F->ok) return LCG_NULL_PRECONDITION_MATRIX;              // lcg_hip_csr_build_ic0 / _ilu0 has not run (or its pivot failed)
+    }
     TRY(ensure_init());
-    if (k == 2) return run_multi<2, PCG>(A, M, B, p, ret, iterations, residual, mem);
-    if (k == 4) return run_multi<4, PCG>(A, M, B, p, ret, iterations, residual, mem);
-    return run_multi<8, PCG>(A, M, B, p, ret, iterations, residual, mem);
+    if (F) TRY(tri_multi_reserve(F, k, 2));
+    if (k == 2) return run_multi<2, PCG>(A, F, M, B, p, ret, iterations, residual, mem);
+    if (k == 4) return run_multi<4, PCG>(A, F, M, B, p, ret, iterations, residual, mem);
+    return run_multi<8, PCG>(A, F, M, B, p, ret, iterations, residual, mem);
 }
 
 } // namespace
@@ -428,14 +497,21 @@ int lcg_hip_lcg_multi(lcg_hip_csr_t A, int k, double *M, const double *B, const 
                       double *residual, int mem)
 {
     NOT_DENSE(A, LCG_HIP_E_ARG);
-    return solve_multi<false>("lcg_hip_lcg_multi", A, k, M, B, param, ret, iterations, residual, mem);
+    return solve_multi<false>("lcg_hip_lcg_multi", A, k, LCG_HIP_M_JACOBI, M, B, param, ret, iterations, residual, mem);
 }
 
 int lcg_hip_lpcg_multi(lcg_hip_csr_t A, int k, double *M, const double *B, const lcg_para *param, int *ret, int *iterations,
                        double *residual, int mem)
 {
     NOT_DENSE(A, LCG_HIP_E_ARG);
-    return solve_multi<true>("lcg_hip_lpcg_multi", A, k, M, B, param, ret, iterations, residual, mem);
+    return solve_multi<true>("lcg_hip_lpcg_multi", A, k, LCG_HIP_M_JACOBI, M, B, param, ret, iterations, residual, mem);
+}
+
+int lcg_hip_lpcg_multi_m(lcg_hip_csr_t A, int k, int precond, double *M, const double *B, const lcg_para *param, int *ret,
+                         int *iterations, double *residual, int mem)
+{
+    NOT_DENSE(A, LCG_HIP_E_ARG);
+    return solve_multi<true>("lcg_hip_lpcg_multi_m", A, k, precond, M, B, param, ret, iterations, residual, mem);
 }
 
 } // extern "C"
