@@ -570,6 +570,12 @@ int lcg_hip_spmm(lcg_hip_csr_t A, int k, const double *X, double *Y);
 /* The same product carrying, per column, the sum the batched loops take right after it (d.Ad): dots[j] = (A.X)_j . U_j, j < k
  * (host, after a stream synchronise).  The sums ride in the product's epilogue as per-workgroup partial sums added in a fixed order. */
 int lcg_hip_spmm_dot(lcg_hip_csr_t A, int k, const double *X, double *Y, const double *U, double *dots);
+/* The same product carrying TWO sums per column, the ones BiCGStab takes right after its second product (lcg.cpp:733-741, As.s
+ * and As.As): dots2[j] = (A.X)_j . U_j and dots2[k + j] = (A.X)_j . (A.X)_j, j < k (host, after a stream synchronise).  dots2[j]
+ * has the bits of lcg_hip_spmm_dot's dots[j] for the same inputs; column j's two sums depend on A, X_j and U_j alone, bit for
+ * bit, whatever k is and whatever the other columns hold.  Arguments and handles are checked as lcg_hip_spmm_dot's: LCG_HIP_E_ARG
+ * before the device is touched, Y untouched. */
+int lcg_hip_spmm_dot2(lcg_hip_csr_t A, int k, const double *X, double *Y, const double *U, double *dots2);
 /* Batched CG (lcg.cpp:143-274) and PCG with the built-in Jacobi (lcg.cpp:293-434; needs lcg_hip_csr_build_jacobi(A)) over
  * k = 2, 4 or 8 right-hand sides against one real fp64 CSR matrix on one GPU: M (in/out) and B are blocks of k vectors in
  * lcg_hip_spmm's layout and live where `mem` says.  Each column runs the reference's recurrence as if it were alone -- its own
@@ -602,6 +608,27 @@ enum { LCG_HIP_M_JACOBI = 0, LCG_HIP_M_IC0 = 1, LCG_HIP_M_ILU0 = 2 };
  * LCG_HIP_E_ARG; no factor (or no Jacobi diagonal): LCG_NULL_PRECONDITION_MATRIX.  Everything else as lcg_hip_lpcg_multi. */
 int lcg_hip_lpcg_multi_m(lcg_hip_csr_t A, int k, int precond, double *M, const double *B, const lcg_para *param,
                          int *ret, int *iterations, double *residual, int mem);
+enum { LCG_HIP_M_NONE = -1 };   /* no preconditioner (lcg_hip_lbicgstab_multi only) */
+/* Batched BiCGStab (lcg.cpp:629-794) over k = 2, 4 or 8 right-hand sides for a square real fp64 CSR matrix on one GPU, symmetric
+ * or not; layout, mem, ret / iterations / residual, "returns 0 when the loop ran" and the parameter checks are
+ * lcg_hip_lpcg_multi_m's.  Each column runs the reference's recurrence as if it were alone -- its own ak, wk, betak and rkr0_T,
+ * r0_T = p = r = B - A.m, both "already optimised" criteria in the reference's order, the stop test at the loop head, the NaN
+ * scan of m after the update, its own count and code; a breakdown (Apk.r0_T = 0 or As.As = 0) ends that column alone with
+ * LCG_NAN_VALUE.  Schedule, precond = LCG_HIP_M_NONE: two products and three k-wide passes per iteration,
+ *     v = A.p carrying v.r0 | [ak] s = r - ak v | t = A.s carrying t.s, t.t | [wk] m += ak p + wk s; r = s - wk t + sums | [close] p = r + betak (p - wk v)
+ * LCG_HIP_M_JACOBI / _IC0 / _ILU0: right preconditioning carried in x-space,
+ *     ph = M^-1 p; v = A.ph; s = r - ak v; sh = M^-1 s; t = A.sh; m += ak ph + wk sh; r = s - wk t; p = r + betak (p - wk v)
+ * so M (the block) holds the solution itself, the stop rule sees |m| and nothing is applied after the loop (the single-vector
+ * lcg_hip_csr_ax_ilu0 route iterates on u and needs a final ilu0_solve; this one does not).  In exact arithmetic the residuals are
+ * those of A.M^-1 u = b - A.m0 from u = 0, and m = m0 + M^-1 u.  A factor is applied k wide at the handle's sweeps setting, twice
+ * per iteration (its launches count as vector passes in lcg_hip_last_launches); the Jacobi multiply rides in the passes that write
+ * p and s.  A column that has stopped is final: its columns of m, r, p and s are not stored to again.  NaN count: a column that
+ * ends with LCG_NAN_VALUE reports the iteration in which the NaN appeared (t after its t++), as the batched CG does -- one more
+ * than the last count the reference's progress callback saw.  Column j's results depend on A, its factor, column j of B and M and
+ * param alone, bit for bit: whatever the other columns hold, whatever k is, from call to call.  Any other precond: LCG_HIP_E_ARG;
+ * no factor or no Jacobi diagonal: LCG_NULL_PRECONDITION_MATRIX. */
+int lcg_hip_lbicgstab_multi(lcg_hip_csr_t A, int k, int precond, double *M, const double *B, const lcg_para *param,
+                            int *ret, int *iterations, double *residual, int mem);
 /* y = op(A).x for a complex64 handle (layout / conjugate as lcg_hip_spmv_op: A, A^T, conj(A), A^H), summed in fp32 as cuSPARSE's
  * CUDA_C_32F (clcg_cudaf.cu's Afp), each row in one fixed order: bit-identical from call to call.  k_c64_rows (W lanes per row,
  * each pair of entries one 16-byte value load and one 8-byte column load, row ends masked by selects) and, for rows of more than max(256, 64 W) entries, k_c64_long (one workgroup per row);

@@ -146,9 +146,11 @@ SIGNATURES = {
     "lcg_hip_spmv_dot": (C.c_int, [vp, vp, vp, vp, c_double_p]),
     "lcg_hip_spmm": (C.c_int, [vp, C.c_int, vp, vp]),
     "lcg_hip_spmm_dot": (C.c_int, [vp, C.c_int, vp, vp, vp, c_double_p]),
+    "lcg_hip_spmm_dot2": (C.c_int, [vp, C.c_int, vp, vp, vp, c_double_p]),
     "lcg_hip_lcg_multi": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(LcgPara), c_int_p, c_int_p, c_double_p, C.c_int]),
     "lcg_hip_lpcg_multi": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(LcgPara), c_int_p, c_int_p, c_double_p, C.c_int]),
     "lcg_hip_lpcg_multi_m": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.POINTER(LcgPara), c_int_p, c_int_p, c_double_p, C.c_int]),
+    "lcg_hip_lbicgstab_multi": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.POINTER(LcgPara), c_int_p, c_int_p, c_double_p, C.c_int]),
     "lcg_hip_ic0_solve_multi": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
     "lcg_hip_ilu0_solve_multi": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
     "lcg_hip_dot": (C.c_int, [C.c_int, vp, vp, c_double_p]),

@@ -279,6 +279,14 @@ class CsrMatrix:
         k = _block_k(X, Y)
         _chk(L.load().lcg_hip_spmm(self.h, k, _ptr(X)[0], _ptr(Y)[0]), "spmm")
 
+    def spmm_dot2(self, X, Y, U):
+        """spmm carrying two sums per column (lcg_hip_spmm_dot2): returns a float64 array of 2k, [j] = Y_j . U_j and
+        [k + j] = Y_j . Y_j -- what BiCGStab takes after its second product.  X, Y, U as spmm's blocks."""
+        k = _block_k(X, Y, U)
+        out = (C.c_double * (2 * k))()
+        _chk(L.load().lcg_hip_spmm_dot2(self.h, k, _ptr(X)[0], _ptr(Y)[0], _ptr(U)[0], out), "spmm_dot2")
+        return np.array(out[:], dtype=np.float64)
+
     def distribute(self, n_global: int, mode: int = 0):
         _chk(L.load().lcg_hip_csr_distribute(self.h, n_global, mode), "csr_distribute")
 
@@ -471,6 +479,7 @@ def _block_k(*blocks):
 
 
 PRECONDS = {"jacobi": 0, "ic0": 1, "ilu0": 2}       # LCG_HIP_M_JACOBI, LCG_HIP_M_IC0, LCG_HIP_M_ILU0
+M_NONE = -1                                         # LCG_HIP_M_NONE
 
 
 def _multi(name, A, M, B, param, precond=None):
@@ -505,6 +514,15 @@ def lpcg_multi(A, M, B, param, precond="jacobi") -> list:
     if precond == "jacobi":
         return _multi("lcg_hip_lpcg_multi", A, M, B, param)
     return _multi("lcg_hip_lpcg_multi_m", A, M, B, param, PRECONDS[precond])
+
+
+def lbicgstab_multi(A, M, B, param, precond=None) -> list:
+    """Batched BiCGStab for a square real matrix, symmetric or not (lcg_hip_lbicgstab_multi).  precond None: plain; "jacobi",
+    "ic0", "ilu0": right-preconditioned in x-space with the handle's diagonal or factor (built first) applied to all columns at
+    once -- M holds the solution itself, nothing is applied afterwards.  As lcg_multi."""
+    if precond is not None and precond not in PRECONDS:
+        raise ValueError('precond is None, "jacobi", "ic0" or "ilu0"')
+    return _multi("lcg_hip_lbicgstab_multi", A, M, B, param, M_NONE if precond is None else PRECONDS[precond])
 
 
 def lcgs(Afp, Pfp, m, B, n_size, param, instance, *workspaces) -> SolveInfo:

@@ -1,4 +1,4 @@
-// csr_multi.hip -- Y = A.X for k = 2, 4, 8 vectors at once (real fp64 CSR, one GPU): lcg_hip_spmm, lcg_hip_spmm_dot.
+// csr_multi.hip -- Y = A.X for k = 2, 4, 8 vectors at once (real fp64 CSR, one GPU): lcg_hip_spmm, lcg_hip_spmm_dot, lcg_hip_spmm_dot2.
 //
 // The product is what an iteration costs, and one vector cannot pay less for it than 12 bytes per entry.  k vectors interleaved row
 // by row (multi.hpp) share ONE pass over col / val, and every gather of x fetches k * 8 contiguous bytes.
@@ -14,6 +14,8 @@
 //      whatever the other columns hold, whatever k is, from call to call.  No atomics.
 //      <DOT>: the lanes that write Y multiply it with U on the way out and the block leaves one partial sum per column, as
 //      k_spmv_lds1d does for one vector (more than MM_MG blocks: k_mm_fold adds runs of consecutive blocks, in order).
+//      <DOT = 2>: the same lanes also square what they write: a second partial sum per column, (A.X)_j . (A.X)_j, in rows K .. 2K - 1
+//      of the table -- the two sums BiCGStab takes after its second product (t.s, t.t).  The first has the bits of <DOT = 1>'s.
 //
 // The handle's single-vector plans (packed columns, tiles, bins) are neither used nor built.
 #include "multi.hpp"
@@ -24,7 +26,7 @@ typedef int m4i __attribute__((ext_vector_type(4)));    // (native vector types:
 
 constexpr int MM_CH = 2304;     // entries per LDS window: 27,648 B of staging, five blocks per CU; 64 rows of 33 entries fit one
 
-template <int K, int R, bool DOT>
+template <int K, int R, int DOT>
 __global__ __launch_bounds__(VB) void k_spmm(int n, const int *__restrict__ rowptr, const int *__restrict__ col,
                                              const double *__restrict__ val, const double *__restrict__ X, double *__restrict__ Y,
                                              const int *done, bool wide, const double *__restrict__ U, double *__restrict__ part,
@@ -128,7 +130,7 @@ __global__ __launch_bounds__(VB) void k_spmm(int n, const int *__restrict__ rowp
 #pragma unroll
     for (int h = 0; h < K2; h++) sred[(h * T + j0) * R + rl] = acc[h];
     __syncthreads();
-    double dsum[K];
+    double dsum[K], dsq[K];
     if (mine) {
 #pragma unroll
         for (int h = 0; h < K2; h++) {
@@ -136,16 +138,24 @@ __global__ __launch_bounds__(VB) void k_spmm(int n, const int *__restrict__ rowp
             for (int j = 1; j < T; j++) v += sred[(h * T + j) * R + rl];
             reinterpret_cast<m2d *>(Y)[(long)(row0 + rl) * K2 + h] = v;
             if (DOT) { dsum[2 * h] = v.x * uv[h].x; dsum[2 * h + 1] = v.y * uv[h].y; }
+            if (DOT == 2) { dsq[2 * h] = v.x * v.x; dsq[2 * h + 1] = v.y * v.y; }
         }
     } else if (DOT) {
 #pragma unroll
-        for (int j = 0; j < K; j++) dsum[j] = 0.0;
+        for (int j = 0; j < K; j++) { dsum[j] = 0.0; dsq[j] = 0.0; }
     }
     if (DOT && tid < 64) {
 #pragma unroll
         for (int j = 0; j < K; j++) {
             const double t = wave_sum(dsum[j]);
             if (tid == WSUM_LANE) part[(size_t)j * pstride + blockIdx.x] = t;
+        }
+    }
+    if (DOT == 2 && tid < 64) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            const double t = wave_sum(dsq[j]);
+            if (tid == WSUM_LANE) part[(size_t)(K + j) * pstride + blockIdx.x] = t;
         }
     }
 }
@@ -162,7 +172,7 @@ __global__ __launch_bounds__(VB) void k_mm_fold(const double *__restrict__ big, 
     out[j * MM_MG + f] = t;
 }
 
-// the k dots of lcg_hip_spmm_dot out of their partial sums
+// the k dots of lcg_hip_spmm_dot (the 2k of lcg_hip_spmm_dot2: K = 2k) out of their partial sums
 template <int K>
 __global__ __launch_bounds__(VB) void k_mm_dots(const double *dots, int slots, double *out)
 {
@@ -178,31 +188,32 @@ static int rows_per_block(const CsrPart &P)
 }
 static long spmm_blocks(const CsrPart &P) { const int R = rows_per_block(P); return ((long)P.n_rows + R - 1) / R; }
 
-size_t spmm_big_doubles(const CsrPart &P, int k)
+size_t spmm_big_doubles(const CsrPart &P, int k, bool dot2)
 {
     const long nb = spmm_blocks(P);
-    return nb > MM_MG ? (size_t)nb * k : 0;
+    return nb > MM_MG ? (size_t)nb * k * (dot2 ? 2 : 1) : 0;
 }
 
 template <int K, int R>
 static void spmm_go(const CsrPart &P, const double *X, double *Y, hipStream_t s, const int *done, bool wide, const double *U, double *part,
-                    int pstride)
+                    int pstride, bool dot2)
 {
     const unsigned nb = (unsigned)(((long)P.n_rows + R - 1) / R);
-    if (U) hipLaunchKernelGGL((k_spmm<K, R, true>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
-    else hipLaunchKernelGGL((k_spmm<K, R, false>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
+    if (U && dot2) hipLaunchKernelGGL((k_spmm<K, R, 2>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
+    else if (U) hipLaunchKernelGGL((k_spmm<K, R, 1>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
+    else hipLaunchKernelGGL((k_spmm<K, R, 0>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
 }
 template <int K>
 static void spmm_k(const CsrPart &P, int R, const double *X, double *Y, hipStream_t s, const int *done, bool wide, const double *U, double *part,
-                   int pstride)
+                   int pstride, bool dot2)
 {
-    if (R == 64) spmm_go<K, 64>(P, X, Y, s, done, wide, U, part, pstride);
-    else if (R == 16) spmm_go<K, 16>(P, X, Y, s, done, wide, U, part, pstride);
-    else spmm_go<K, 4>(P, X, Y, s, done, wide, U, part, pstride);
+    if (R == 64) spmm_go<K, 64>(P, X, Y, s, done, wide, U, part, pstride, dot2);
+    else if (R == 16) spmm_go<K, 16>(P, X, Y, s, done, wide, U, part, pstride, dot2);
+    else spmm_go<K, 4>(P, X, Y, s, done, wide, U, part, pstride, dot2);
 }
 
 int spmm_launch(const CsrPart &P, int k, const double *X, double *Y, hipStream_t s, const int *done, const double *U, double *big,
-                double *dots, int *slots)
+                double *dots, int *slots, bool dot2)
 {
     const int R = rows_per_block(P);
     const long nb = spmm_blocks(P);
@@ -210,18 +221,19 @@ int spmm_launch(const CsrPart &P, int k, const double *X, double *Y, hipStream_t
     const bool wide = P.padded && (((uintptr_t)P.col | (uintptr_t)P.val) & 15) == 0;
     const bool folded = U != nullptr && nb > MM_MG;
     if (U && (!dots || !slots || (folded && !big))) return LCG_HIP_E_ARG;
+    if (dot2 && !U) return LCG_HIP_E_ARG;
     double *part = folded ? big : dots;
     const int pstride = folded ? (int)nb : MM_MG;
-    if (k == 2) spmm_k<2>(P, R, X, Y, s, done, wide, U, part, pstride);
-    else if (k == 4) spmm_k<4>(P, R, X, Y, s, done, wide, U, part, pstride);
-    else spmm_k<8>(P, R, X, Y, s, done, wide, U, part, pstride);
+    if (k == 2) spmm_k<2>(P, R, X, Y, s, done, wide, U, part, pstride, dot2);
+    else if (k == 4) spmm_k<4>(P, R, X, Y, s, done, wide, U, part, pstride, dot2);
+    else spmm_k<8>(P, R, X, Y, s, done, wide, U, part, pstride, dot2);
     HIPCHK(hipGetLastError());
     if (U) {
         *slots = (int)nb;
         if (folded) {
             // (the fold runs whatever the stop flag says: after a stop it adds up what the last live product left, and nobody reads it)
             const int per = (int)((nb + MM_MG - 1) / MM_MG), nf = (int)((nb + per - 1) / per);
-            hipLaunchKernelGGL(k_mm_fold, dim3((nf + VB - 1) / VB, k), dim3(VB), 0, s, big, (int)nb, per, nf, dots);
+            hipLaunchKernelGGL(k_mm_fold, dim3((nf + VB - 1) / VB, dot2 ? 2 * k : k), dim3(VB), 0, s, big, (int)nb, per, nf, dots);
             HIPCHK(hipGetLastError());
             *slots = nf;
         }
@@ -253,6 +265,38 @@ int multi_handle(const char *entry, const lcg_hip_csr *A)
     return LCG_HIP_E_ARG;
 }
 
+// lcg_hip_spmm_dot (k sums) and lcg_hip_spmm_dot2 (2k: the Y.U sums, then the Y.Y sums)
+static int spmm_dot_entry(const char *entry, lcg_hip_csr *A, int k, const double *X, double *Y, const double *U, double *dots, bool dot2)
+{
+    TRY(multi_args(entry, k, X, Y, U));
+    TRY(multi_handle(entry, A));
+    if (!dots) { ctx().err = std::string(entry) + ": the result array is a null pointer"; return LCG_HIP_E_ARG; }
+    TRY(ensure_init());
+    Ctx &c = ctx();
+    // (outside a solve the k-wide table of the loops is free: partials_pair[0] holds the partial sums, ax_partials the results)
+    const int ns = dot2 ? 2 * k : k;
+    double *big = nullptr;
+    const size_t nbig = spmm_big_doubles(A->main, k, dot2);
+    if (nbig) HIPCHK(hipMalloc(&big, sizeof(double) * nbig));
+    int slots = 0;
+    int rc = spmm_launch(A->main, k, X, Y, c.stream, nullptr, U, big, c.partials_pair[0], &slots, dot2);
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        if (ns == 2) hipLaunchKernelGGL((k_mm_dots<2>), dim3(1), dim3(VB), 0, c.stream, c.partials_pair[0], slots, c.ax_partials);
+        else if (ns == 4) hipLaunchKernelGGL((k_mm_dots<4>), dim3(1), dim3(VB), 0, c.stream, c.partials_pair[0], slots, c.ax_partials);
+        else if (ns == 8) hipLaunchKernelGGL((k_mm_dots<8>), dim3(1), dim3(VB), 0, c.stream, c.partials_pair[0], slots, c.ax_partials);
+        else hipLaunchKernelGGL((k_mm_dots<16>), dim3(1), dim3(VB), 0, c.stream, c.partials_pair[0], slots, c.ax_partials);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(c.scratch_host, c.ax_partials, sizeof(double) * ns, hipMemcpyDeviceToHost, c.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    }
+    if (big) (void)hipFree(big);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(e, "spmm_dot", __FILE__, __LINE__);
+    for (int j = 0; j < ns; j++) dots[j] = c.scratch_host[j];
+    return 0;
+}
+
 } // namespace lcgh
 
 using namespace lcgh;
@@ -272,31 +316,13 @@ int lcg_hip_spmm(lcg_hip_csr_t A, int k, const double *X, double *Y)
 int lcg_hip_spmm_dot(lcg_hip_csr_t A, int k, const double *X, double *Y, const double *U, double *dots)
 {
     NOT_DENSE(A, LCG_HIP_E_ARG);
-    TRY(multi_args("lcg_hip_spmm_dot", k, X, Y, U));
-    TRY(multi_handle("lcg_hip_spmm_dot", A));
-    if (!dots) { ctx().err = "lcg_hip_spmm_dot: the result array is a null pointer"; return LCG_HIP_E_ARG; }
-    TRY(ensure_init());
-    Ctx &c = ctx();
-    // (outside a solve the k-wide table of the loops is free: partials_pair[0] holds the partial sums, ax_partials the k results)
-    double *big = nullptr;
-    const size_t nbig = spmm_big_doubles(A->main, k);
-    if (nbig) HIPCHK(hipMalloc(&big, sizeof(double) * nbig));
-    int slots = 0;
-    int rc = spmm_launch(A->main, k, X, Y, c.stream, nullptr, U, big, c.partials_pair[0], &slots);
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        if (k == 2) hipLaunchKernelGGL((k_mm_dots<2>), dim3(1), dim3(VB), 0, c.stream, c.partials_pair[0], slots, c.ax_partials);
-        else if (k == 4) hipLaunchKernelGGL((k_mm_dots<4>), dim3(1), dim3(VB), 0, c.stream, c.partials_pair[0], slots, c.ax_partials);
-        else hipLaunchKernelGGL((k_mm_dots<8>), dim3(1), dim3(VB), 0, c.stream, c.partials_pair[0], slots, c.ax_partials);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(c.scratch_host, c.ax_partials, sizeof(double) * k, hipMemcpyDeviceToHost, c.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    }
-    if (big) (void)hipFree(big);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(e, "spmm_dot", __FILE__, __LINE__);
-    for (int j = 0; j < k; j++) dots[j] = c.scratch_host[j];
-    return 0;
+    return spmm_dot_entry("lcg_hip_spmm_dot", A, k, X, Y, U, dots, false);
+}
+
+int lcg_hip_spmm_dot2(lcg_hip_csr_t A, int k, const double *X, double *Y, const double *U, double *dots2)
+{
+    NOT_DENSE(A, LCG_HIP_E_ARG);
+    return spmm_dot_entry("lcg_hip_spmm_dot2", A, k, X, Y, U, dots2, true);
 }
 
 } // extern "C"

@@ -20,12 +20,12 @@ int multi_args(const char *entry, int k, const void *a, const void *b, const voi
 int multi_handle(const char *entry, const lcg_hip_csr *A);
 
 // Y = A.X for the k columns in one launch (P's plain CSR arrays: no plan is built or used).  With U: column j's sum
-// (A.X)_j . U_j is left as *slots <= MM_MG partial sums at dots[j * MM_MG ...], to be added in index order.  `big` holds the
-// per-workgroup sums of a matrix with more than MM_MG row blocks on their way there (spmm_big_doubles(P, k) doubles; may be
-// null where that is 0).
+// (A.X)_j . U_j is left as *slots <= MM_MG partial sums at dots[j * MM_MG ...], to be added in index order; with dot2 besides it
+// (A.X)_j . (A.X)_j at dots[(k + j) * MM_MG ...], the first sum's bits unchanged.  `big` holds the per-workgroup sums of a matrix
+// with more than MM_MG row blocks on their way there (spmm_big_doubles(P, k, dot2) doubles; may be null where that is 0).
 int spmm_launch(const CsrPart &P, int k, const double *X, double *Y, hipStream_t s, const int *done, const double *U = nullptr,
-                double *big = nullptr, double *dots = nullptr, int *slots = nullptr);
-size_t spmm_big_doubles(const CsrPart &P, int k);
+                double *big = nullptr, double *dots = nullptr, int *slots = nullptr, bool dot2 = false);
+size_t spmm_big_doubles(const CsrPart &P, int k, bool dot2 = false);
 
 // Sum the g <= MM_MG partials of each of NS running sums (table row r = pin + r * MM_MG) into sums[r] (LDS), the whole block taking
 // part: per lane its partials in index order, the lanes by wave_sum, the wavefronts in order -- the same bits wherever and
@@ -56,6 +56,40 @@ __device__ __forceinline__ void msum(const double *pin, int g, double *sums)
         sums[threadIdx.x] = t;
     }
     __syncthreads();
+}
+
+// The same sums as ONE binary tree over the table's MM_MG slots, adjacent slots first (g <= MM_MG partials, the rest read as +0):
+// a lane adds its 8 consecutive slots pairwise, the lanes meet by xor 1, 2, 4, ... 32, one wavefront per running sum.  Partials that
+// are themselves such trees over 2^m consecutive leaves (k_mvecf's TREE passes) add up to the tree over all leaves, however many
+// leaves a partial holds: what lets a column's sums not depend on k.  Ends with a barrier.
+template <int NS>
+__device__ __forceinline__ void msum_tree(const double *pin, int g, double *sums)
+{
+    static_assert(MM_MG == 64 * 8, "eight slots per lane");
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int r = w; r < NS; r += VB / 64) {
+        double x[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const int j = 8 * lane + q;
+            const double v = pin[r * MM_MG + (j < g ? j : 0)];      // branch-free: select after the load
+            x[q] = j < g ? v : 0.0;
+        }
+        double t = ((x[0] + x[1]) + (x[2] + x[3])) + ((x[4] + x[5]) + (x[6] + x[7]));
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) t += __shfl_xor(t, off, 64);
+        if (lane == 0) sums[r] = t;
+    }
+    __syncthreads();
+}
+
+// the leaves of a TREE pass: rows i, i + S, i + 2 S, ... share leaf i mod S.  S depends on n alone, so a thread's leaf does not
+// depend on k; the pass runs S * (k / 2) / VB workgroups (k = 8: at most MM_MG)
+inline long tree_leaves(long n)
+{
+    long s = 256;
+    while (s < n && s < 64 * MM_MG) s <<= 1;
+    return s;
 }
 
 } // namespace lcgh

@@ -7,8 +7,9 @@
 //
 // The classic three-pass schedule of solvers_real.hip, k wide (vectors: multi.hpp's row-major blocks):
 //     A.d carrying d.Ad  |  [alpha] m += a d, g += a Ad (PCG: r -= a Ad, z = r / diag) + m.m, g.g (r.r, z.r), NaN  |  [close] d = b d - g (z + b d)
-// All scalars live on the device in MState, k wide.  A scalar step rides in the prologue of the pass that consumes it, as in
-// k_vecf (devcommon.hpp): every block adds the previous pass's partial sums in msum's fixed order, runs the step for all columns on
+// All scalars live on the device in MState, k wide.  A scalar step rides in the prologue of the pass that consumes it (k_mvecf,
+// multi_loop.hpp: shared with the batched BiCGStab of solvers_multi_bicg.hip), as in k_vecf (devcommon.hpp): every block adds the
+// previous pass's partial sums in msum's fixed order, runs the step for all columns on
 // a copy of MState in LDS, and block 0 commits the copy to the other buffer of a pair.
 //
 // With a factor as M the multiply leaves the update pass:
@@ -24,7 +25,7 @@
 // change: their coefficients and stop words sit in registers, their sums are two accumulators per running sum.  A column's partial
 // sums are added in a fixed order (lane's own in index order, lanes of a wavefront by xor-butterfly, wavefronts in order, blocks in
 // order): the same bits whatever the other columns hold, from call to call.
-#include "multi.hpp"
+#include "multi_loop.hpp"
 #include "csr_tri.hpp"
 
 namespace lcgh {
@@ -51,27 +52,7 @@ __global__ void k_minit(MState *st, double eps, double n_global, int abs_diff, i
     if (threadIdx.x == 0) { st->eps = eps; st->n_global = n_global; st->abs_diff = abs_diff; st->pub_mask = pub_mask; st->host = host; }
 }
 
-__device__ __forceinline__ void mpublish(MState *st)
-{
-    HostStatus *h = st->host;
-    if (!h) return;         // a block's private copy: only block 0 mirrors to the host
-    if (!st->all_done && (st->it & st->pub_mask)) return;
-    h->done = st->all_done;
-    h->it = st->it;         // (posted writes: the host paces itself on them and reads MState with a real copy before it returns)
-}
-template <int K> __device__ __forceinline__ void all_stopped(MState *st)
-{
-    int all = 1;
-#pragma unroll
-    for (int j = 0; j < K; j++) all &= st->stop[j] != ST_RUNNING;
-    st->all_done = all;
-}
-
 // ---- scalar steps: sums[s * K + j] = running sum s of column j ------------------------------------------------------------------
-template <int K> struct MFinNone {
-    static constexpr int NS = 0;
-    __device__ void operator()(MState *, const double *) const {}
-};
 // setup: |m|^2 (clamped), the residual's numerator, rho; "already optimised" per column (lcg.cpp:178-203, 341-359: in abs_diff mode
 // BOTH criteria are tried, in this order).  PCG: sums m.m, r.r, z.r; CG: m.m, g.g (rho = g.g)
 template <int K, bool PCG> struct MFinInit {
@@ -133,23 +114,6 @@ template <int K, bool PCG> struct MFinClose {
 };
 
 // ---- vector passes ----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ m2d ld2(const double *p, long e) { return reinterpret_cast<const m2d *>(p)[e]; }
-// only the running halves of a piece are written: a stopped column's bytes are never stored to again
-__device__ __forceinline__ void st2(double *p, long e, m2d v, bool r0, bool r1)
-{
-    if (r0 && r1) reinterpret_cast<m2d *>(p)[e] = v;
-    else if (r0) p[2 * e] = v.x;
-    else if (r1) p[2 * e + 1] = v.y;
-}
-__device__ __forceinline__ m2d nan2(m2d v) { m2d f; f.x = v.x != v.x ? 1.0 : 0.0; f.y = v.y != v.y ? 1.0 : 0.0; return f; }
-
-// Op provides: static constexpr int NS;  void prep(const MState &, int c0) (the coefficients of columns c0, c0 + 1);
-//              void apply(long e, long row, bool r0, bool r1, m2d *acc)
-struct MOpNone {
-    static constexpr int NS = 0;
-    __device__ void prep(const MState &, int) {}
-    __device__ void apply(long, long, bool, bool, m2d *) {}
-};
 struct MOpCgInit {      // g = Ad - B; d = -g; m.m, g.g                   lcg.cpp:171-183
     static constexpr int NS = 2;
     const double *Ad, *B, *m; double *g, *d;
@@ -249,73 +213,7 @@ struct MOpPcgDir {      // d = z + b d                                     lcg.c
     __device__ void apply(long e, long, bool r0, bool r1, m2d *) { st2(d, e, ld2(z, e) + bk * ld2(d, e), r0, r1); }
 };
 
-// One fused pass over n2 = n * K / 2 pieces with the scalar step `fin` in its prologue.  ALL: every column is worked on whatever its
-// stop word says (the setup passes, before the words mean anything).
-template <int K, class Fin, class Op, bool ALL>
-__global__ __launch_bounds__(VB) void k_mvecf(Fin fin, Op op, long n2, const double *pin, int gin, double *pout, const MState *cur, MState *next)
-{
-    constexpr int K2 = K / 2;
-    constexpr int NSF = Fin::NS > 0 ? Fin::NS * K : 1, NSO = Op::NS > 0 ? Op::NS : 1;
-    __shared__ MState L;
-    __shared__ double sums[NSF];
-    __shared__ double wsh[VB / 64][NSO][K];
-    {
-        const double *src = reinterpret_cast<const double *>(cur);
-        double *dst = reinterpret_cast<double *>(&L);
-        for (int i = threadIdx.x; i < (int)(sizeof(MState) / 8); i += VB) dst[i] = src[i];
-    }
-    if (Fin::NS > 0) msum<NSF>(pin, gin, sums);     // ends with a barrier: L and sums are complete
-    else __syncthreads();
-    if (threadIdx.x == 0) {
-        if (blockIdx.x != 0) L.host = nullptr;
-        fin(&L, sums);
-    }
-    __syncthreads();
-    if (blockIdx.x == 0) {
-        const double *src = reinterpret_cast<const double *>(&L);
-        double *dst = reinterpret_cast<double *>(next);
-        for (int i = threadIdx.x; i < (int)(sizeof(MState) / 8); i += VB) dst[i] = src[i];
-    }
-    if (L.all_done && !ALL) return;
-    // (gridDim.x * VB and VB are multiples of K2: this thread's pieces all belong to columns c0, c0 + 1)
-    const int c0 = 2 * ((int)threadIdx.x % K2);
-    const bool r0 = ALL || L.stop[c0] == ST_RUNNING, r1 = ALL || L.stop[c0 + 1] == ST_RUNNING;
-    op.prep(L, c0);
-    m2d acc[NSO];
-#pragma unroll
-    for (int s = 0; s < NSO; s++) acc[s] = (m2d)(0.0);
-    if (r0 || r1) {
-        const long stride = (long)gridDim.x * VB;
-        for (long e = (long)blockIdx.x * VB + threadIdx.x; e < n2; e += stride) op.apply(e, e / K2, r0, r1, acc);
-    }
-    if (Op::NS > 0) {
-        // lanes l, l + K2, l + 2 K2, ... of a wavefront hold the same two columns: xor-butterfly over them, then the wavefronts in order
-        const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-        for (int s = 0; s < NSO; s++) {
-            double x = acc[s].x, y = acc[s].y;
-#pragma unroll
-            for (int off = 32; off >= K2; off >>= 1) { x += __shfl_xor(x, off, 64); y += __shfl_xor(y, off, 64); }
-            if (lane < K2) { wsh[w][s][2 * lane] = x; wsh[w][s][2 * lane + 1] = y; }
-        }
-        __syncthreads();
-        if (threadIdx.x < NSO * K) {
-            const int s = threadIdx.x / K, j = threadIdx.x % K;
-            double v = 0.0;
-#pragma unroll
-            for (int q = 0; q < VB / 64; q++) v += wsh[q][s][j];
-            pout[(s * K + j) * MM_MG + blockIdx.x] = v;
-        }
-    }
-}
-
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
-struct SolveGuard {     // what ~Driver does for the single-vector loops
-    Ctx &c;
-    explicit SolveGuard(Ctx &c_) : c(c_) { c.in_solve = true; c.ax_rc = 0; c.cnt_vec = c.cnt_scal = c.cnt_allreduce = c.cnt_ax = 0; }
-    ~SolveGuard() { c.in_solve = false; }
-};
-
 template <int K, bool PCG>
 struct MultiSolve {
     Ctx &c;
@@ -329,22 +227,12 @@ struct MultiSolve {
     template <class Fin, class Op, bool ALL = false> int pass(Fin fin, Op op, const double *pin, int gin, int g = 0)
     {
         c.cnt_vec++;
-        hipLaunchKernelGGL((k_mvecf<K, Fin, Op, ALL>), dim3(g ? g : grid), dim3(VB), 0, c.stream, fin, op, n2, pin, gin, tab_sum, cur, next);
+        hipLaunchKernelGGL((k_mvecf<MState, K, Fin, Op, ALL>), dim3(g ? g : grid), dim3(VB), 0, c.stream, fin, op, n2, pin, gin, tab_sum, cur, next);
         HIPCHK(hipGetLastError());
         std::swap(cur, next);
         return 0;
     }
 };
-
-static int lcg_code(int stop)
-{
-    switch (stop) {
-    case ST_ALREADY: return LCG_ALREADY_OPTIMIZIED;
-    case ST_NAN: return LCG_NAN_VALUE;
-    case ST_CONVERGED: return LCG_CONVERGENCE;
-    default: return LCG_REACHED_MAX_ITERATIONS;
-    }
-}
 
 template <int K, bool PCG>
 static int run_multi(lcg_hip_csr *A, const TriFactor *F, double *M, const double *B, const lcg_para &p, int *ret, int *iterations,
@@ -380,12 +268,12 @@ static int run_multi(lcg_hip_csr *A, const TriFactor *F, double *M, const double
     TRY(spmm_launch(k.P, K, M, Ad, c.stream, nullptr));
     const int m_launches = PCG && F ? tri_apply_launches(F, 2) : 0;        // counted as vector passes (lcg_hip_last_launches)
     if (PCG && F) {
-        TRY((k.template pass<MFinNone<K>, MOpFRes, true>(MFinNone<K>{}, MOpFRes{Ad, B, g}, nullptr, 0)));
+        TRY((k.template pass<MFinNone, MOpFRes, true>(MFinNone{}, MOpFRes{Ad, B, g}, nullptr, 0)));
         c.cnt_vec += m_launches;
         TRY(tri_apply_multi(F, K, 2, g, z, c.stream, nullptr));
-        TRY((k.template pass<MFinNone<K>, MOpFInit, true>(MFinNone<K>{}, MOpFInit{M, g, z, d}, nullptr, 0)));
-    } else if (PCG) TRY((k.template pass<MFinNone<K>, MOpPcgInit, true>(MFinNone<K>{}, MOpPcgInit{Ad, B, M, A->invdiag, g, z, d}, nullptr, 0)));
-    else TRY((k.template pass<MFinNone<K>, MOpCgInit, true>(MFinNone<K>{}, MOpCgInit{Ad, B, M, g, d}, nullptr, 0)));
+        TRY((k.template pass<MFinNone, MOpFInit, true>(MFinNone{}, MOpFInit{M, g, z, d}, nullptr, 0)));
+    } else if (PCG) TRY((k.template pass<MFinNone, MOpPcgInit, true>(MFinNone{}, MOpPcgInit{Ad, B, M, A->invdiag, g, z, d}, nullptr, 0)));
+    else TRY((k.template pass<MFinNone, MOpCgInit, true>(MFinNone{}, MOpCgInit{Ad, B, M, g, d}, nullptr, 0)));
     TRY((k.template pass<MFinInit<K, PCG>, MOpNone, true>(MFinInit<K, PCG>{}, MOpNone{}, k.tab_sum, k.grid, 1)));
 
     auto body = [&]() -> int {
@@ -395,7 +283,7 @@ static int run_multi(lcg_hip_csr *A, const TriFactor *F, double *M, const double
             TRY(k.pass(MFinAlpha<K>{}, MOpFUpdate{M, g, d, Ad, m2d()}, k.tab_dot, k.g_dot));                   // :390-399
             c.cnt_vec += m_launches;
             TRY(tri_apply_multi(F, K, 2, g, z, c.stream, &k.cur->all_done));                                   // :400
-            TRY(k.pass(MFinNone<K>{}, MOpFSums{M, g, z}, nullptr, 0));                                         // :401-414
+            TRY(k.pass(MFinNone{}, MOpFSums{M, g, z}, nullptr, 0));                                         // :401-414
             TRY(k.pass(MFinClose<K, true>{}, MOpPcgDir{d, z, m2d()}, k.tab_sum, k.grid));                      // :415-422
         } else if (PCG) {
             TRY(k.pass(MFinAlpha<K>{}, MOpPcgUpdate{M, g, z, d, Ad, A->invdiag, m2d()}, k.tab_dot, k.g_dot));  // :390-414
@@ -407,36 +295,13 @@ static int run_multi(lcg_hip_csr *A, const TriFactor *F, double *M, const double
         return 0;
     };
 
-    // the asynchronous loop of driver.hpp: the host only enqueues, at most `inflight` bodies ahead of the device
     MState h;
     auto read_state = [&]() -> int {
         HIPCHK(hipMemcpyAsync(&h, k.cur, sizeof h, hipMemcpyDeviceToHost, c.stream));
         HIPCHK(hipStreamSynchronize(c.stream));
         return 0;
     };
-    const int inflight = work >= (1 << 20) ? 6 : 24;
-    int enq = 0, rc = 0;
-    for (;;) {
-        if (p.max_iterations > 0 && enq >= p.max_iterations) break;
-        rc = body(); if (rc) break;
-        enq++;
-        if (c.hstat->done) break;
-        int spins = 0;
-        while (c.hstat->it < enq - inflight && !c.hstat->done) {
-            if (++spins > 2000) std::this_thread::sleep_for(std::chrono::microseconds(20));
-            if (spins > 200000) {   // backstop: the mapped mirror is not advancing
-                rc = read_state(); if (rc) break;
-                if (h.all_done || h.it >= enq - inflight) break;
-                spins = 0;
-            }
-        }
-        if (rc) break;
-        if ((enq & 255) == 0) {     // authoritative check now and then
-            rc = read_state(); if (rc) break;
-            if (h.all_done) break;
-        }
-    }
-    if (!rc) rc = read_state();
+    const int rc = enqueue_ahead(c, p.max_iterations, work >= (1 << 20) ? 6 : 24, body, read_state, h);
     if (!rc) {
         int longest = 0;
         for (int j = 0; j < K; j++) {
