@@ -629,6 +629,46 @@ enum { LCG_HIP_M_NONE = -1 };   /* no preconditioner (lcg_hip_lbicgstab_multi on
  * no factor or no Jacobi diagonal: LCG_NULL_PRECONDITION_MATRIX. */
 int lcg_hip_lbicgstab_multi(lcg_hip_csr_t A, int k, int precond, double *M, const double *B, const lcg_para *param,
                             int *ret, int *iterations, double *residual, int mem);
+/* Y = A.X for k = 2, 4 or 8 COMPLEX vectors in ONE launch against a complex128 CSR handle: col / val (20 bytes per entry) are read
+ * once for all of them.  A block of k complex vectors is one array of rows x k interleaved (re, im) pairs, row-major: column j of
+ * row i is doubles 2 (i k + j) and 2 (i k + j) + 1 (X: n_cols rows, Y: n_rows), its base 16-byte aligned; other counts are padded
+ * with zero columns.  Any other k, a null pointer or a misaligned base: LCG_HIP_E_ARG before the device or the handle is looked at.
+ * Complex128 CSR handles on one GPU: real, complex64, dense and sharded handles return LCG_HIP_E_ARG (lcg_hip_last_error() says
+ * why), Y untouched; lcg_hip_spmm serves the real ones.  Column j's sums are added in an order fixed by the matrix alone: the same
+ * bits whatever the other columns hold (NaN and Inf included), whatever k is, from call to call.  Reads the plain CSR arrays: no
+ * single-vector plan is built or used. */
+int clcg_hip_spmm(lcg_hip_csr_t A, int k, const double *X, double *Y);
+/* The same product carrying, per column, the sum the batched complex loops take right after it (d.Ad): dots[2 j], dots[2 j + 1] =
+ * re, im of the UNCONJUGATED sum over i of (A.X)_ij U_ij (clcg_dot, cublasZdotu), j < k (2k doubles on the host, after a stream
+ * synchronise).  The sums ride in the product's epilogue as per-workgroup partial sums added in a fixed order: column j's sum
+ * depends on A, X_j and U_j alone, bit for bit. */
+int clcg_hip_spmm_dot(lcg_hip_csr_t A, int k, const double *X, double *Y, const double *U, double *dots);
+/* Batched BiCG for complex-symmetric A (clbicg_symmetric, clcg.cpp:228-364) and PCG with the handle's reciprocal Jacobi diagonal
+ * (clpcg, clcg_cuda.cu:403-558; needs lcg_hip_csr_build_jacobi(A)) over k = 2, 4 or 8 right-hand sides against one square
+ * complex128 CSR matrix on one GPU: M (in/out) and B are blocks of k complex vectors in clcg_hip_spmm's layout and live where `mem`
+ * says.  Each column runs the reference's recurrence as if it were alone -- its own ak, bk and rr (PCG: r.s), unconjugated inner
+ * products, its own stop test, "already optimised" test, count and code -- while one multi-vector product per iteration reads the
+ * matrix once for all of them.  Three launches per iteration:
+ *     A.d carrying d.Ad | [ak] m += ak d; r -= ak Ad (PCG: s = r / diag) + sums | [close] d = r + bk d (PCG: s + bk d)
+ * BiCG-sym: the 4th-power stop rule of the CPU complex loops, (sum |r|^2)^2 / max((sum |m|^2)^2, 1), or sum |r|^2 / n with
+ * abs_diff; both "already optimised" criteria in the reference's order; the NaN scan of m after the update ends that column with
+ * CLCG_NAN_VALUE, its count the iteration in which the NaN appeared (t after its t++).  PCG: the real loops' rule, sum |r|^2 /
+ * max(sum |m|^2, 1), or sqrt(sum |r|^2) / n with abs_diff, where |m|^2 takes no part ("already optimised" included).  One
+ * deliberate deviation: the reference's clpcg and clcg_hip_solver_preconditioned(CLCG_PCG) have no NaN scan and a broken system
+ * runs to the cap; in a batch a column whose sum |m|^2, sum |r|^2 or r.s is NaN stops with CLCG_NAN_VALUE at that iteration, as
+ * the complex64 loops do -- otherwise one NaN column would keep the batch alive for ever at max_iterations = 0.
+ * A column that has stopped is final: its elements of M, r, d and s are not stored to again.  ret, iterations, residual: host
+ * arrays of k (or NULL) receiving each column's code (CLCG_CONVERGENCE, LCG_REACHED_MAX_ITERATIONS (-1019, as the complex loops
+ * return at the cap), CLCG_ALREADY_OPTIMIZIED, CLCG_NAN_VALUE), iteration count and residual; lcg_hip_last_iterations / _residual
+ * report the column that ran longest.  Returns 0 when the loop ran, whatever the columns' verdicts; LCG_HIP_E_ARG (k, null or
+ * misaligned M / B, a real / complex64 / dense / sharded / non-square handle; before the device is touched),
+ * CLCG_INVILAD_MAX_ITERATIONS, CLCG_INVILAD_EPSILON, LCG_NULL_PRECONDITION_MATRIX (PCG without a Jacobi diagonal), or a runtime
+ * failure.  No progress callback, no caller workspaces; column j's iterate, count, residual and code depend on A, its diagonal,
+ * column j of B and M and param alone, bit for bit: whatever the other columns hold, whatever k is, from call to call. */
+int clcg_hip_lbicg_sym_multi(lcg_hip_csr_t A, int k, double *M, const double *B, const clcg_para *param,
+                             int *ret, int *iterations, double *residual, int mem);
+int clcg_hip_lpcg_multi(lcg_hip_csr_t A, int k, double *M, const double *B, const clcg_para *param,
+                        int *ret, int *iterations, double *residual, int mem);
 /* y = op(A).x for a complex64 handle (layout / conjugate as lcg_hip_spmv_op: A, A^T, conj(A), A^H), summed in fp32 as cuSPARSE's
  * CUDA_C_32F (clcg_cudaf.cu's Afp), each row in one fixed order: bit-identical from call to call.  k_c64_rows (W lanes per row,
  * each pair of entries one 16-byte value load and one 8-byte column load, row ends masked by selects) and, for rows of more than max(256, 64 W) entries, k_c64_long (one workgroup per row);

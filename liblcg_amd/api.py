@@ -287,6 +287,20 @@ class CsrMatrix:
         _chk(L.load().lcg_hip_spmm_dot2(self.h, k, _ptr(X)[0], _ptr(Y)[0], _ptr(U)[0], out), "spmm_dot2")
         return np.array(out[:], dtype=np.float64)
 
+    def cspmm(self, X, Y):
+        """Y = A.X for the k = 2, 4 or 8 complex columns of X in one launch (clcg_hip_spmm): X (n_cols, k) and Y (n_rows, k) are
+        C-contiguous complex128 CUDA tensors, 16-byte aligned.  Complex128 matrices on one GPU."""
+        k = _block_k(X, Y, cplx=True)
+        _chk(L.load().clcg_hip_spmm(self.h, k, _ptr(X)[0], _ptr(Y)[0]), "cspmm")
+
+    def cspmm_dot(self, X, Y, U):
+        """cspmm carrying one unconjugated sum per column (clcg_hip_spmm_dot): returns a complex128 array of k,
+        [j] = sum_i Y_ij U_ij -- what the batched complex loops take after their product.  X, Y, U as cspmm's blocks."""
+        k = _block_k(X, Y, U, cplx=True)
+        out = (C.c_double * (2 * k))()
+        _chk(L.load().clcg_hip_spmm_dot(self.h, k, _ptr(X)[0], _ptr(Y)[0], _ptr(U)[0], out), "cspmm_dot")
+        return np.array(out[:], dtype=np.float64).view(np.complex128)
+
     def distribute(self, n_global: int, mode: int = 0):
         _chk(L.load().lcg_hip_csr_distribute(self.h, n_global, mode), "csr_distribute")
 
@@ -461,17 +475,18 @@ def lcg(Afp, Pfp, m, B, n_size, param, instance, Gk=None, Dk=None, ADk=None) -> 
     return SolveInfo(rc, lib.lcg_hip_last_iterations(), lib.lcg_hip_last_residual())
 
 
-def _block_k(*blocks):
-    """k of 2-D (n, k) C-contiguous float64 blocks of vectors (numpy arrays or torch tensors), all alike."""
+def _block_k(*blocks, cplx=False):
+    """k of 2-D (n, k) C-contiguous float64 (cplx: complex128) blocks of vectors (numpy arrays or torch tensors), all alike."""
     k = None
     for X in blocks:
         if isinstance(X, np.ndarray):
-            ok = X.ndim == 2 and X.dtype == np.float64 and X.flags["C_CONTIGUOUS"]
+            ok = X.ndim == 2 and X.dtype == (np.complex128 if cplx else np.float64) and X.flags["C_CONTIGUOUS"]
         else:
             import torch
-            ok = isinstance(X, torch.Tensor) and X.dim() == 2 and X.dtype == torch.float64 and X.is_contiguous()
+            ok = (isinstance(X, torch.Tensor) and X.dim() == 2 and X.dtype == (torch.complex128 if cplx else torch.float64)
+                  and X.is_contiguous())
         if not ok:
-            raise ValueError("a block of vectors is a 2-D (n, k) C-contiguous float64 array or tensor")
+            raise ValueError(f"a block of vectors is a 2-D (n, k) C-contiguous {'complex128' if cplx else 'float64'} array or tensor")
         if k is not None and X.shape[1] != k:
             raise ValueError("blocks of vectors with different k")
         k = int(X.shape[1])
@@ -482,9 +497,9 @@ PRECONDS = {"jacobi": 0, "ic0": 1, "ilu0": 2}       # LCG_HIP_M_JACOBI, LCG_HIP_
 M_NONE = -1                                         # LCG_HIP_M_NONE
 
 
-def _multi(name, A, M, B, param, precond=None):
+def _multi(name, A, M, B, param, precond=None, cplx=False):
     lib = L.load()
-    k = _block_k(M, B)
+    k = _block_k(M, B, cplx=cplx)
     if tuple(M.shape) != tuple(B.shape):
         raise ValueError("M and B must have the same shape")
     (pm, mem), (pb, mem_b) = _ptr(M), _ptr(B)
@@ -523,6 +538,19 @@ def lbicgstab_multi(A, M, B, param, precond=None) -> list:
     if precond is not None and precond not in PRECONDS:
         raise ValueError('precond is None, "jacobi", "ic0" or "ilu0"')
     return _multi("lcg_hip_lbicgstab_multi", A, M, B, param, M_NONE if precond is None else PRECONDS[precond])
+
+
+def clbicg_sym_multi(A, M, B, param) -> list:
+    """Batched BiCG for a complex-symmetric complex128 matrix (clcg_hip_lbicg_sym_multi): M (in/out) and B are (n, k) complex128
+    blocks of k = 2, 4 or 8 columns, every column solved as if it were alone while the matrix is read once per iteration for all
+    of them.  param: a ClcgPara (or None).  Returns one SolveInfo per column."""
+    return _multi("clcg_hip_lbicg_sym_multi", A, M, B, param, cplx=True)
+
+
+def clpcg_multi(A, M, B, param) -> list:
+    """Batched complex PCG with the handle's Jacobi diagonal (clcg_hip_lpcg_multi; A.build_jacobi() first).  A column whose sums
+    turn NaN stops with CLCG_NAN_VALUE (the single-vector loop runs to the cap).  As clbicg_sym_multi."""
+    return _multi("clcg_hip_lpcg_multi", A, M, B, param, cplx=True)
 
 
 def lcgs(Afp, Pfp, m, B, n_size, param, instance, *workspaces) -> SolveInfo:
