@@ -301,6 +301,16 @@ int lcg_hip_csr_set_packed(lcg_hip_csr_t A, int mode);
  * with the value stream (-22 % on the headline A.x, bit-identical y).  Returns the number of run blocks of the packed copy
  * (0 before the first product built it, or when there are none); *blocks_out (may be NULL) = all blocks of 64 rows. */
 int64_t lcg_hip_csr_packed_runs(lcg_hip_csr_t A, int64_t *blocks_out);
+/* STRETCHES of run blocks: consecutive full run blocks with the same row length and the same offsets column - row, their entries
+ * one behind the other (the interior of a constant-diagonal system is one stretch).  The four longest (of >= 2 blocks) travel in the
+ * kernel's arguments and their blocks load neither row pointers nor their per-block plan (bit-identical y and carried sums).
+ * mode: 0 off (default), 1 on; LCG_HIP_RUN_STRETCHES=0/1 overrides for the whole process.  OFF by default: on the headline system the
+ * blocks' staggered starts behind their own cold loads serve the value stream better than starting together -- same-box A/B 1542-1555
+ * CG iterations/s without, 1514-1529 with (profiles/run_stretches_ab.txt).  No reference counterpart. */
+int lcg_hip_csr_set_run_stretches(lcg_hip_csr_t A, int mode);
+/* Stretches the packed kernel runs from (0 before the first product built them, when switched off or when there are none);
+ * *blocks_out (may be NULL) = the blocks they cover. */
+int64_t lcg_hip_csr_run_stretches(lcg_hip_csr_t A, int64_t *blocks_out);
 /* Blocks of 64 rows the packed form stores as TEMPLATE blocks: every entry on one of <= 64 diagonals (the union of the rows'), rows of
  * <= 32 entries, and a 64-bit mask per row saying which diagonals the row has -- what a stencil's blocks look like where grid boundaries pass
  * through them.  Like run blocks they stream values only and are bit-identical to the plain row-block kernel.

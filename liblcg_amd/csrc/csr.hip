@@ -546,6 +546,58 @@ __global__ __launch_bounds__(VB) void k_pk_pack(int n, const int *rowptr, const 
     }
 }
 
+// Stretches of run blocks (internal.hpp: RunStretches).  flag[b]: 0 = block b can be in no stretch (not a run block, or the partial
+// last block), L = a full run block of L entries per row, -L = one that CONTINUES the stretch of block b - 1: the same L, row 0's
+// columns those of block b - 1 plus 64 (the same offsets from the block's first row -- and with them the same slot of the diagonal),
+// its entries right behind that block's.  One thread per block: 2 L small reads, once per plan.
+__global__ __launch_bounds__(VB) void k_pk_stretch_flags(int n, int nb, const int *__restrict__ rowptr, const int *__restrict__ col,
+                                                         const int *__restrict__ base, int *__restrict__ flag)
+{
+    const int b = blockIdx.x * VB + threadIdx.x;
+    if (b >= nb) return;
+    const int bs = base[b];
+    int f = 0;
+    if (bs < 0 && bs > -TPL_CODE && (long)b * PK_R + PK_R <= (long)n) {
+        const int L = -1 - bs;
+        f = L;
+        if (b > 0 && base[b - 1] == bs) {
+            const int s = rowptr[(long)b * PK_R], sp = rowptr[(long)(b - 1) * PK_R];
+            bool same = (long)s == (long)sp + (long)PK_R * L;
+            for (int k = 0; k < L && same; k++) same = col[s + k] - PK_R == col[sp + k];
+            if (same) f = -L;
+        }
+    }
+    flag[b] = f;
+}
+
+// Block i writes the table of stretch i (offset of slot k = column(row 0, k) - first row of its first block, at [(k % 4) * Q + k / 4]:
+// the slots of one wavefront of k_spmv_ldsp side by side, zeros behind the L-th; the tables lie behind each other) and leaves
+// out[2 i] = the first entry of the stretch, out[2 i + 1] = the slot whose offset is 0 (every row's diagonal; -1: none), which is
+// what k_pk_pack keeps behind the columns of each of its blocks.
+__global__ __launch_bounds__(64) void k_pk_stretch_fill(RunStretches rs, const int *__restrict__ rowptr, const int *__restrict__ col,
+                                                        int *__restrict__ off, int *__restrict__ out)
+{
+    __shared__ int kd;
+    int o = 0, L = 0, Q = 1, b0 = 0;
+#pragma unroll
+    for (int j = 0; j < RS_MAX; j++) {
+        if (j < (int)blockIdx.x) o += 4 * rs.s[j].Q;
+        if (j == (int)blockIdx.x) { L = rs.s[j].L; Q = rs.s[j].Q; b0 = rs.s[j].b0; }
+    }
+    const long row0 = (long)b0 * PK_R;
+    const int s = rowptr[row0];
+    if (threadIdx.x == 0) kd = -1;
+    __syncthreads();
+    for (int i = threadIdx.x; i < 4 * Q; i += 64) {
+        const int k = i / Q + 4 * (i % Q);
+        const int d = k < L ? col[s + k] - (int)row0 : 0;
+        off[o + i] = d;
+        if (k < L && d == 0) kd = k;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) { out[2 * blockIdx.x] = s; out[2 * blockIdx.x + 1] = kd; }
+}
+
 // NS: gathers a lane keeps in flight.  NS = 8: batches of 8 while they are full, then one by one.
 // NS > 8: the FIRST batch is predicated (slots past the row's end read entry 0 with a zero
 // coefficient), so rows of up to NS*T entries -- 33 entries on 4 lanes are 9 for one lane, 8 for the
@@ -586,7 +638,7 @@ template <bool PUSH, int NS, int BITS, bool DOT = false, int CHE = LdsCfg<double
 __global__ __launch_bounds__(VB) void k_spmv_ldsp(int n, const int *__restrict__ rowptr, const v4i *__restrict__ packed,
                                                   const int *__restrict__ pofs, const int *__restrict__ pbase,
                                                   const double *__restrict__ val, const double *__restrict__ x,
-                                                  double *__restrict__ y, const int *done, PushPlan pp, DotPlan dp)
+                                                  double *__restrict__ y, const int *done, PushPlan pp, DotPlan dp, RunStretches st)
 {
     if (PUSH && (int)blockIdx.x < pp.nblocks) { push_block(pp, blockIdx.x); return; }
     if (PUSH && pp.nrecv > 0 && (int)blockIdx.x >= (int)gridDim.x - pp.nrecv) { recv_block(pp, (int)blockIdx.x - ((int)gridDim.x - pp.nrecv)); return; }
@@ -602,12 +654,112 @@ __global__ __launch_bounds__(VB) void k_spmv_ldsp(int n, const int *__restrict__
     __shared__ __attribute__((aligned(16))) double sval[CH + 2];
     __shared__ __attribute__((aligned(16))) int scol[NG * PER];
     double(*sred)[R] = reinterpret_cast<double(*)[R]>(sval);
-    if (done && *done) return;
-
     const int tid = threadIdx.x;
     const int row0 = bid * R;
-    const int nrows = min(R, n - row0);
     const int rl = tid % R, j0 = tid / R;
+
+    // RUN block (k_pk_meta): every row holds L entries and column(row r, slot k) = column(row 0, slot k) + r.  Nothing but
+    // the values streams; the columns are row 0's L integers, read through the scalar cache (a wavefront is one slot j0 of
+    // 64 rows: its k is uniform), and -- the point -- the x gathers no longer wait for the staged columns: they go out
+    // TOGETHER with the value stream, one memory latency per block instead of two.  Entry order per lane and the order of
+    // the additions are those of the general path below: the same bits.
+    // [s, e): the block's entries; column(row 0, slot k) = bcol[k], or cadd + the stretch's table (stride Q per wavefront); uv: the
+    // lane's u where it does not come from the gathers.
+    // STRETCH: the block is one of a stretch (below) and has not looked at the stop flag yet: it asks for it with the columns and
+    // consults it once everything is requested, before the first LDS store -- a stopped solve's trailing products stay cheap.
+    auto run_block = [&](auto stretch_tag, int s, int e, int nrows, int L, int kd, const int *__restrict__ bcol, int cadd, int Q, double uv) {
+        constexpr bool STRETCH = decltype(stretch_tag)::value;
+        const int bv = s & ~1, cntv = e - bv;
+        const int w = __builtin_amdgcn_readfirstlane(j0);
+        const bool live = rl < nrows;
+        v2d pv[VR];
+#pragma unroll
+        for (int r = 0; r < VR; r++) {
+            const int u = 2 * (tid + r * VB);
+            // (non-temporal value loads, so that the stream would not push x out of the L2: 581 vs 520 us -- measured and removed)
+            pv[r] = *reinterpret_cast<const v2d *>(val + (long)bv + (u < cntv ? u : 0));
+        }
+        // (a stretch: the wavefront's slots lie side by side in the stretch's table, zeros behind the L-th -- read unconditionally, in
+        //  one request, the stop flag with them)
+        int stop = 0, cs[UNR];
+        const int *__restrict__ tw = bcol + (STRETCH ? w * Q : 0);
+        if constexpr (STRETCH) {
+            if (done) stop = *done;
+#pragma unroll
+            for (int q = 0; q < UNR; q++) cs[q] = tw[q];
+        }
+        double xv[UNR];
+#pragma unroll
+        for (int q = 0; q < UNR; q++) {
+            const int k = w + q * T;                     // uniform
+            const int c0 = STRETCH ? cs[q] + cadd : bcol[k < L ? k : 0];    // scalar load
+            xv[q] = x[(k < L && live) ? c0 + rl : 0];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (STRETCH && stop) return;                    // uniform
+#pragma unroll
+        for (int r = 0; r < VR; r++) {
+            const int u = 2 * (tid + r * VB);
+            if (u < cntv) *reinterpret_cast<v2d *>(sval + u) = pv[r];
+        }
+        __syncthreads();
+        double acc = 0.0;
+        const int rs0 = s + rl * L - bv;                   // first entry of this lane's row in the staged values
+        double *sud = reinterpret_cast<double *>(scol);     // (a run block stages no columns: its u, where the diagonal is among the gathers)
+        if (live) {
+#pragma unroll
+            for (int q = 0; q < UNR; q++) {
+                const int k = w + q * T;
+                acc = k < L ? fma(sval[rs0 + k], xv[q], acc) : acc;
+                if (DOT && k == kd) sud[rl] = xv[q];        // (uniform: one wavefront, one q)
+            }
+            for (int k = w + UNR * T; k < L; k += T) {
+                const double xk = x[(STRETCH ? tw[k / T] + cadd : bcol[k]) + rl];
+                acc = fma(sval[rs0 + k], xk, acc);
+                if (DOT && k == kd) sud[rl] = xk;
+            }
+        }
+        __syncthreads();
+        sred[j0][rl] = acc;
+        __syncthreads();
+        if (DOT && kd >= 0 && j0 == 0 && live) uv = sud[rl];
+        double vfin = 0.0;
+        if (j0 == 0 && live) {
+            double v = sred[0][rl];
+#pragma unroll
+            for (int j = 1; j < T; j++) v += sred[j][rl];
+            y[row0 + rl] = v;
+            vfin = v;
+        }
+        if (DOT) ldsp_dot_tail(dp, bid, j0, vfin, uv);
+    };
+
+    if constexpr (RR == 64) {
+        // A block of a STRETCH (k_pk_stretch_flags) loads no row pointer, no pofs / pbase and no columns of its own: its entries, its
+        // L and the slot of its diagonal follow from its number and the stretch's few numbers in the kernel arguments (scalar
+        // arithmetic), its columns from the stretch's offsets -- one table for all its blocks, hot in the scalar cache.  The value
+        // loads wait for no load at all, the gathers for the hot table only; from the first LDS store on it is a run block like any other.
+        static_assert(T == 4, "the stretches' tables are laid out for four wavefronts per block");
+        RunStretch me = st.s[0];        // (all four read at once, chosen by selects: no dependent loads)
+#pragma unroll
+        for (int i = 1; i < RS_MAX; i++) {
+            const RunStretch c = st.s[i];
+            const bool in = bid >= c.b0 && bid < c.b1;
+            me.b0 = in ? c.b0 : me.b0; me.b1 = in ? c.b1 : me.b1; me.s0 = in ? c.s0 : me.s0; me.L = in ? c.L : me.L;
+            me.kd = in ? c.kd : me.kd; me.Q = in ? c.Q : me.Q; me.off = in ? c.off : me.off;
+        }
+        if (bid >= me.b0 && bid < me.b1) {       // uniform
+            const int s = me.s0 + (bid - me.b0) * (R * me.L);
+            const int kd = (DOT && dp.ux) ? me.kd : -1;
+            double uv = 0.0;
+            if (DOT && kd < 0) uv = dp.u[j0 == 0 ? row0 + rl : 0];
+            run_block(std::true_type{}, s, s + R * me.L, R, me.L, kd, me.off, row0, me.Q, uv);
+            return;
+        }
+    }
+    if (done && *done) return;
+
+    const int nrows = min(R, n - row0);
     const int s = rowptr[row0], e = rowptr[row0 + nrows];
     const int dof = RR == 64 ? 1 : dp.dof;             // (uniform; groups of consecutive columns are a shape of the long-row blocks)
     const int cnt = e - s, ng = (cnt + PER * dof - 1) / (PER * dof);
@@ -707,66 +859,8 @@ __global__ __launch_bounds__(VB) void k_spmv_ldsp(int n, const int *__restrict__
         if (DOT) ldsp_dot_tail(dp, bid, j0, vfin, uv);
         return;
     }
-    if (RR == 64 && bs < 0) {
-        // RUN block (k_pk_meta): every row holds L entries and column(row r, slot k) = column(row 0, slot k) + r.  Nothing but
-        // the values streams; the columns are row 0's L integers, read through the scalar cache (a wavefront is one slot j0 of
-        // 64 rows: its k is uniform), and -- the point -- the x gathers no longer wait for the staged columns: they go out
-        // TOGETHER with the value stream, one memory latency per block instead of two.  Entry order per lane and the order of
-        // the additions are those of the general path below: the same bits.
-        const int L = -1 - bs;
-        const int w = __builtin_amdgcn_readfirstlane(j0);
-        const int *bcol = reinterpret_cast<const int *>(packed + po);
-        const bool live = rl < nrows;
-        v2d pv[VR];
-#pragma unroll
-        for (int r = 0; r < VR; r++) {
-            const int u = 2 * (tid + r * VB);
-            // (non-temporal value loads, so that the stream would not push x out of the L2: 581 vs 520 us -- measured and removed)
-            pv[r] = *reinterpret_cast<const v2d *>(val + (long)bv + (u < cntv ? u : 0));
-        }
-        double xv[UNR];
-#pragma unroll
-        for (int q = 0; q < UNR; q++) {
-            const int k = w + q * T;                     // uniform
-            const int c0 = bcol[k < L ? k : 0];           // scalar load
-            xv[q] = x[(k < L && live) ? c0 + rl : 0];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int r = 0; r < VR; r++) {
-            const int u = 2 * (tid + r * VB);
-            if (u < cntv) *reinterpret_cast<v2d *>(sval + u) = pv[r];
-        }
-        __syncthreads();
-        double acc = 0.0;
-        const int rs = s + rl * L - bv;                    // first entry of this lane's row in the staged values
-        double *sud = reinterpret_cast<double *>(scol);     // (a run block stages no columns: its u, where the diagonal is among the gathers)
-        if (live) {
-#pragma unroll
-            for (int q = 0; q < UNR; q++) {
-                const int k = w + q * T;
-                acc = k < L ? fma(sval[rs + k], xv[q], acc) : acc;
-                if (DOT && k == kd) sud[rl] = xv[q];        // (uniform: one wavefront, one q)
-            }
-            for (int k = w + UNR * T; k < L; k += T) {
-                const double xk = x[bcol[k] + rl];
-                acc = fma(sval[rs + k], xk, acc);
-                if (DOT && k == kd) sud[rl] = xk;
-            }
-        }
-        __syncthreads();
-        sred[j0][rl] = acc;
-        __syncthreads();
-        if (DOT && kd >= 0 && j0 == 0 && live) uv = sud[rl];
-        double vfin = 0.0;
-        if (j0 == 0 && live) {
-            double v = sred[0][rl];
-#pragma unroll
-            for (int j = 1; j < T; j++) v += sred[j][rl];
-            y[row0 + rl] = v;
-            vfin = v;
-        }
-        if (DOT) ldsp_dot_tail(dp, bid, j0, vfin, uv);
+    if (RR == 64 && bs < 0) {       // RUN block (above), its plan loaded per block
+        run_block(std::false_type{}, s, e, nrows, -1 - bs, kd, reinterpret_cast<const int *>(packed + po), 0, 0, uv);
         return;
     }
 
@@ -1142,6 +1236,63 @@ __global__ __launch_bounds__(RUN1D_WG) void k_spmv_run1d(int n, int LP, const in
 // runs_only (k_spmv_run1, short rows): only the run blocks get anything -- row 0's columns; the other blocks are walked
 // from the CSR arrays -- so the copy costs a few integers per block, and small systems take it too (pk_state = 2).
 
+static bool run_stretches_on(const CsrPart &P)
+{
+    static const int env = [] { const char *e = std::getenv("LCG_HIP_RUN_STRETCHES"); return e ? atoi(e) : -1; }();      // A/B runs: 0 / 1 for the whole process
+    return (env >= 0 ? env : P.rs_mode) != 0;
+}
+
+static void run_stretches_free(const CsrPart &P)
+{
+    if (P.pk_rs_off) hipFree(P.pk_rs_off);
+    P.pk_rs_off = nullptr; P.pk_rs = RunStretches(); P.pk_rs_blocks = 0; P.pk_rs_groups = 0;
+}
+
+// The (up to RS_MAX) longest stretches of at least two blocks, from the flags of k_pk_stretch_flags (read back once: 4 bytes per block);
+// their offset tables and the two numbers the host does not know (first entry, slot of the diagonal) come from k_pk_stretch_fill.
+// A plan without stretches is still a plan: nothing here fails the build.
+static void run_stretches_build(const CsrPart &P, hipStream_t s, const std::vector<int> &flag)
+{
+    struct St { int b0, b1, L; };
+    std::vector<St> all;
+    const int nb = (int)flag.size();
+    for (int b = 0; b < nb;) {
+        if (flag[b] <= 0) { b++; continue; }
+        int e = b + 1;
+        while (e < nb && flag[e] == -flag[b]) e++;
+        if (e - b >= 2) all.push_back({b, e, flag[b]});
+        b = e;
+    }
+    if (all.empty()) return;
+    std::stable_sort(all.begin(), all.end(), [](const St &a, const St &c) { return a.b1 - a.b0 > c.b1 - c.b0; });
+    if (all.size() > (size_t)RS_MAX) all.resize(RS_MAX);
+    std::sort(all.begin(), all.end(), [](const St &a, const St &c) { return a.b0 < c.b0; });
+    RunStretches rs;
+    rs.n = (int)all.size();
+    int ints = 0;
+    for (int i = 0; i < rs.n; i++) {
+        rs.s[i].b0 = all[i].b0; rs.s[i].b1 = all[i].b1; rs.s[i].L = all[i].L; rs.s[i].Q = std::max(RS_QMIN, (all[i].L + 3) / 4);
+        ints += 4 * rs.s[i].Q;
+    }
+    int h[2 * RS_MAX];
+    bool ok = hipMalloc(&P.pk_rs_off, sizeof(int) * ((size_t)ints + 2 * RS_MAX)) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(k_pk_stretch_fill, dim3(rs.n), dim3(64), 0, s, rs, P.rowptr, P.col, P.pk_rs_off, P.pk_rs_off + ints);
+        ok = hipMemcpyAsync(h, P.pk_rs_off + ints, sizeof(int) * 2 * rs.n, hipMemcpyDeviceToHost, s) == hipSuccess &&
+             hipStreamSynchronize(s) == hipSuccess;
+    }
+    if (!ok) { (void)hipGetLastError(); run_stretches_free(P); return; }
+    int o = 0;
+    for (int i = 0; i < rs.n; i++) {
+        RunStretch &r = rs.s[i];
+        r.s0 = h[2 * i]; r.kd = h[2 * i + 1]; r.off = P.pk_rs_off + o;
+        o += 4 * r.Q;
+        P.pk_rs_blocks += r.b1 - r.b0;
+        P.pk_rs_groups += (long)(r.b1 - r.b0) * ((r.L + 1 + 3) / 4);
+    }
+    P.pk_rs = rs;
+}
+
 static bool packed_build(const CsrPart &P, hipStream_t s, bool runs_only, int R = PK_R)
 {
     if (P.pk_state != 0) return P.pk_state == (runs_only ? 2 : 1) && P.pk_R == R;
@@ -1153,7 +1304,9 @@ static bool packed_build(const CsrPart &P, hipStream_t s, bool runs_only, int R 
     PlanTimer timer(P, s);
     const int n = P.n_rows;
     const int nb = (n + R - 1) / R;
-    int *ngr = nullptr, *span = nullptr;
+    int *ngr = nullptr, *span = nullptr, *sflag = nullptr;
+    std::vector<int> hflag;
+    const bool stretches = !runs_only && R == PK_R && run_stretches_on(P);      // (looked for only where they are switched on)
     long total = 0;
     int hspan[4] = {0, 0, 0, 0};
     int dof = 1;
@@ -1174,6 +1327,11 @@ static bool packed_build(const CsrPart &P, hipStream_t s, bool runs_only, int R 
     if (ok) {
         // (k_pk_meta: 0 no run blocks, 1 run blocks and template blocks, 2 run blocks only)
         hipLaunchKernelGGL(k_pk_meta, dim3(nb), dim3(64), 0, s, n, P.rowptr, P.col, P.pk_base, ngr, span, R == PK_R ? 1 : 0, R);
+        if (stretches && hipMalloc(&sflag, sizeof(int) * (size_t)nb) == hipSuccess) {       // (read back with the block statistics: one wait for both)
+            hflag.resize(nb);
+            hipLaunchKernelGGL(k_pk_stretch_flags, dim3((nb + VB - 1) / VB), dim3(VB), 0, s, n, nb, P.rowptr, P.col, P.pk_base, sflag);
+            if (hipMemcpyAsync(hflag.data(), sflag, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost, s) != hipSuccess) { (void)hipGetLastError(); hflag.clear(); }
+        }
         ok = hipMemcpyAsync(hspan, span, 4 * sizeof(int), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
     }
     if (ok) ok = runs_only ? 2L * (hspan[2] + hspan[3]) >= nb : hspan[0] < PK_SPAN;     // runs only: worth it when most blocks are runs or templates
@@ -1195,6 +1353,7 @@ static bool packed_build(const CsrPart &P, hipStream_t s, bool runs_only, int R 
     }
     if (ngr) hipFree(ngr);
     if (span) hipFree(span);
+    if (sflag) hipFree(sflag);
     if (!ok) {
         (void)hipGetLastError();
         if (P.pk_base) hipFree(P.pk_base);
@@ -1211,6 +1370,7 @@ static bool packed_build(const CsrPart &P, hipStream_t s, bool runs_only, int R 
     P.pk_R = R;
     P.pk_dof = dof;
     P.pk_state = runs_only ? 2 : 1;
+    if (!hflag.empty() && hspan[2] > 1) run_stretches_build(P, s, hflag);
     return true;
 }
 static bool packed_ready(const CsrPart &P, hipStream_t s, int R = PK_R) { return packed_build(P, s, false, R); }
@@ -1302,7 +1462,7 @@ static void ldsp_launch(const AxChoice &c, const CsrPart &P, const double *x, do
             pick<PK_CH_8, PK_CH_7, PK_CH_SMALL, LdsCfg<double>::CH>(c.win, [&](auto win) {
                 hipLaunchKernelGGL((k_spmv_ldsp<PUSH, decltype(ns)::value, decltype(bits)::value, DOT, decltype(win)::value, RR>), dim3(g),
                                    dim3(VB), 0, s, P.n_rows, P.rowptr, static_cast<const v4i *>(P.pk_data), P.pk_ofs, P.pk_base, P.val,
-                                   x, y, done, pp, dp);
+                                   x, y, done, pp, dp, run_stretches_on(P) ? P.pk_rs : RunStretches());
             });
         });
     };
@@ -1617,6 +1777,7 @@ void free_part(CsrPart &P)
     if (P.pk_base) hipFree(P.pk_base);
     if (P.pk_ofs) hipFree(P.pk_ofs);
     if (P.pk_data) hipFree(P.pk_data);
+    run_stretches_free(P);
     if (P.dot_part) hipFree(P.dot_part);
     P = CsrPart();
 }
@@ -1721,6 +1882,7 @@ int lcg_hip_csr_set_packed(lcg_hip_csr_t A, int mode)
             if (ctx().inited) (void)hipDeviceSynchronize();
             hipFree(P->pk_base); hipFree(P->pk_ofs); hipFree(P->pk_data);
             P->pk_base = P->pk_ofs = nullptr; P->pk_data = nullptr;
+            run_stretches_free(*P);
         }
         if (P->pk_state < 0 || mode == 0) P->pk_state = 0;     // decide again at the next product
     }
@@ -1809,6 +1971,38 @@ int64_t lcg_hip_csr_packed_runs(lcg_hip_csr_t A, int64_t *blocks_out)
     return P.pk_state > 0 ? P.pk_runs : 0;
 }
 
+int lcg_hip_csr_set_run_stretches(lcg_hip_csr_t A, int mode)
+{
+    NOT_DENSE(A, LCG_HIP_E_ARG);
+    if (!A || mode < 0 || mode > 1) return LCG_HIP_E_ARG;
+    TRY_C64(A, "lcg_hip_csr_set_run_stretches");
+    for (CsrPart *P : {&A->main, &A->loc}) {
+        P->rs_mode = mode;
+        ranges_free(*P);                    // the ranges inherit the modes: cut again at the next product
+        if (mode == 1 && P->pk_state == 1 && P->pk_rs.n == 0) {     // a plan built without looking for stretches: build it again at the next product
+            if (ctx().inited) (void)hipDeviceSynchronize();
+            hipFree(P->pk_base); hipFree(P->pk_ofs); hipFree(P->pk_data);
+            P->pk_base = P->pk_ofs = nullptr; P->pk_data = nullptr;
+            P->pk_state = 0;
+        }
+    }
+    return 0;
+}
+
+// the stretches a part's k_spmv_ldsp runs from, as things stand
+static bool stretches_in_use(const CsrPart &P) { return P.pk_state == 1 && run_stretches_on(P) && P.pk_rs.n > 0; }
+
+int64_t lcg_hip_csr_run_stretches(lcg_hip_csr_t A, int64_t *blocks_out)
+{
+    NOT_DENSE(A, LCG_HIP_E_ARG);
+    if (blocks_out) *blocks_out = 0;
+    if (!A) return 0;
+    const CsrPart &P = A->distributed ? A->loc : A->main;
+    if (!stretches_in_use(P)) return 0;
+    if (blocks_out) *blocks_out = P.pk_rs_blocks;
+    return P.pk_rs.n;
+}
+
 static int64_t part_traffic_model(const CsrPart &P)
 {
     const char *k = P.last_kernel;
@@ -1826,8 +2020,14 @@ static int64_t part_traffic_model(const CsrPart &P)
     if (std::strncmp(k, "k_lr_", 5) == 0) return 12 * P.nnz + vectors;       // CSR as it is, the chunk lists are small
     if (std::strncmp(k, "k_bin_", 6) == 0) return binned_traffic_bytes(P);
     if (std::strncmp(k, "k_tile", 6) == 0) return tiled_traffic_bytes(P);
-    if (std::strncmp(k, "k_spmv_ldsp", 11) == 0)       // values + packed columns (run blocks: row 0's columns only) + two words per block
-        return 8 * P.nnz + 16 * (int64_t)P.pk_groups + 8 * nb + vectors;
+    if (std::strncmp(k, "k_spmv_ldsp", 11) == 0) {     // values + packed columns (run blocks: row 0's columns only) + two words per block
+        int64_t b = 8 * P.nnz + 16 * (int64_t)P.pk_groups + 8 * nb + vectors;
+        if (stretches_in_use(P)) {          // their blocks read no row pointers, no two words, no columns of their own: one table per stretch instead
+            b -= (4 * PK_R + 8) * (int64_t)P.pk_rs_blocks + 16 * (int64_t)P.pk_rs_groups;
+            for (int i = 0; i < P.pk_rs.n; i++) b += 16 * P.pk_rs.s[i].Q;
+        }
+        return b;
+    }
     if (std::strncmp(k, "k_spmv_run1", 11) == 0) {     // values + row 0's columns of the run blocks + the CSR columns of the other blocks
         const double other = nb > 0 ? 1.0 - (double)(P.pk_runs + P.pk_tpls) / (double)nb : 1.0;
         return 8 * P.nnz + (int64_t)(4.0 * other * (double)P.nnz) + 16 * (int64_t)P.pk_groups + 8 * nb + vectors;
@@ -1859,6 +2059,7 @@ int lcg_hip_csr_plan_info(lcg_hip_csr_t A, double *build_ms, int64_t *extra_byte
     int64_t b = 0;
     auto add = [&](const CsrPart &Q) {
         if (Q.pk_state > 0) b += 16 * ((int64_t)Q.pk_groups + 4) + 8 * (((int64_t)Q.n_rows + Q.pk_R - 1) / Q.pk_R + 1);
+        for (int i = 0; i < Q.pk_rs.n; i++) b += 16 * Q.pk_rs.s[i].Q;      // the stretches' tables
         if (Q.bn_plan) b += (int64_t)binned_plan_bytes(Q);
         if (Q.tl_plan) b += (int64_t)tiled_plan_bytes(Q);
     };

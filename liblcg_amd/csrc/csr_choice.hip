@@ -456,7 +456,7 @@ bool ranges_chosen(const CsrPart &P, hipStream_t s)
         V.n_rows = r1 - r0; V.nnz = cut[i + 1] - cut[i]; V.rowptr = P.rowptr + r0; V.col = P.col; V.val = P.val;
         V.owned = false; V.padded = r1 < n ? true : P.padded;       // (behind an inner range lies the next range)
         V.end_abs = cut[i + 1]; V.n_cols = P.n_cols;
-        V.pk_mode = P.pk_mode; V.bn_mode = P.bn_mode; V.tl_mode = P.tl_mode; V.rg_mode = 0; V.rg_state = -1;
+        V.pk_mode = P.pk_mode; V.rs_mode = P.rs_mode; V.bn_mode = P.bn_mode; V.tl_mode = P.tl_mode; V.rg_mode = 0; V.rg_state = -1;
         // a stretch classed as scattered takes the binned product where it is eligible at all (its own mean span may sit just
         // under the whole-matrix threshold: the class was decided chunk by chunk)
         // (not for a short stretch: 200,000 scattered rows of a 1M-row matrix went from 86 to 176 us per product that way -- the binned

@@ -101,6 +101,23 @@ struct DotPlan {
     int dof = 1;            // k_spmv_ldsp, long rows: a packed column field stands for `dof` consecutive columns (csr.hip: k_pk_dof)
 };
 
+// Stretches of run blocks (csr.hip: k_pk_stretch / the stretch path of k_spmv_ldsp): consecutive full 64-row run blocks [b0, b1) with the
+// same L, the same offsets column(row 0, k) - first row and entries that follow each other without a gap.  A block of a stretch
+// derives everything it would load from the per-block plan from its number: it travels in the kernel arguments like the two plans above.
+constexpr int RS_MAX = 4;
+constexpr int RS_QMIN = 12;         // slots per wavefront a table holds at least: the largest first batch of k_spmv_ldsp reads them unconditionally
+struct RunStretch {                 // 32 bytes: one scalar load
+    int b0 = 0, b1 = 0;             // blocks [b0, b1) (an unused one is empty)
+    int s0 = 0;                     // first entry of block b0
+    int L = 0, kd = -1;             // entries per row; slot of the diagonal (offset 0) or -1
+    int Q = 0;                      // the offset of slot k lies at off[(k % 4) * Q + k / 4]: wavefront w's slots w, w + 4, ... side by side (zeros behind the L-th)
+    const int *off = nullptr;       // the table, one per stretch (device)
+};
+struct RunStretches {
+    RunStretch s[RS_MAX];
+    int n = 0;
+};
+
 struct DevState;
 
 // Mirror of the stop state in host-mapped pinned memory; written by the scalar kernels,
@@ -255,6 +272,10 @@ struct CsrPart {
     mutable int pk_runs = 0;                                // blocks stored as runs (row 0's columns only; csr.hip: k_pk_meta)
     mutable int pk_tpls = 0;                                // blocks stored as templates (<= 32 diagonals + a mask per row)
     mutable long pk_groups = 0;                             // 16-byte groups of the packed columns
+    mutable int rs_mode = 0;                                // run stretches: 0 (default: measured slower) every run block loads its per-block plan, 1 the blocks of a stretch do not
+    mutable RunStretches pk_rs;                             // the (up to four) longest stretches of run blocks, found with the packed form
+    mutable int *pk_rs_off = nullptr;                       // their offset tables
+    mutable long pk_rs_blocks = 0, pk_rs_groups = 0;        // blocks they cover; 16-byte groups of per-block columns those blocks no longer read
     mutable double *dot_part = nullptr;                     // [2][dot_cap]: per-block (per-chunk) sums of a product that carries its dot (k_spmv_ldsp<DOT>, k_tile_spmv2<DOT>)
     mutable long dot_cap = 0;
     // two-pass "binned" product for scattered columns (csr_binned.hip), plan built on first use
