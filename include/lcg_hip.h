@@ -108,7 +108,15 @@ typedef int (*clcg_hip_progress_c64_ptr)(void *instance, const float *m, const f
 
 /* ------------------------------------------------------- runtime / stream */
 int  lcg_hip_init(int device);                 /* selects the device; idempotent. */
-int  lcg_hip_set_stream(void *hip_stream);     /* NULL = the library's own stream */
+/* lcg_hip_set_stream: NULL = the library's own stream.  Two rules:
+ *   1. a stream other than the current one waits (one event, on the device: nothing is drained, the host does not wait) for
+ *      everything the library has enqueued on the previous stream, so work enqueued after the switch never overtakes work
+ *      enqueued before it -- the enqueue-only entries share scratch per handle and per context.  Setting the current stream
+ *      again does nothing;
+ *   2. the previous stream must still exist at the call: switch away from a stream BEFORE destroying it.
+ * Work that OTHERS put on either stream is the caller's to order.  hip_stream is a stream the caller created (hipStreamCreate*);
+ * the runtime's special handles hipStreamLegacy / hipStreamPerThread are not accepted (events cannot be recorded on them). */
+int  lcg_hip_set_stream(void *hip_stream);
 void *lcg_hip_get_stream(void);                /* stream callbacks must launch on */
 int  lcg_hip_synchronize(void);   /* also where a timed-out direct exchange (multi-GPU) surfaces: LCG_HIP_E_COMM */
 /* Blocking copy on the library stream.  kind: 1 host->device, 2 device->host, 3 device->device

@@ -63,6 +63,11 @@ def use_torch_stream():
     _chk(L.load().lcg_hip_set_stream(C.c_void_p(torch.cuda.current_stream().cuda_stream)), "set_stream")
 
 
+def use_own_stream():
+    """Back to the library's own stream (lcg_hip_set_stream(NULL)); it waits for what was enqueued on the previous one."""
+    _chk(L.load().lcg_hip_set_stream(None), "set_stream")
+
+
 class CsrMatrix:
     """An HBM-resident CSR matrix (handle ``lcg_hip_csr_t``)."""
     is_c64 = False      # values are complex64 (from_csr_c64)

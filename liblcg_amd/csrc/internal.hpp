@@ -157,7 +157,8 @@ struct Ctx {
     hipStream_t own_stream = nullptr;  // created by the library
     hipStream_t comm_stream = nullptr; // second stream for gather/compute overlap
     hipEvent_t ev_a = nullptr, ev_b = nullptr;
-    double *partials = nullptr;        // [MAXR][MAXG]: the table the latest reducing pass wrote (one of partials_pair)
+    hipEvent_t ev_switch = nullptr;    // lcg_hip_set_stream: the new stream waits for the previous one's queue (made at the first switch)
+    double *partials = nullptr;       // [MAXR][MAXG]: the table the latest reducing pass wrote (one of partials_pair)
     DevState *state = nullptr;         // the state the next kernel is handed (one of state_pair: driver.hpp, vecf)
     double *partials_pair[2] = {nullptr, nullptr};
     double *ax_partials = nullptr;     // [2][AXP_CAP]: the sums an A.x kernel carried (csr.hip: k_spmv_lds1d), see PartCount

@@ -179,7 +179,15 @@ int lcg_hip_set_stream(void *s)
 {
     int rc = ensure_init(); if (rc) return rc;
     Ctx &c = ctx();
-    c.stream = s ? static_cast<hipStream_t>(s) : c.own_stream;
+    hipStream_t next = s ? static_cast<hipStream_t>(s) : c.own_stream;
+    if (next == c.stream) return 0;
+    // Most entries only enqueue, and they share scratch per handle and per context (a factor's tmp, a plan's expand buffer, the
+    // partial sums): work on the new stream must not overtake what is still queued on the previous one.  One marker there, one
+    // wait here; nothing is drained and the host does not wait.
+    if (!c.ev_switch) HIPCHK(hipEventCreateWithFlags(&c.ev_switch, hipEventDisableTiming));
+    HIPCHK(hipEventRecord(c.ev_switch, c.stream));
+    HIPCHK(hipStreamWaitEvent(next, c.ev_switch, 0));
+    c.stream = next;
     return 0;
 }
 
