@@ -562,6 +562,40 @@ const char *lcg_hip_dense_kernel_name(int index);
  * fewer than 32 16-byte packs, or M >= 8192).  K^T.x has one form (3 is accepted and changes nothing).  A forced path holds for the
  * products it names; the others stay automatic. */
 int lcg_hip_dense_set_kernel(lcg_hip_dense_t K, int variant);
+/* The same products over k = 2, 4 or 8 right-hand sides with K read ONCE for all of them.  A block of k vectors is
+ * lcg_hip_spmm's: one array of rows x k doubles, row-major (X[i * k + j] = row i of column j), its base 16-byte aligned.  Any other k,
+ * a null block or a misaligned base: LCG_HIP_E_ARG before the device or the handle is looked at.  Real fp64 dense handles on one GPU:
+ * a handle that is not a dense one (a CSR handle included), a complex dense handle, a layout outside 0 / 1, normal = 0 on a
+ * non-square K, or X and Y overlapping return LCG_HIP_E_ARG with lcg_hip_last_error() naming the entry and the reason, Y untouched.
+ * Column j's bits depend on K, the handle's forced variant and column j of X (and U) alone: the same whatever k is, whatever the
+ * other columns hold (NaN and Inf included), from call to call.  They need not be the bits of lcg_hip_dense_matvec on that column.
+ * lcg_hip_dense_set_kernel's variants 1 / 2 force the k-wide row form / split row form as they do for K.x; 4 - 6 are not looked at.
+ * The M x k block between the two products of K^T.(K.X) and the k-wide table of partial sums belong to the handle: the first call at
+ * a k larger than any before may allocate and wait, later ones only launch; lcg_hip_dense_destroy frees them. */
+/* Y = K.X (layout 0: X is N x k, Y is M x k) or Y = K^T.X (layout 1: X is M x k, Y is N x k), K read once for all k columns. */
+int lcg_hip_dense_matmat(lcg_hip_dense_t K, int k, const double *X, double *Y, int layout);
+/* Y[N x k] = K^T.(K.X): two passes over K; the M x k block in between belongs to the handle. */
+int lcg_hip_dense_ata_multi(lcg_hip_dense_t K, int k, const double *X, double *Y);
+/* The operator of the batched loops with the sum they take after it: Y = (normal ? K^T.K : K).X and, with U != NULL,
+ * dots[j] = Y_j . U_j (host, k values, after a stream synchronise; NULL dots = enqueue only).  normal = 0 needs square K.  The sum
+ * costs no pass over K: one k-wide launch over Y and U leaves at most 512 partial sums per column, added in a fixed order. */
+int lcg_hip_dense_op_multi_dot(lcg_hip_dense_t K, int k, int normal, const double *X, double *Y, const double *U, double *dots);
+/* Name of the k-wide kernel family the latest k-wide product with K used ("" before the first), and the list of all of them
+ * (index 0, 1, ...; NULL behind the last): k_dnm_row, k_dnm_row_split, k_dnm_col, k_dnm_ata_two_pass.  The single-vector names
+ * (lcg_hip_dense_last_kernel, lcg_hip_dense_kernel_name) are not touched by the k-wide products. */
+const char *lcg_hip_dense_multi_last_kernel(lcg_hip_dense_t K);
+const char *lcg_hip_dense_multi_kernel_name(int index);
+/* Batched CG and PCG on a dense handle: lcg_hip_lcg_multi / lcg_hip_lpcg_multi's loop, contract and codes, word for word, with the
+ * operator A = K^T.K (normal = 1: sample1.cpp's CalAx, the normal equations) or A = K (normal = 0, square K).  M (in/out) and B are
+ * N x k blocks where `mem` says.  PCG uses the reciprocals of lcg_hip_dense_build_jacobi(K, normal, ...): none built, or built for
+ * the other operator, returns LCG_NULL_PRECONDITION_MATRIX.  Per iteration K is read twice (normal = 1) or once for all k columns.
+ * Column j's results depend on K, column j of B and M and param alone, bit for bit: whatever k is, whatever the other columns hold,
+ * from call to call.  lcg_hip_last_launches counts every kernel of the operator (its products, folds and the carried sum) as a
+ * product. */
+int lcg_hip_dense_lcg_multi (lcg_hip_dense_t K, int k, int normal, double *M, const double *B, const lcg_para *param,
+                             int *ret, int *iterations, double *residual, int mem);
+int lcg_hip_dense_lpcg_multi(lcg_hip_dense_t K, int k, int normal, double *M, const double *B, const lcg_para *param,
+                             int *ret, int *iterations, double *residual, int mem);
 
 /* ---------------------------------------------------------------- kernels */
 /* Stand-alone launches of the hot-path kernels on the current stream (device pointers).

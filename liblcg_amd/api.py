@@ -394,6 +394,38 @@ class DenseMatrix:
                 return out
             out.append(s.decode()); i += 1
 
+    def matmat(self, X, Y, layout=0):
+        """Y = K.X (layout 0: X (n, k), Y (m, k)) or K^T.X (layout 1: X (m, k), Y (n, k)) for the k = 2, 4 or 8 columns of X with K
+        read once for all of them (lcg_hip_dense_matmat): C-contiguous float64 CUDA tensors, 16-byte aligned.  Real fp64 matrices."""
+        k = _block_k(X, Y)
+        return _chk(L.load().lcg_hip_dense_matmat(self.h, k, _ptr(X)[0], _ptr(Y)[0], layout), "dense_matmat")
+
+    def ata_multi(self, X, Y):
+        """Y = K^T.(K.X) for the k columns of X, K read twice for all of them (lcg_hip_dense_ata_multi).  X, Y: (n, k) blocks."""
+        k = _block_k(X, Y)
+        return _chk(L.load().lcg_hip_dense_ata_multi(self.h, k, _ptr(X)[0], _ptr(Y)[0]), "dense_ata_multi")
+
+    def op_multi_dot(self, X, Y, U, normal=True):
+        """Y = (K^T.K if normal else K).X carrying, per column, the sum the batched loops take after it (lcg_hip_dense_op_multi_dot):
+        returns a float64 array of k, [j] = Y_j . U_j.  X, Y, U: (n, k) blocks."""
+        k = _block_k(X, Y, U)
+        out = (C.c_double * k)()
+        _chk(L.load().lcg_hip_dense_op_multi_dot(self.h, k, int(normal), _ptr(X)[0], _ptr(Y)[0], _ptr(U)[0], out), "dense_op_multi_dot")
+        return np.array(out[:], dtype=np.float64)
+
+    @property
+    def multi_last_kernel(self) -> str:
+        return L.load().lcg_hip_dense_multi_last_kernel(self.h).decode()
+
+    @staticmethod
+    def multi_kernel_names():
+        lib, out, i = L.load(), [], 0
+        while True:
+            s = lib.lcg_hip_dense_multi_kernel_name(i)
+            if s is None:
+                return out
+            out.append(s.decode()); i += 1
+
     def destroy(self):
         if self.h:
             L.load().lcg_hip_dense_destroy(self.h)
@@ -534,6 +566,18 @@ def lpcg_multi(A, M, B, param, precond="jacobi") -> list:
     if precond == "jacobi":
         return _multi("lcg_hip_lpcg_multi", A, M, B, param)
     return _multi("lcg_hip_lpcg_multi_m", A, M, B, param, PRECONDS[precond])
+
+
+def dense_lcg_multi(K, M, B, param, normal=True) -> list:
+    """Batched CG on a dense matrix (lcg_hip_dense_lcg_multi): the operator is K^T.K (normal: sample1's normal equations) or K
+    (square); M (in/out) and B are (n, k) blocks of k = 2, 4 or 8 columns, every column solved as if it were alone while K is read
+    once per product for all of them.  Returns one SolveInfo per column, as lcg_multi."""
+    return _multi("lcg_hip_dense_lcg_multi", K, M, B, param, int(normal))
+
+
+def dense_lpcg_multi(K, M, B, param, normal=True) -> list:
+    """Batched PCG on a dense matrix with the reciprocals of K.build_jacobi(normal) (lcg_hip_dense_lpcg_multi).  As dense_lcg_multi."""
+    return _multi("lcg_hip_dense_lpcg_multi", K, M, B, param, int(normal))
 
 
 def lbicgstab_multi(A, M, B, param, precond=None) -> list:

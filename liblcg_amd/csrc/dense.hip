@@ -16,28 +16,12 @@
 #include <cstdarg>
 #include <cstring>
 
-#include "internal.hpp"
-
-struct lcg_hip_dense {
-    uint64_t kind = lcgh::KIND_DENSE;   // internal.hpp: the word both kinds of handle begin with
-    int M = 0, N = 0;
-    bool cplx = false;
-    int64_t ldp = 0;            // packs per stored row
-    int NP = 0;                 // packs that hold a row's entries: N (c128) or ceil(N / 2)
-    double2 *val = nullptr;     // M * ldp packs + slack
-    double *t = nullptr;        // the M-vector between the two products of K^T.K.x
-    double *part = nullptr;     // the partial-sum table
-    int64_t part_doubles = 0;
-    double *invdiag = nullptr;  // N (or 2 N) doubles after lcg_hip_dense_build_jacobi
-    int variant = 0;
-    const char *last_kernel = "";
-};
+#include "dense.hpp"
 
 namespace lcgh {
 
 static const char *const DN_NAMES[] = {"k_dn_row", "k_dn_row_split", "k_dn_col", "k_dn_ata_two_pass", "k_dn_ata_one_pass",
                                        "k_dn_ata_small"};
-enum { DN_AUTO = 0, DN_ROW = 1, DN_ROW_SPLIT = 2, DN_COL = 3, DN_ATA2 = 4, DN_ATA1 = 5, DN_ATA_SMALL = 6 };
 
 static int dn_error(const char *fmt, ...)
 {
@@ -46,9 +30,6 @@ static int dn_error(const char *fmt, ...)
     ctx().err = buf;
     return LCG_HIP_E_ARG;
 }
-
-static inline int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double2 ldpack(const double2 *p) { return *p; }
@@ -301,39 +282,8 @@ __global__ __launch_bounds__(256) void k_dn_diag(const double2 *__restrict__ K, 
     else d[i] = row[i];
 }
 
-// ---- plans (pure functions of the shape: the table is sized from them when the handle is made) -----------------------------
-struct RowPlan { int W, S, pps; };
-struct ColPlan { int CW, CT, RS, rps; };
+// ---- plans (pure functions of the shape: the table is sized from them when the handle is made; the row and column plans: dense.hpp)
 struct AtaPlan { int BS, U, RB, CW, G; bool ok; };
-
-// strips of the row form: enough wavefronts for the chip when there are few rows (forced: also where the rows are short)
-static RowPlan row_plan(int M, int NP, bool split, bool forced)
-{
-    RowPlan r;
-    int S = 1;
-    if (split) {
-        const int cap = std::max(1, forced ? NP / 16 : NP / 256);
-        S = std::min((int)cdiv(8192, M), cap);      // 8192 wavefronts: 32 per compute unit
-    }
-    r.pps = (int)cdiv(NP, S);
-    r.S = (int)cdiv(NP, r.pps);
-    r.W = std::min(64, std::max(4, pow2ceil(r.pps)));
-    return r;
-}
-static bool row_split_auto(int M, int NP) { return M < 1024 && row_plan(M, NP, true, false).S >= 2; }
-
-static ColPlan col_plan(int M, int NP)
-{
-    ColPlan c;
-    c.CW = std::min(256, pow2ceil(NP));
-    const int RG = 256 / c.CW;
-    c.CT = (int)cdiv(NP, c.CW);
-    const int rs_max = (int)cdiv(M, (int64_t)RG * 16);      // at least two batches of eight rows per thread
-    const int RS = std::max(1, std::min((int)cdiv(1024, c.CT), rs_max));
-    c.rps = (int)(cdiv(cdiv(M, RS), RG) * RG);
-    c.RS = (int)cdiv(M, c.rps);
-    return c;
-}
 
 static AtaPlan ata_plan(int M, int NP, int N, bool small)
 {
@@ -461,6 +411,7 @@ static void dense_release(lcg_hip_dense *K)
     if (K->t) hipFree(K->t);
     if (K->part) hipFree(K->part);
     if (K->invdiag) hipFree(K->invdiag);
+    dnm_release(K);
     delete K;
 }
 
@@ -634,6 +585,7 @@ int lcg_hip_dense_build_jacobi(lcg_hip_dense_t K, int normal, double *diag_out)
     const int w = K->cplx ? 2 : 1, n = K->N;
     const size_t bytes = sizeof(double) * (size_t)w * (size_t)n;
     if (!K->invdiag) HIPCHK(hipMalloc(&K->invdiag, bytes));
+    K->invdiag_normal = -1;
     std::vector<double> d((size_t)w * n);
     if (normal) {       // one more column-form pass
         int rc = col_product(K, nullptr, K->invdiag, 0, true, c.stream); if (rc) return rc;
@@ -664,6 +616,7 @@ int lcg_hip_dense_build_jacobi(lcg_hip_dense_t K, int normal, double *diag_out)
     }
     HIPCHK(hipMemcpyAsync(K->invdiag, r.data(), bytes, hipMemcpyHostToDevice, c.stream));
     HIPCHK(hipStreamSynchronize(c.stream));
+    K->invdiag_normal = normal;     // (the batched PCG asks: dense_multi.hip)
     return 0;
 }
 

@@ -1,0 +1,79 @@
+// dense.hpp -- what the dense units share (dense.hip: the single-vector products; dense_multi.hip: the k-wide ones): the handle and
+// the plans of the row and column forms.  Not installed.  DESIGN.md sections 14 and 19.
+#pragma once
+
+#include <algorithm>
+
+#include "internal.hpp"
+
+namespace lcgh { struct DenseMulti; }   // dense_multi.hip: the work memory of the k-wide products
+
+struct lcg_hip_dense {
+    uint64_t kind = lcgh::KIND_DENSE;   // internal.hpp: the word both kinds of handle begin with
+    int M = 0, N = 0;
+    bool cplx = false;
+    int64_t ldp = 0;            // packs per stored row
+    int NP = 0;                 // packs that hold a row's entries: N (c128) or ceil(N / 2)
+    double2 *val = nullptr;     // M * ldp packs + slack
+    double *t = nullptr;        // the M-vector between the two products of K^T.K.x
+    double *part = nullptr;     // the partial-sum table
+    int64_t part_doubles = 0;
+    double *invdiag = nullptr;  // N (or 2 N) doubles after lcg_hip_dense_build_jacobi
+    int invdiag_normal = -1;    // which operator the reciprocals belong to: 1 K^T.K, 0 K (-1: none built)
+    int variant = 0;
+    const char *last_kernel = "";
+    lcgh::DenseMulti *multi = nullptr;  // made by the first k-wide product (dense_multi.hip: dnm_reserve), freed with the handle
+};
+
+namespace lcgh {
+
+enum { DN_AUTO = 0, DN_ROW = 1, DN_ROW_SPLIT = 2, DN_COL = 3, DN_ATA2 = 4, DN_ATA1 = 5, DN_ATA_SMALL = 6 };
+
+static inline int pow2ceil(int v) { int p = 1; while (p < v) p <<= 1; return p; }
+static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// ---- plans (pure functions of the shape: the tables are sized from them) ----------------------------------------------------
+struct RowPlan { int W, S, pps; };
+struct ColPlan { int CW, CT, RS, rps; };
+
+// strips of the row form: enough wavefronts for the chip when there are few rows (forced: also where the rows are short)
+static inline RowPlan row_plan(int M, int NP, bool split, bool forced)
+{
+    RowPlan r;
+    int S = 1;
+    if (split) {
+        const int cap = std::max(1, forced ? NP / 16 : NP / 256);
+        S = std::min((int)cdiv(8192, M), cap);      // 8192 wavefronts: 32 per compute unit
+    }
+    r.pps = (int)cdiv(NP, S);
+    r.S = (int)cdiv(NP, r.pps);
+    r.W = std::min(64, std::max(4, pow2ceil(r.pps)));
+    return r;
+}
+static inline bool row_split_auto(int M, int NP) { return M < 1024 && row_plan(M, NP, true, false).S >= 2; }
+
+static inline ColPlan col_plan(int M, int NP)
+{
+    ColPlan c;
+    c.CW = std::min(256, pow2ceil(NP));
+    const int RG = 256 / c.CW;
+    c.CT = (int)cdiv(NP, c.CW);
+    const int rs_max = (int)cdiv(M, (int64_t)RG * 16);      // at least two batches of eight rows per thread
+    const int RS = std::max(1, std::min((int)cdiv(1024, c.CT), rs_max));
+    c.rps = (int)(cdiv(cdiv(M, RS), RG) * RG);
+    c.RS = (int)cdiv(M, c.rps);
+    return c;
+}
+
+// dense_multi.hip
+void dnm_release(lcg_hip_dense *K);     // the k-wide work memory of a handle that goes (the caller has drained the device)
+// a real dense handle, or nullptr with the entry's name and the reason in lcg_hip_last_error()
+lcg_hip_dense *dnm_handle(const char *entry, const void *h);
+// the handle's M x k block and k-wide slot table: the first call at a k larger than any before allocates and waits, later ones return
+int dnm_reserve(lcg_hip_dense *K, int k);
+// Y = (normal ? K^T.K : K).X for the k columns and, with U, column j's Y_j . U_j as *slots <= MM_MG partial sums at dots[j * MM_MG ...]
+// (multi.hpp's table format, added in index order by msum).  *launches grows by the kernels enqueued.  Checked handle, reserved k.
+int dnm_op(lcg_hip_dense *K, int k, int normal, const double *X, double *Y, hipStream_t s, const int *done, const double *U, double *dots,
+           int *slots, int *launches);
+
+} // namespace lcgh

@@ -1,5 +1,7 @@
 // solvers_multi.hip -- batched CG and PCG over k = 2, 4, 8 right-hand sides: lcg_hip_lcg_multi, lcg_hip_lpcg_multi (the built-in
-// Jacobi), lcg_hip_lpcg_multi_m (Jacobi, or the handle's IC(0) / ILU(0) factor applied k wide: csr_tri_multi.hip).
+// Jacobi), lcg_hip_lpcg_multi_m (Jacobi, or the handle's IC(0) / ILU(0) factor applied k wide: csr_tri_multi.hip), and the same loop
+// on a dense handle's K^T.K or K: lcg_hip_dense_lcg_multi, lcg_hip_dense_lpcg_multi (dense_multi.hip).  The loop reaches the matrix
+// through a small operator argument (CsrOp, DenseOp below).
 //
 // Each column runs the reference's own recurrence as if it were alone (lcg.cpp:143-274, 293-434): its own alpha, beta, rho, its own
 // residual under the same stop rule, its own "already optimised" test, NaN scan, count and return code.  What the columns share is
@@ -27,6 +29,7 @@
 // order): the same bits whatever the other columns hold, from call to call.
 #include "multi_loop.hpp"
 #include "csr_tri.hpp"
+#include "dense.hpp"
 
 namespace lcgh {
 namespace {
@@ -217,29 +220,71 @@ struct MOpPcgDir {      // d = z + b d                                     lcg.c
 template <int K, bool PCG>
 struct MultiSolve {
     Ctx &c;
-    const CsrPart &P;
     long n2;
     int grid;
     MState *cur, *next;
     double *tab_dot, *tab_sum;      // the k-wide tables: d.Ad's partial sums (the product's), the update pass's
     int g_dot = 0;
 
-    template <class Fin, class Op, bool ALL = false> int pass(Fin fin, Op op, const double *pin, int gin, int g = 0)
+    // TREE: multi_loop.hpp -- 1: this pass leaves sums, 2: it adds up a pass's sums (0: the plain order, what the CSR entries compute)
+    template <class Fin, class Op, bool ALL = false, int TREE = 0> int pass(Fin fin, Op op, const double *pin, int gin, int g = 0)
     {
         c.cnt_vec++;
-        hipLaunchKernelGGL((k_mvecf<MState, K, Fin, Op, ALL>), dim3(g ? g : grid), dim3(VB), 0, c.stream, fin, op, n2, pin, gin, tab_sum, cur, next);
+        hipLaunchKernelGGL((k_mvecf<MState, K, Fin, Op, ALL, TREE>), dim3(g ? g : grid), dim3(VB), 0, c.stream, fin, op, n2, pin, gin, tab_sum, cur, next);
         HIPCHK(hipGetLastError());
         std::swap(cur, next);
         return 0;
     }
 };
 
-template <int K, bool PCG>
-static int run_multi(lcg_hip_csr *A, const TriFactor *F, double *M, const double *B, const lcg_para &p, int *ret, int *iterations,
-                     double *residual, int mem)
-{   // F: the factor that is M (PCG only; its k-wide work vectors reserved by the caller), nullptr: the built-in Jacobi
+// ---- the matrix, as the loop sees it ---------------------------------------------------------------------------------------------------
+// rows(), invdiag() (the Jacobi reciprocals), big_doubles(k) (what the product's carried sum needs on its way to the table), grid(n, K)
+// (workgroups of a vector pass) and apply(): Y = A.X for the K columns and, with U, column j's (A.X)_j . U_j as *slots partial sums in
+// `dots` (multi.hpp's table format).  TREE: the passes add their sums as multi_loop.hpp's binary tree, so that a column's bits do not
+// depend on K either.  factor(): a triangular factor as M (null: the built-in Jacobi).
+struct CsrOp {
+    static constexpr bool TREE = false;      // (the sums these entries have always computed)
+    lcg_hip_csr *A;
+    const TriFactor *F;
+    int rows() const { return A->n_rows; }
+    const double *invdiag() const { return A->invdiag; }
+    const TriFactor *factor() const { return F; }
+    size_t big_doubles(int k) const { return spmm_big_doubles(A->main, k); }
+    int grid(long n, int k) const { return grid_for(n * (k / 2)); }
+    int apply(Ctx &c, int k, const double *X, double *Y, const int *done, const double *U = nullptr, double *big = nullptr,
+              double *dots = nullptr, int *slots = nullptr) const
+    {
+        c.cnt_ax++;
+        return spmm_launch(A->main, k, X, Y, c.stream, done, U, big, dots, slots);
+    }
+};
+// K^T.K or K of a dense handle (dense_multi.hip): the product is two to five launches, all counted as products
+struct DenseOp {
+    static constexpr bool TREE = true;
+    lcg_hip_dense *D;
+    int normal;
+    int rows() const { return D->N; }
+    const double *invdiag() const { return D->invdiag; }
+    const TriFactor *factor() const { return nullptr; }
+    size_t big_doubles(int) const { return 0; }
+    int grid(long n, int k) const { return (int)(tree_leaves(n) * (k / 2) / VB); }      // a thread's rows do not depend on k
+    int apply(Ctx &c, int k, const double *X, double *Y, const int *done, const double *U = nullptr, double * = nullptr,
+              double *dots = nullptr, int *slots = nullptr) const
+    {
+        int launches = 0;
+        const int rc = dnm_op(D, k, normal, X, Y, c.stream, done, U, dots, slots, &launches);
+        c.cnt_ax += launches;
+        return rc;
+    }
+};
+
+template <int K, bool PCG, class OpA>
+static int run_multi(const OpA &A, double *M, const double *B, const lcg_para &p, int *ret, int *iterations, double *residual, int mem)
+{   // A.factor(): the factor that is M (PCG only; its k-wide work vectors reserved by the caller), nullptr: the built-in Jacobi
     Ctx &c = ctx();
-    const int n = A->n_rows;
+    const int n = A.rows();
+    const TriFactor *F = A.factor();
+    constexpr int T1 = OpA::TREE ? 1 : 0, T2 = OpA::TREE ? 2 : 0;
     const size_t nb = sizeof(double) * (size_t)n * K;
     HostBridge hb;
     Workspace ws;
@@ -250,35 +295,33 @@ static int run_multi(lcg_hip_csr *A, const TriFactor *F, double *M, const double
     if (PCG) TRY(ws.get(z, nullptr, nb));
     TRY(ws.get(d, nullptr, nb));
     TRY(ws.get(Ad, nullptr, nb));
-    const size_t nbig = spmm_big_doubles(A->main, K);
+    const size_t nbig = A.big_doubles(K);
     if (nbig) TRY(ws.get(big, nullptr, sizeof(double) * nbig));
     TRY(ws.get(stmem, nullptr, 2 * 512));
     static_assert(sizeof(MState) <= 512, "two states share one small pool vector");
 
-    MultiSolve<K, PCG> k{c, A->main, (long)n * (K / 2), 0, reinterpret_cast<MState *>(stmem),
+    MultiSolve<K, PCG> k{c, (long)n * (K / 2), 0, reinterpret_cast<MState *>(stmem),
                          reinterpret_cast<MState *>(reinterpret_cast<char *>(stmem) + 512), c.partials_pair[0], c.partials_pair[1]};
-    k.grid = grid_for(k.n2);
+    k.grid = A.grid(n, K);
     const long work = (long)n * K;
     c.hstat->it = 0; c.hstat->done = 0; c.hstat->status = 0; c.hstat->t = 0; c.hstat->residual = 0.0;
     hipLaunchKernelGGL(k_minit, dim3(1), dim3(64), 0, c.stream, k.cur, p.epsilon, (double)n, p.abs_diff, work >= (1 << 20) ? 0 : 3, c.hstat_dev);
     HIPCHK(hipGetLastError());
 
     // setup (lcg.cpp:168-203, 314-359): A.m for the guess, the first residual and direction, the verdict "already optimised"
-    c.cnt_ax++;
-    TRY(spmm_launch(k.P, K, M, Ad, c.stream, nullptr));
+    TRY(A.apply(c, K, M, Ad, nullptr));
     const int m_launches = PCG && F ? tri_apply_launches(F, 2) : 0;        // counted as vector passes (lcg_hip_last_launches)
-    if (PCG && F) {
+    if (PCG && F) {         // (a factor comes with a CsrOp only: the plain order of the sums)
         TRY((k.template pass<MFinNone, MOpFRes, true>(MFinNone{}, MOpFRes{Ad, B, g}, nullptr, 0)));
         c.cnt_vec += m_launches;
         TRY(tri_apply_multi(F, K, 2, g, z, c.stream, nullptr));
         TRY((k.template pass<MFinNone, MOpFInit, true>(MFinNone{}, MOpFInit{M, g, z, d}, nullptr, 0)));
-    } else if (PCG) TRY((k.template pass<MFinNone, MOpPcgInit, true>(MFinNone{}, MOpPcgInit{Ad, B, M, A->invdiag, g, z, d}, nullptr, 0)));
-    else TRY((k.template pass<MFinNone, MOpCgInit, true>(MFinNone{}, MOpCgInit{Ad, B, M, g, d}, nullptr, 0)));
-    TRY((k.template pass<MFinInit<K, PCG>, MOpNone, true>(MFinInit<K, PCG>{}, MOpNone{}, k.tab_sum, k.grid, 1)));
+    } else if (PCG) TRY((k.template pass<MFinNone, MOpPcgInit, true, T1>(MFinNone{}, MOpPcgInit{Ad, B, M, A.invdiag(), g, z, d}, nullptr, 0)));
+    else TRY((k.template pass<MFinNone, MOpCgInit, true, T1>(MFinNone{}, MOpCgInit{Ad, B, M, g, d}, nullptr, 0)));
+    TRY((k.template pass<MFinInit<K, PCG>, MOpNone, true, T2>(MFinInit<K, PCG>{}, MOpNone{}, k.tab_sum, k.grid, 1)));
 
     auto body = [&]() -> int {
-        c.cnt_ax++;
-        TRY(spmm_launch(k.P, K, d, Ad, c.stream, &k.cur->all_done, d, big, k.tab_dot, &k.g_dot));          // :232-234, :387-389
+        TRY(A.apply(c, K, d, Ad, &k.cur->all_done, d, big, k.tab_dot, &k.g_dot));                          // :232-234, :387-389
         if (PCG && F) {
             TRY(k.pass(MFinAlpha<K>{}, MOpFUpdate{M, g, d, Ad, m2d()}, k.tab_dot, k.g_dot));                   // :390-399
             c.cnt_vec += m_launches;
@@ -286,11 +329,11 @@ static int run_multi(lcg_hip_csr *A, const TriFactor *F, double *M, const double
             TRY(k.pass(MFinNone{}, MOpFSums{M, g, z}, nullptr, 0));                                         // :401-414
             TRY(k.pass(MFinClose<K, true>{}, MOpPcgDir{d, z, m2d()}, k.tab_sum, k.grid));                      // :415-422
         } else if (PCG) {
-            TRY(k.pass(MFinAlpha<K>{}, MOpPcgUpdate{M, g, z, d, Ad, A->invdiag, m2d()}, k.tab_dot, k.g_dot));  // :390-414
-            TRY(k.pass(MFinClose<K, true>{}, MOpPcgDir{d, z, m2d()}, k.tab_sum, k.grid));                      // :415-422
+            TRY((k.template pass<MFinAlpha<K>, MOpPcgUpdate, false, T1>(MFinAlpha<K>{}, MOpPcgUpdate{M, g, z, d, Ad, A.invdiag(), m2d()}, k.tab_dot, k.g_dot)));  // :390-414
+            TRY((k.template pass<MFinClose<K, true>, MOpPcgDir, false, T2>(MFinClose<K, true>{}, MOpPcgDir{d, z, m2d()}, k.tab_sum, k.grid)));                     // :415-422
         } else {
-            TRY(k.pass(MFinAlpha<K>{}, MOpCgUpdate{M, g, d, Ad, m2d()}, k.tab_dot, k.g_dot));                  // :235-255
-            TRY(k.pass(MFinClose<K, false>{}, MOpCgDir{d, g, m2d()}, k.tab_sum, k.grid));                      // :256-263
+            TRY((k.template pass<MFinAlpha<K>, MOpCgUpdate, false, T1>(MFinAlpha<K>{}, MOpCgUpdate{M, g, d, Ad, m2d()}, k.tab_dot, k.g_dot)));                     // :235-255
+            TRY((k.template pass<MFinClose<K, false>, MOpCgDir, false, T2>(MFinClose<K, false>{}, MOpCgDir{d, g, m2d()}, k.tab_sum, k.grid)));                     // :256-263
         }
         return 0;
     };
@@ -346,9 +389,34 @@ static int solve_multi(const char *entry, lcg_hip_csr *A, int k, int precond, do
     }
     TRY(ensure_init());
     if (F) TRY(tri_multi_reserve(F, k, 2));
-    if (k == 2) return run_multi<2, PCG>(A, F, M, B, p, ret, iterations, residual, mem);
-    if (k == 4) return run_multi<4, PCG>(A, F, M, B, p, ret, iterations, residual, mem);
-    return run_multi<8, PCG>(A, F, M, B, p, ret, iterations, residual, mem);
+    const CsrOp op{A, F};
+    if (k == 2) return run_multi<2, PCG>(op, M, B, p, ret, iterations, residual, mem);
+    if (k == 4) return run_multi<4, PCG>(op, M, B, p, ret, iterations, residual, mem);
+    return run_multi<8, PCG>(op, M, B, p, ret, iterations, residual, mem);
+}
+
+// the dense entries: A = K^T.K (normal = 1) or K (normal = 0, square), PCG with the reciprocals of lcg_hip_dense_build_jacobi
+template <bool PCG>
+static int solve_dense_multi(const char *entry, const void *Kh, int k, int normal, double *M, const double *B, const lcg_para *param, int *ret,
+                             int *iterations, double *residual, int mem)
+{
+    TRY(multi_args(entry, k, M, B));
+    lcg_hip_dense *D = dnm_handle(entry, Kh);
+    if (!D) return LCG_HIP_E_ARG;
+    if (normal != 0 && normal != 1) { ctx().err = std::string(entry) + ": normal is neither 1 (K^T.K) nor 0 (K)"; return LCG_HIP_E_ARG; }
+    if (!normal && D->M != D->N) { ctx().err = std::string(entry) + ": the matrix is not square: normal = 0 needs a square one"; return LCG_HIP_E_ARG; }
+    if (mem != LCG_HIP_MEM_HOST && mem != LCG_HIP_MEM_DEVICE) { ctx().err = std::string(entry) + ": mem is neither LCG_HIP_MEM_HOST nor LCG_HIP_MEM_DEVICE"; return LCG_HIP_E_ARG; }
+    const lcg_para p = param ? *param : lcg_hip_default_parameters();
+    if (p.max_iterations < 0) return LCG_INVILAD_MAX_ITERATIONS;            // lcg.cpp:150-155
+    if (p.epsilon <= 0.0 || p.epsilon >= 1.0) return LCG_INVILAD_EPSILON;
+    // no diagonal, or the other operator's (lcg_hip_dense_build_jacobi records which it built)
+    if (PCG && (D->invdiag == nullptr || D->invdiag_normal != normal)) return LCG_NULL_PRECONDITION_MATRIX;
+    TRY(ensure_init());
+    TRY(dnm_reserve(D, k));
+    const DenseOp op{D, normal};
+    if (k == 2) return run_multi<2, PCG>(op, M, B, p, ret, iterations, residual, mem);
+    if (k == 4) return run_multi<4, PCG>(op, M, B, p, ret, iterations, residual, mem);
+    return run_multi<8, PCG>(op, M, B, p, ret, iterations, residual, mem);
 }
 
 } // namespace
@@ -377,6 +445,18 @@ int lcg_hip_lpcg_multi_m(lcg_hip_csr_t A, int k, int precond, double *M, const d
 {
     NOT_DENSE(A, LCG_HIP_E_ARG);
     return solve_multi<true>("lcg_hip_lpcg_multi_m", A, k, precond, M, B, param, ret, iterations, residual, mem);
+}
+
+int lcg_hip_dense_lcg_multi(lcg_hip_dense_t K, int k, int normal, double *M, const double *B, const lcg_para *param, int *ret,
+                            int *iterations, double *residual, int mem)
+{
+    return solve_dense_multi<false>("lcg_hip_dense_lcg_multi", K, k, normal, M, B, param, ret, iterations, residual, mem);
+}
+
+int lcg_hip_dense_lpcg_multi(lcg_hip_dense_t K, int k, int normal, double *M, const double *B, const lcg_para *param, int *ret,
+                             int *iterations, double *residual, int mem)
+{
+    return solve_dense_multi<true>("lcg_hip_dense_lpcg_multi", K, k, normal, M, B, param, ret, iterations, residual, mem);
 }
 
 } // extern "C"
