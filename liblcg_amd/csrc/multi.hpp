@@ -84,11 +84,12 @@ __device__ __forceinline__ void msum_tree(const double *pin, int g, double *sums
 }
 
 // the leaves of a TREE pass: rows i, i + S, i + 2 S, ... share leaf i mod S.  S depends on n alone, so a thread's leaf does not
-// depend on k; the pass runs S * (k / 2) / VB workgroups (k = 8: at most MM_MG)
-inline long tree_leaves(long n)
+// depend on k; with g lanes to a row the pass runs S * g / VB workgroups, at most MM_MG with the widest row's gmax lanes (k = 8: 4 for
+// real blocks, 8 for complex ones)
+inline long tree_leaves(long n, int gmax)
 {
     long s = 256;
-    while (s < n && s < 64 * MM_MG) s <<= 1;
+    while (s < n && s < MM_MG * VB / gmax) s <<= 1;
     return s;
 }
 

@@ -22,13 +22,4 @@ int cspmm_launch(const CsrPart &P, int k, const double *X, double *Y, hipStream_
                  double *big = nullptr, double *dots = nullptr, int *slots = nullptr);
 size_t cspmm_big_doubles(const CsrPart &P, int k);
 
-// the leaves of a complex TREE pass (k_cvecf): rows i, i + S, i + 2 S, ... share leaf i mod S.  S depends on n alone, so a thread's
-// leaf does not depend on k; the pass runs S * k / VB workgroups (k = 8: at most MM_MG)
-inline long ctree_leaves(long n)
-{
-    long s = 256;
-    while (s < n && s < 32 * MM_MG) s <<= 1;
-    return s;
-}
-
 } // namespace lcgh

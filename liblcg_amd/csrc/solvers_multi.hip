@@ -34,26 +34,9 @@
 namespace lcgh {
 namespace {
 
-struct MState {
+struct MState : MultiHead {
     double ak[MM_MAXK], bk[MM_MAXK], rho[MM_MAXK], m2[MM_MAXK], g2[MM_MAXK], residual[MM_MAXK];
-    double eps, n_global;
-    int t[MM_MAXK];         // completed iterations (the reference's t), per column
-    int stop[MM_MAXK];      // ST_RUNNING, or why the column stopped (ST_CONVERGED, ST_NAN, ST_ALREADY)
-    int abs_diff;
-    int it;                 // iteration bodies started
-    int all_done;           // every column has stopped: every later kernel is a no-op
-    int pub_mask;           // HostStatus is refreshed when (it & pub_mask) == 0, and when all columns have stopped
-    HostStatus *host;
 };
-static_assert(sizeof(MState) % 8 == 0, "MState is copied in 8-byte words");
-
-__global__ void k_minit(MState *st, double eps, double n_global, int abs_diff, int pub_mask, HostStatus *host)
-{
-    double *w = reinterpret_cast<double *>(st);
-    for (int i = threadIdx.x; i < (int)(sizeof(MState) / 8); i += blockDim.x) w[i] = 0.0;
-    __syncthreads();
-    if (threadIdx.x == 0) { st->eps = eps; st->n_global = n_global; st->abs_diff = abs_diff; st->pub_mask = pub_mask; st->host = host; }
-}
 
 // ---- scalar steps: sums[s * K + j] = running sum s of column j ------------------------------------------------------------------
 // setup: |m|^2 (clamped), the residual's numerator, rho; "already optimised" per column (lcg.cpp:178-203, 341-359: in abs_diff mode
@@ -66,13 +49,7 @@ template <int K, bool PCG> struct MFinInit {
         for (int j = 0; j < K; j++) {
             const double m2 = clamp1(sum[j]), g2 = sum[K + j];
             st->m2[j] = m2; st->g2[j] = g2; st->rho[j] = PCG ? sum[2 * K + j] : g2;
-            double r;
-            bool already = false;
-            if (st->abs_diff && sqrt(g2) / st->n_global <= st->eps) { r = sqrt(g2) / st->n_global; already = true; }
-            else if (g2 / m2 <= st->eps) { r = g2 / m2; already = true; }
-            else r = st->abs_diff ? sqrt(g2) / st->n_global : g2 / m2;
-            st->residual[j] = r;
-            st->stop[j] = already ? ST_ALREADY : ST_RUNNING;
+            m_already(st, j, g2, m2);
         }
         all_stopped<K>(st);
         mpublish(st);
@@ -106,7 +83,7 @@ template <int K, bool PCG> struct MFinClose {
                 st->bk[j] = rho_new / st->rho[j];
                 st->rho[j] = rho_new;
                 st->g2[j] = g2;
-                const double r = st->abs_diff ? sqrt(g2) / st->n_global : g2 / st->m2[j];      // the next loop head's test (lcg.cpp:208-222)
+                const double r = m_residual(st, g2, st->m2[j]);      // the next loop head's test (lcg.cpp:208-222)
                 st->residual[j] = r;
                 if (r <= st->eps) st->stop[j] = ST_CONVERGED;
             }
@@ -216,32 +193,11 @@ struct MOpPcgDir {      // d = z + b d                                     lcg.c
     __device__ void apply(long e, long, bool r0, bool r1, m2d *) { st2(d, e, ld2(z, e) + bk * ld2(d, e), r0, r1); }
 };
 
-// ---- host side ------------------------------------------------------------------------------------------------------------------------
-template <int K, bool PCG>
-struct MultiSolve {
-    Ctx &c;
-    long n2;
-    int grid;
-    MState *cur, *next;
-    double *tab_dot, *tab_sum;      // the k-wide tables: d.Ad's partial sums (the product's), the update pass's
-    int g_dot = 0;
-
-    // TREE: multi_loop.hpp -- 1: this pass leaves sums, 2: it adds up a pass's sums (0: the plain order, what the CSR entries compute)
-    template <class Fin, class Op, bool ALL = false, int TREE = 0> int pass(Fin fin, Op op, const double *pin, int gin, int g = 0)
-    {
-        c.cnt_vec++;
-        hipLaunchKernelGGL((k_mvecf<MState, K, Fin, Op, ALL, TREE>), dim3(g ? g : grid), dim3(VB), 0, c.stream, fin, op, n2, pin, gin, tab_sum, cur, next);
-        HIPCHK(hipGetLastError());
-        std::swap(cur, next);
-        return 0;
-    }
-};
-
 // ---- the matrix, as the loop sees it ---------------------------------------------------------------------------------------------------
-// rows(), invdiag() (the Jacobi reciprocals), big_doubles(k) (what the product's carried sum needs on its way to the table), grid(n, K)
-// (workgroups of a vector pass) and apply(): Y = A.X for the K columns and, with U, column j's (A.X)_j . U_j as *slots partial sums in
-// `dots` (multi.hpp's table format).  TREE: the passes add their sums as multi_loop.hpp's binary tree, so that a column's bits do not
-// depend on K either.  factor(): a triangular factor as M (null: the built-in Jacobi).
+// rows(), invdiag() (the Jacobi reciprocals), big_doubles(k) (what the product's carried sum needs on its way to the table) and
+// apply(): Y = A.X for the K columns and, with U, column j's (A.X)_j . U_j as *slots partial sums in `dots` (multi.hpp's table
+// format).  TREE: the passes add their sums as multi_loop.hpp's binary tree, so that a column's bits do not depend on K either.
+// factor(): a triangular factor as M (null: the built-in Jacobi).
 struct CsrOp {
     static constexpr bool TREE = false;      // (the sums these entries have always computed)
     lcg_hip_csr *A;
@@ -250,7 +206,6 @@ struct CsrOp {
     const double *invdiag() const { return A->invdiag; }
     const TriFactor *factor() const { return F; }
     size_t big_doubles(int k) const { return spmm_big_doubles(A->main, k); }
-    int grid(long n, int k) const { return grid_for(n * (k / 2)); }
     int apply(Ctx &c, int k, const double *X, double *Y, const int *done, const double *U = nullptr, double *big = nullptr,
               double *dots = nullptr, int *slots = nullptr) const
     {
@@ -267,7 +222,6 @@ struct DenseOp {
     const double *invdiag() const { return D->invdiag; }
     const TriFactor *factor() const { return nullptr; }
     size_t big_doubles(int) const { return 0; }
-    int grid(long n, int k) const { return (int)(tree_leaves(n) * (k / 2) / VB); }      // a thread's rows do not depend on k
     int apply(Ctx &c, int k, const double *X, double *Y, const int *done, const double *U = nullptr, double * = nullptr,
               double *dots = nullptr, int *slots = nullptr) const
     {
@@ -281,87 +235,51 @@ struct DenseOp {
 template <int K, bool PCG, class OpA>
 static int run_multi(const OpA &A, double *M, const double *B, const lcg_para &p, int *ret, int *iterations, double *residual, int mem)
 {   // A.factor(): the factor that is M (PCG only; its k-wide work vectors reserved by the caller), nullptr: the built-in Jacobi
-    Ctx &c = ctx();
-    const int n = A.rows();
     const TriFactor *F = A.factor();
-    constexpr int T1 = OpA::TREE ? 1 : 0, T2 = OpA::TREE ? 2 : 0;
-    const size_t nb = sizeof(double) * (size_t)n * K;
-    HostBridge hb;
-    Workspace ws;
-    SolveGuard guard(c);
-    TRY(hb.open(mem, M, B, nb, c.stream));
-    double *g = nullptr, *z = nullptr, *d = nullptr, *Ad = nullptr, *big = nullptr, *stmem = nullptr;
-    TRY(ws.get(g, nullptr, nb));        // (PCG: r)
-    if (PCG) TRY(ws.get(z, nullptr, nb));
-    TRY(ws.get(d, nullptr, nb));
-    TRY(ws.get(Ad, nullptr, nb));
+    constexpr int T1 = OpA::TREE ? 1 : 0, T2 = OpA::TREE ? 2 : 0;      // (a factor comes with a CsrOp only: the plain order of the sums)
+    MultiFrame<MState, K, K / 2> f(A.rows());
+    Ctx &c = f.c;
+    TRY(f.open(mem, M, B));
+    double *g = nullptr, *z = nullptr, *d = nullptr, *Ad = nullptr, *big = nullptr;
+    TRY(f.vec(g));          // (PCG: r)
+    if (PCG) TRY(f.vec(z));
+    TRY(f.vec(d));
+    TRY(f.vec(Ad));
     const size_t nbig = A.big_doubles(K);
-    if (nbig) TRY(ws.get(big, nullptr, sizeof(double) * nbig));
-    TRY(ws.get(stmem, nullptr, 2 * 512));
-    static_assert(sizeof(MState) <= 512, "two states share one small pool vector");
-
-    MultiSolve<K, PCG> k{c, (long)n * (K / 2), 0, reinterpret_cast<MState *>(stmem),
-                         reinterpret_cast<MState *>(reinterpret_cast<char *>(stmem) + 512), c.partials_pair[0], c.partials_pair[1]};
-    k.grid = A.grid(n, K);
-    const long work = (long)n * K;
-    c.hstat->it = 0; c.hstat->done = 0; c.hstat->status = 0; c.hstat->t = 0; c.hstat->residual = 0.0;
-    hipLaunchKernelGGL(k_minit, dim3(1), dim3(64), 0, c.stream, k.cur, p.epsilon, (double)n, p.abs_diff, work >= (1 << 20) ? 0 : 3, c.hstat_dev);
-    HIPCHK(hipGetLastError());
+    if (nbig) TRY(f.ws.get(big, nullptr, sizeof(double) * nbig));
+    TRY(f.start(OpA::TREE ? f.tree_grid() : grid_for(f.n2), p.epsilon, p.abs_diff));
 
     // setup (lcg.cpp:168-203, 314-359): A.m for the guess, the first residual and direction, the verdict "already optimised"
     TRY(A.apply(c, K, M, Ad, nullptr));
     const int m_launches = PCG && F ? tri_apply_launches(F, 2) : 0;        // counted as vector passes (lcg_hip_last_launches)
-    if (PCG && F) {         // (a factor comes with a CsrOp only: the plain order of the sums)
-        TRY((k.template pass<MFinNone, MOpFRes, true>(MFinNone{}, MOpFRes{Ad, B, g}, nullptr, 0)));
+    if (PCG && F) {
+        TRY((f.template pass<0, true>(MFinNone{}, MOpFRes{Ad, B, g}, nullptr, 0)));
         c.cnt_vec += m_launches;
         TRY(tri_apply_multi(F, K, 2, g, z, c.stream, nullptr));
-        TRY((k.template pass<MFinNone, MOpFInit, true>(MFinNone{}, MOpFInit{M, g, z, d}, nullptr, 0)));
-    } else if (PCG) TRY((k.template pass<MFinNone, MOpPcgInit, true, T1>(MFinNone{}, MOpPcgInit{Ad, B, M, A.invdiag(), g, z, d}, nullptr, 0)));
-    else TRY((k.template pass<MFinNone, MOpCgInit, true, T1>(MFinNone{}, MOpCgInit{Ad, B, M, g, d}, nullptr, 0)));
-    TRY((k.template pass<MFinInit<K, PCG>, MOpNone, true, T2>(MFinInit<K, PCG>{}, MOpNone{}, k.tab_sum, k.grid, 1)));
+        TRY((f.template pass<0, true>(MFinNone{}, MOpFInit{M, g, z, d}, nullptr, 0)));
+    } else if (PCG) TRY((f.template pass<T1, true>(MFinNone{}, MOpPcgInit{Ad, B, M, A.invdiag(), g, z, d}, nullptr, 0)));
+    else TRY((f.template pass<T1, true>(MFinNone{}, MOpCgInit{Ad, B, M, g, d}, nullptr, 0)));
+    TRY((f.template pass<T2, true>(MFinInit<K, PCG>{}, MOpNone{}, f.tab_sum, f.grid, 1)));
 
-    auto body = [&]() -> int {
-        TRY(A.apply(c, K, d, Ad, &k.cur->all_done, d, big, k.tab_dot, &k.g_dot));                          // :232-234, :387-389
+    int g_dot = 0;
+    f.run(p.max_iterations, [&]() -> int {
+        TRY(A.apply(c, K, d, Ad, &f.cur->all_done, d, big, f.tab_dot, &g_dot));                                 // :232-234, :387-389
         if (PCG && F) {
-            TRY(k.pass(MFinAlpha<K>{}, MOpFUpdate{M, g, d, Ad, m2d()}, k.tab_dot, k.g_dot));                   // :390-399
+            TRY(f.template pass<0>(MFinAlpha<K>{}, MOpFUpdate{M, g, d, Ad, m2d()}, f.tab_dot, g_dot));          // :390-399
             c.cnt_vec += m_launches;
-            TRY(tri_apply_multi(F, K, 2, g, z, c.stream, &k.cur->all_done));                                   // :400
-            TRY(k.pass(MFinNone{}, MOpFSums{M, g, z}, nullptr, 0));                                         // :401-414
-            TRY(k.pass(MFinClose<K, true>{}, MOpPcgDir{d, z, m2d()}, k.tab_sum, k.grid));                      // :415-422
+            TRY(tri_apply_multi(F, K, 2, g, z, c.stream, &f.cur->all_done));                                    // :400
+            TRY(f.template pass<0>(MFinNone{}, MOpFSums{M, g, z}, nullptr, 0));                                 // :401-414
+            TRY(f.template pass<0>(MFinClose<K, true>{}, MOpPcgDir{d, z, m2d()}, f.tab_sum, f.grid));           // :415-422
         } else if (PCG) {
-            TRY((k.template pass<MFinAlpha<K>, MOpPcgUpdate, false, T1>(MFinAlpha<K>{}, MOpPcgUpdate{M, g, z, d, Ad, A.invdiag(), m2d()}, k.tab_dot, k.g_dot)));  // :390-414
-            TRY((k.template pass<MFinClose<K, true>, MOpPcgDir, false, T2>(MFinClose<K, true>{}, MOpPcgDir{d, z, m2d()}, k.tab_sum, k.grid)));                     // :415-422
+            TRY(f.template pass<T1>(MFinAlpha<K>{}, MOpPcgUpdate{M, g, z, d, Ad, A.invdiag(), m2d()}, f.tab_dot, g_dot));  // :390-414
+            TRY(f.template pass<T2>(MFinClose<K, true>{}, MOpPcgDir{d, z, m2d()}, f.tab_sum, f.grid));          // :415-422
         } else {
-            TRY((k.template pass<MFinAlpha<K>, MOpCgUpdate, false, T1>(MFinAlpha<K>{}, MOpCgUpdate{M, g, d, Ad, m2d()}, k.tab_dot, k.g_dot)));                     // :235-255
-            TRY((k.template pass<MFinClose<K, false>, MOpCgDir, false, T2>(MFinClose<K, false>{}, MOpCgDir{d, g, m2d()}, k.tab_sum, k.grid)));                     // :256-263
+            TRY(f.template pass<T1>(MFinAlpha<K>{}, MOpCgUpdate{M, g, d, Ad, m2d()}, f.tab_dot, g_dot));        // :235-255
+            TRY(f.template pass<T2>(MFinClose<K, false>{}, MOpCgDir{d, g, m2d()}, f.tab_sum, f.grid));          // :256-263
         }
         return 0;
-    };
-
-    MState h;
-    auto read_state = [&]() -> int {
-        HIPCHK(hipMemcpyAsync(&h, k.cur, sizeof h, hipMemcpyDeviceToHost, c.stream));
-        HIPCHK(hipStreamSynchronize(c.stream));
-        return 0;
-    };
-    const int rc = enqueue_ahead(c, p.max_iterations, work >= (1 << 20) ? 6 : 24, body, read_state, h);
-    if (!rc) {
-        int longest = 0;
-        for (int j = 0; j < K; j++) {
-            if (ret) ret[j] = lcg_code(h.stop[j]);
-            if (iterations) iterations[j] = h.t[j];
-            if (residual) residual[j] = h.residual[j];
-            if (h.t[j] > h.t[longest]) longest = j;
-        }
-        c.last_iters = h.t[longest];
-        c.last_residual = h.residual[longest];
-        c.last_ax_calls = 0; c.last_ax_mean_us = 0.0; c.prof_pending = 0;
-    } else {
-        (void)hipStreamSynchronize(c.stream);       // nothing of this solve may still run on vectors that go back to the pool
-        (void)hipGetLastError();
-    }
-    const int rc2 = hb.close(c.stream);
-    return rc ? rc : rc2;
+    });
+    return f.finish(lcg_code, ret, iterations, residual);
 }
 
 // precond: LCG_HIP_M_JACOBI (CG: not looked at), LCG_HIP_M_IC0, LCG_HIP_M_ILU0
@@ -369,30 +287,18 @@ template <bool PCG>
 static int solve_multi(const char *entry, lcg_hip_csr *A, int k, int precond, double *M, const double *B, const lcg_para *param, int *ret, int *iterations,
                        double *residual, int mem)
 {
+    lcg_para p;
+    MultiPrecond m;
     TRY(multi_args(entry, k, M, B));
     TRY(multi_handle(entry, A));
-    if (A->n_rows != A->n_cols) { ctx().err = std::string(entry) + ": the matrix is not square"; return LCG_HIP_E_ARG; }
-    if (mem != LCG_HIP_MEM_HOST && mem != LCG_HIP_MEM_DEVICE) { ctx().err = std::string(entry) + ": mem is neither LCG_HIP_MEM_HOST nor LCG_HIP_MEM_DEVICE"; return LCG_HIP_E_ARG; }
-    if (precond != LCG_HIP_M_JACOBI && precond != LCG_HIP_M_IC0 && precond != LCG_HIP_M_ILU0) {
-        ctx().err = std::string(entry) + ": precond is none of LCG_HIP_M_JACOBI, LCG_HIP_M_IC0, LCG_HIP_M_ILU0";
-        return LCG_HIP_E_ARG;
-    }
-    const lcg_para p = param ? *param : lcg_hip_default_parameters();
-    if (p.max_iterations < 0) return LCG_INVILAD_MAX_ITERATIONS;            // lcg.cpp:150-155
-    if (p.epsilon <= 0.0 || p.epsilon >= 1.0) return LCG_INVILAD_EPSILON;
-    TriFactor *F = nullptr;
-    if (precond == LCG_HIP_M_JACOBI) {
-        if (PCG && A->invdiag == nullptr) return LCG_NULL_PRECONDITION_MATRIX;      // lcg_hip_csr_build_jacobi has not run
-    } else {
-        F = precond == LCG_HIP_M_IC0 ? A->ic0 : A->ilu0;
-        if (!F || !F->ok) return LCG_NULL_PRECONDITION_MATRIX;              // lcg_hip_csr_build_ic0 / _ilu0 has not run (or its pivot failed)
-    }
+    TRY(multi_shape(entry, A->n_rows == A->n_cols, mem));
+    TRY(multi_precond(entry, A, precond, false, PCG, m));
+    TRY(multi_para<false>(param, p, A->n_rows));
+    if (!m.built) return LCG_NULL_PRECONDITION_MATRIX;
     TRY(ensure_init());
-    if (F) TRY(tri_multi_reserve(F, k, 2));
-    const CsrOp op{A, F};
-    if (k == 2) return run_multi<2, PCG>(op, M, B, p, ret, iterations, residual, mem);
-    if (k == 4) return run_multi<4, PCG>(op, M, B, p, ret, iterations, residual, mem);
-    return run_multi<8, PCG>(op, M, B, p, ret, iterations, residual, mem);
+    if (m.F) TRY(tri_multi_reserve(m.F, k, 2));
+    const CsrOp op{A, m.F};
+    return multi_k(k, [&](auto K) { return run_multi<decltype(K)::value, PCG>(op, M, B, p, ret, iterations, residual, mem); });
 }
 
 // the dense entries: A = K^T.K (normal = 1) or K (normal = 0, square), PCG with the reciprocals of lcg_hip_dense_build_jacobi
@@ -400,23 +306,19 @@ template <bool PCG>
 static int solve_dense_multi(const char *entry, const void *Kh, int k, int normal, double *M, const double *B, const lcg_para *param, int *ret,
                              int *iterations, double *residual, int mem)
 {
+    lcg_para p;
     TRY(multi_args(entry, k, M, B));
     lcg_hip_dense *D = dnm_handle(entry, Kh);
     if (!D) return LCG_HIP_E_ARG;
     if (normal != 0 && normal != 1) { ctx().err = std::string(entry) + ": normal is neither 1 (K^T.K) nor 0 (K)"; return LCG_HIP_E_ARG; }
-    if (!normal && D->M != D->N) { ctx().err = std::string(entry) + ": the matrix is not square: normal = 0 needs a square one"; return LCG_HIP_E_ARG; }
-    if (mem != LCG_HIP_MEM_HOST && mem != LCG_HIP_MEM_DEVICE) { ctx().err = std::string(entry) + ": mem is neither LCG_HIP_MEM_HOST nor LCG_HIP_MEM_DEVICE"; return LCG_HIP_E_ARG; }
-    const lcg_para p = param ? *param : lcg_hip_default_parameters();
-    if (p.max_iterations < 0) return LCG_INVILAD_MAX_ITERATIONS;            // lcg.cpp:150-155
-    if (p.epsilon <= 0.0 || p.epsilon >= 1.0) return LCG_INVILAD_EPSILON;
+    TRY(multi_shape(entry, normal || D->M == D->N, mem, ": normal = 0 needs a square one"));
+    TRY(multi_para<false>(param, p, D->N));
     // no diagonal, or the other operator's (lcg_hip_dense_build_jacobi records which it built)
     if (PCG && (D->invdiag == nullptr || D->invdiag_normal != normal)) return LCG_NULL_PRECONDITION_MATRIX;
     TRY(ensure_init());
     TRY(dnm_reserve(D, k));
     const DenseOp op{D, normal};
-    if (k == 2) return run_multi<2, PCG>(op, M, B, p, ret, iterations, residual, mem);
-    if (k == 4) return run_multi<4, PCG>(op, M, B, p, ret, iterations, residual, mem);
-    return run_multi<8, PCG>(op, M, B, p, ret, iterations, residual, mem);
+    return multi_k(k, [&](auto K) { return run_multi<decltype(K)::value, PCG>(op, M, B, p, ret, iterations, residual, mem); });
 }
 
 } // namespace
@@ -460,3 +362,4 @@ int lcg_hip_dense_lpcg_multi(lcg_hip_dense_t K, int k, int normal, double *M, co
 }
 
 } // extern "C"
+

@@ -30,28 +30,9 @@
 namespace lcgh {
 namespace {
 
-struct BState {
+struct BState : MultiHead {
     double ak[MM_MAXK], wk[MM_MAXK], bk[MM_MAXK], rho[MM_MAXK], m2[MM_MAXK], r2[MM_MAXK], residual[MM_MAXK];
-    double eps, n_global;
-    int t[MM_MAXK];         // completed iterations (the reference's t), per column
-    int stop[MM_MAXK];      // ST_RUNNING, or why the column stopped (ST_CONVERGED, ST_NAN, ST_ALREADY)
-    int abs_diff;
-    int it;                 // iteration bodies started
-    int all_done;           // every column has stopped: every later kernel is a no-op
-    int pub_mask;           // HostStatus is refreshed when (it & pub_mask) == 0, and when all columns have stopped
-    HostStatus *host;
 };
-static_assert(sizeof(BState) % 8 == 0, "BState is copied in 8-byte words");
-constexpr size_t BSLOT = 1024;
-static_assert(sizeof(BState) <= BSLOT, "two states share one small pool vector");
-
-__global__ void k_binit(BState *st, double eps, double n_global, int abs_diff, int pub_mask, HostStatus *host)
-{
-    double *w = reinterpret_cast<double *>(st);
-    for (int i = threadIdx.x; i < (int)(sizeof(BState) / 8); i += blockDim.x) w[i] = 0.0;
-    __syncthreads();
-    if (threadIdx.x == 0) { st->eps = eps; st->n_global = n_global; st->abs_diff = abs_diff; st->pub_mask = pub_mask; st->host = host; }
-}
 
 // ---- scalar steps ---------------------------------------------------------------------------------------------------------------------
 // setup: |m|^2 (clamped), r.r, rkr0_T (= r.r: r0_T is r, added in the same order); "already optimised" per column, in abs_diff mode
@@ -64,13 +45,7 @@ template <int K> struct BFinInit {
         for (int j = 0; j < K; j++) {
             const double m2 = clamp1(sum[j]), r2 = sum[K + j];
             st->m2[j] = m2; st->r2[j] = r2; st->rho[j] = r2;
-            double r;
-            bool already = false;
-            if (st->abs_diff && sqrt(r2) / st->n_global <= st->eps) { r = sqrt(r2) / st->n_global; already = true; }
-            else if (r2 / m2 <= st->eps) { r = r2 / m2; already = true; }
-            else r = st->abs_diff ? sqrt(r2) / st->n_global : r2 / m2;
-            st->residual[j] = r;
-            st->stop[j] = already ? ST_ALREADY : ST_RUNNING;
+            m_already(st, j, r2, m2);
         }
         all_stopped<K>(st);
         mpublish(st);
@@ -113,7 +88,7 @@ template <int K> struct BFinClose {
                 st->bk[j] = (st->ak[j] / st->wk[j]) * rho_new / st->rho[j];
                 st->rho[j] = rho_new;
                 st->r2[j] = r2;
-                const double r = st->abs_diff ? sqrt(r2) / st->n_global : r2 / st->m2[j];
+                const double r = m_residual(st, r2, st->m2[j]);
                 st->residual[j] = r;
                 if (r <= st->eps) st->stop[j] = ST_CONVERGED;
             }
@@ -172,112 +147,50 @@ template <bool JAC> struct BOpDir {        // p = r + betak (p - wk v) [ph = p /
 };
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
-template <int K>
-struct BicgSolve {
-    Ctx &c;
-    long n2;
-    int grid;
-    BState *cur, *next;
-    double *tab_dot, *tab_sum;      // the k-wide tables: the products' partial sums (v.r0; t.s and t.t), the update pass's
-
-    // TREE: multi_loop.hpp -- 1: this pass leaves sums, 2: it adds up a pass's sums (the products' sums are msum's: their order is
-    // the matrix's alone)
-    template <int TREE, class Fin, class Op, bool ALL = false> int pass(Fin fin, Op op, const double *pin, int gin, int g = 0)
-    {
-        c.cnt_vec++;
-        hipLaunchKernelGGL((k_mvecf<BState, K, Fin, Op, ALL, TREE>), dim3(g ? g : grid), dim3(VB), 0, c.stream, fin, op, n2, pin, gin, tab_sum, cur, next);
-        HIPCHK(hipGetLastError());
-        std::swap(cur, next);
-        return 0;
-    }
-};
-
+// The passes' TREE (multi_loop.hpp) -- 1: the pass leaves sums, 2: it adds up a pass's sums (the products' sums are msum's: their order
+// is the matrix's alone)
 template <int K, bool JAC>
 static int run_bicg(lcg_hip_csr *A, const TriFactor *F, double *M, const double *B, const lcg_para &p, int *ret, int *iterations,
                     double *residual, int mem)
 {   // F: the factor that is M (its k-wide work vectors reserved by the caller); JAC: the handle's Jacobi diagonal; neither: plain
-    Ctx &c = ctx();
-    const int n = A->n_rows;
-    const size_t nb = sizeof(double) * (size_t)n * K;
-    HostBridge hb;
-    Workspace ws;
-    SolveGuard guard(c);
-    TRY(hb.open(mem, M, B, nb, c.stream));
-    double *r = nullptr, *r0 = nullptr, *pk = nullptr, *s = nullptr, *v = nullptr, *t = nullptr, *ph = nullptr, *sh = nullptr;
-    double *big = nullptr, *stmem = nullptr;
-    TRY(ws.get(r, nullptr, nb));
-    TRY(ws.get(r0, nullptr, nb));
-    TRY(ws.get(pk, nullptr, nb));
-    TRY(ws.get(s, nullptr, nb));
-    TRY(ws.get(v, nullptr, nb));
-    TRY(ws.get(t, nullptr, nb));
-    if (JAC || F) { TRY(ws.get(ph, nullptr, nb)); TRY(ws.get(sh, nullptr, nb)); }
+    MultiFrame<BState, K, K / 2> f(A->n_rows);
+    Ctx &c = f.c;
+    TRY(f.open(mem, M, B));
+    double *r = nullptr, *r0 = nullptr, *pk = nullptr, *s = nullptr, *v = nullptr, *t = nullptr, *ph = nullptr, *sh = nullptr, *big = nullptr;
+    TRY(f.vec(r));
+    TRY(f.vec(r0));
+    TRY(f.vec(pk));
+    TRY(f.vec(s));
+    TRY(f.vec(v));
+    TRY(f.vec(t));
+    if (JAC || F) { TRY(f.vec(ph)); TRY(f.vec(sh)); }
     else { ph = pk; sh = s; }
     const size_t nbig = spmm_big_doubles(A->main, K, true);
-    if (nbig) TRY(ws.get(big, nullptr, sizeof(double) * nbig));
-    TRY(ws.get(stmem, nullptr, 2 * BSLOT));
-
-    const CsrPart &P = A->main;
-    BicgSolve<K> k{c, (long)n * (K / 2), 0, reinterpret_cast<BState *>(stmem),
-                   reinterpret_cast<BState *>(reinterpret_cast<char *>(stmem) + BSLOT), c.partials_pair[0], c.partials_pair[1]};
-    k.grid = (int)(tree_leaves(n) * (K / 2) / VB);      // a thread's rows do not depend on K (multi_loop.hpp: TREE)
-    const long work = (long)n * K;
-    c.hstat->it = 0; c.hstat->done = 0; c.hstat->status = 0; c.hstat->t = 0; c.hstat->residual = 0.0;
-    hipLaunchKernelGGL(k_binit, dim3(1), dim3(64), 0, c.stream, k.cur, p.epsilon, (double)n, p.abs_diff, work >= (1 << 20) ? 0 : 3, c.hstat_dev);
-    HIPCHK(hipGetLastError());
+    if (nbig) TRY(f.ws.get(big, nullptr, sizeof(double) * nbig));
+    TRY(f.start(f.tree_grid(), p.epsilon, p.abs_diff));
 
     // setup (lcg.cpp:650-689): A.m for the guess, r0 = p = r, the verdict "already optimised"
+    const CsrPart &P = A->main;
     c.cnt_ax++;
     TRY(spmm_launch(P, K, M, t, c.stream, nullptr));
-    TRY((k.template pass<1, MFinNone, BOpInit<JAC>, true>(MFinNone{}, BOpInit<JAC>{t, B, M, A->invdiag, r, r0, pk, ph}, nullptr, 0)));
-    TRY((k.template pass<2, BFinInit<K>, MOpNone, true>(BFinInit<K>{}, MOpNone{}, k.tab_sum, k.grid, 1)));
+    TRY((f.template pass<1, true>(MFinNone{}, BOpInit<JAC>{t, B, M, A->invdiag, r, r0, pk, ph}, nullptr, 0)));
+    TRY((f.template pass<2, true>(BFinInit<K>{}, MOpNone{}, f.tab_sum, f.grid, 1)));
 
     const int m_launches = F ? tri_apply_launches(F, 2) : 0;       // counted as vector passes (lcg_hip_last_launches)
     int g_dot = 0, g_dot2 = 0;
-    auto body = [&]() -> int {
-        if (F) { c.cnt_vec += m_launches; TRY(tri_apply_multi(F, K, 2, pk, ph, c.stream, &k.cur->all_done)); }
+    f.run(p.max_iterations, [&]() -> int {
+        if (F) { c.cnt_vec += m_launches; TRY(tri_apply_multi(F, K, 2, pk, ph, c.stream, &f.cur->all_done)); }
         c.cnt_ax++;
-        TRY(spmm_launch(P, K, ph, v, c.stream, &k.cur->all_done, r0, big, k.tab_dot, &g_dot));                      // :718-724
-        TRY(k.template pass<0>(BFinAlpha<K>{}, BOpS<JAC>{r, v, A->invdiag, s, sh, m2d()}, k.tab_dot, g_dot));                     // :725-731
-        if (F) { c.cnt_vec += m_launches; TRY(tri_apply_multi(F, K, 2, s, sh, c.stream, &k.cur->all_done)); }
+        TRY(spmm_launch(P, K, ph, v, c.stream, &f.cur->all_done, r0, big, f.tab_dot, &g_dot));                      // :718-724
+        TRY(f.template pass<0>(BFinAlpha<K>{}, BOpS<JAC>{r, v, A->invdiag, s, sh, m2d()}, f.tab_dot, g_dot));                     // :725-731
+        if (F) { c.cnt_vec += m_launches; TRY(tri_apply_multi(F, K, 2, s, sh, c.stream, &f.cur->all_done)); }
         c.cnt_ax++;
-        TRY(spmm_launch(P, K, sh, t, c.stream, &k.cur->all_done, s, big, k.tab_dot, &g_dot2, true));                // :733-740
-        TRY(k.template pass<1>(BFinOmega<K>{}, BOpUpdate{M, r, ph, sh, s, t, r0, m2d(), m2d()}, k.tab_dot, g_dot2));              // :741-772
-        TRY(k.template pass<2>(BFinClose<K>{}, BOpDir<JAC>{pk, ph, r, v, A->invdiag, m2d(), m2d()}, k.tab_sum, k.grid));          // :773-780
+        TRY(spmm_launch(P, K, sh, t, c.stream, &f.cur->all_done, s, big, f.tab_dot, &g_dot2, true));                // :733-740
+        TRY(f.template pass<1>(BFinOmega<K>{}, BOpUpdate{M, r, ph, sh, s, t, r0, m2d(), m2d()}, f.tab_dot, g_dot2));              // :741-772
+        TRY(f.template pass<2>(BFinClose<K>{}, BOpDir<JAC>{pk, ph, r, v, A->invdiag, m2d(), m2d()}, f.tab_sum, f.grid));          // :773-780
         return 0;
-    };
-
-    BState h;
-    auto read_state = [&]() -> int {
-        HIPCHK(hipMemcpyAsync(&h, k.cur, sizeof h, hipMemcpyDeviceToHost, c.stream));
-        HIPCHK(hipStreamSynchronize(c.stream));
-        return 0;
-    };
-    const int rc = enqueue_ahead(c, p.max_iterations, work >= (1 << 20) ? 6 : 24, body, read_state, h);
-    if (!rc) {
-        int longest = 0;
-        for (int j = 0; j < K; j++) {
-            if (ret) ret[j] = lcg_code(h.stop[j]);
-            if (iterations) iterations[j] = h.t[j];
-            if (residual) residual[j] = h.residual[j];
-            if (h.t[j] > h.t[longest]) longest = j;
-        }
-        c.last_iters = h.t[longest];
-        c.last_residual = h.residual[longest];
-        c.last_ax_calls = 0; c.last_ax_mean_us = 0.0; c.prof_pending = 0;
-    } else {
-        (void)hipStreamSynchronize(c.stream);       // nothing of this solve may still run on vectors that go back to the pool
-        (void)hipGetLastError();
-    }
-    const int rc2 = hb.close(c.stream);
-    return rc ? rc : rc2;
-}
-
-template <int K>
-static int run_bicg_k(lcg_hip_csr *A, bool jac, const TriFactor *F, double *M, const double *B, const lcg_para &p, int *ret, int *iterations,
-                      double *residual, int mem)
-{
-    return jac ? run_bicg<K, true>(A, F, M, B, p, ret, iterations, residual, mem) : run_bicg<K, false>(A, F, M, B, p, ret, iterations, residual, mem);
+    });
+    return f.finish(lcg_code, ret, iterations, residual);
 }
 
 } // namespace
@@ -291,31 +204,21 @@ int lcg_hip_lbicgstab_multi(lcg_hip_csr_t A, int k, int precond, double *M, cons
                             int *iterations, double *residual, int mem)
 {
     static const char *entry = "lcg_hip_lbicgstab_multi";
+    lcg_para p;
+    MultiPrecond m;
     NOT_DENSE(A, LCG_HIP_E_ARG);
     TRY(multi_args(entry, k, M, B));
     TRY(multi_handle(entry, A));
-    if (A->n_rows != A->n_cols) { ctx().err = std::string(entry) + ": the matrix is not square"; return LCG_HIP_E_ARG; }
-    if (mem != LCG_HIP_MEM_HOST && mem != LCG_HIP_MEM_DEVICE) { ctx().err = std::string(entry) + ": mem is neither LCG_HIP_MEM_HOST nor LCG_HIP_MEM_DEVICE"; return LCG_HIP_E_ARG; }
-    if (precond != LCG_HIP_M_NONE && precond != LCG_HIP_M_JACOBI && precond != LCG_HIP_M_IC0 && precond != LCG_HIP_M_ILU0) {
-        ctx().err = std::string(entry) + ": precond is none of LCG_HIP_M_NONE, LCG_HIP_M_JACOBI, LCG_HIP_M_IC0, LCG_HIP_M_ILU0";
-        return LCG_HIP_E_ARG;
-    }
-    const lcg_para p = param ? *param : lcg_hip_default_parameters();
-    if (p.max_iterations < 0) return LCG_INVILAD_MAX_ITERATIONS;            // lcg.cpp:637-638
-    if (p.epsilon <= 0.0 || p.epsilon >= 1.0) return LCG_INVILAD_EPSILON;
-    TriFactor *F = nullptr;
-    const bool jac = precond == LCG_HIP_M_JACOBI;
-    if (jac) {
-        if (A->invdiag == nullptr) return LCG_NULL_PRECONDITION_MATRIX;     // lcg_hip_csr_build_jacobi has not run
-    } else if (precond != LCG_HIP_M_NONE) {
-        F = precond == LCG_HIP_M_IC0 ? A->ic0 : A->ilu0;
-        if (!F || !F->ok) return LCG_NULL_PRECONDITION_MATRIX;              // lcg_hip_csr_build_ic0 / _ilu0 has not run (or its pivot failed)
-    }
+    TRY(multi_shape(entry, A->n_rows == A->n_cols, mem));
+    TRY(multi_precond(entry, A, precond, true, true, m));
+    TRY(multi_para<false>(param, p, A->n_rows));
+    if (!m.built) return LCG_NULL_PRECONDITION_MATRIX;
     TRY(ensure_init());
-    if (F) TRY(tri_multi_reserve(F, k, 2));
-    if (k == 2) return run_bicg_k<2>(A, jac, F, M, B, p, ret, iterations, residual, mem);
-    if (k == 4) return run_bicg_k<4>(A, jac, F, M, B, p, ret, iterations, residual, mem);
-    return run_bicg_k<8>(A, jac, F, M, B, p, ret, iterations, residual, mem);
+    if (m.F) TRY(tri_multi_reserve(m.F, k, 2));
+    return multi_k(k, [&](auto K) {
+        return m.jac ? run_bicg<decltype(K)::value, true>(A, m.F, M, B, p, ret, iterations, residual, mem)
+                     : run_bicg<decltype(K)::value, false>(A, m.F, M, B, p, ret, iterations, residual, mem);
+    });
 }
 
 } // extern "C"

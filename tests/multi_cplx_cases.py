@@ -6,7 +6,7 @@ Systems, all complex-symmetric and non-Hermitian, by the class of crows_per_bloc
 rows per block, <= 256 -> 16, more -> 4):
   * "helm", nx: the nx x nx five-point Laplacian plus a diagonal 0.05 + 0.3i (0.2 + u), u uniform from a fixed seed; b = A.xt.
     helm 40 is the issue's helm40 (n = 1600); helm 182 (n = 33124) has 518 row blocks of 64 (the folded d.Ad) and rows beyond
-    ctree_leaves' cap of 16384 (a second and third stride of a vector pass); helm 363 (n = 131769) has n k >= 2^20 at k = 8;
+    tree_leaves' cap of 16384 (a second and third stride of a vector pass); helm 363 (n = 131769) has n k >= 2^20 at k = 8;
   * "chain", n: the 1-D chain tridiag(-1, 2, -1) plus the same kind of diagonal, for the size edges n = 1, 2, 3, 65, 513
     (n = 1: the matrix [2.05 + 0.3i (0.2 + u)]);
   * "band30" / "band140", n: multi_cases.band_pattern (real SPD, every offset 1 .. h filled) plus i 0.3 (0.2 + u) d_ii on the
@@ -36,7 +36,7 @@ KS = (2, 4, 8)
 MM_MG = 512                         # multi.hpp
 CMM_W = 1536                        # multi_cplx.hpp: entries per LDS window of k_cspmm
 SMALL = 1e-2                        # the scale of the column whose |m|^2 stays below 1
-TREE_CAP = 32 * MM_MG               # multi_cplx.hpp: ctree_leaves' cap -- rows beyond it are a thread's second piece
+TREE_CAP = 32 * MM_MG               # multi.hpp: tree_leaves' cap for complex blocks -- rows beyond it are a thread's second piece
 
 rows_per_block = mc.rows_per_block  # csr_multi_cplx.hpp: crows_per_block has csr_multi.hip's classes
 
