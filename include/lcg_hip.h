@@ -596,6 +596,38 @@ int lcg_hip_dense_lcg_multi (lcg_hip_dense_t K, int k, int normal, double *M, co
                              int *ret, int *iterations, double *residual, int mem);
 int lcg_hip_dense_lpcg_multi(lcg_hip_dense_t K, int k, int normal, double *M, const double *B, const lcg_para *param,
                              int *ret, int *iterations, double *residual, int mem);
+/* The complex128 twins: the products of clcg_hip_dense_matvec over k = 2, 4 or 8 right-hand sides with K read ONCE
+ * for all of them.  A block of k complex vectors is clcg_hip_spmm's: one array of rows x k interleaved (re, im) pairs, row-major
+ * (column j of row i is doubles 2 (i k + j) and 2 (i k + j) + 1), its base 16-byte aligned.  Any other k, a null block or a misaligned
+ * base: LCG_HIP_E_ARG before the device or the handle is looked at.  Complex128 dense handles on one GPU: a handle that is not a dense
+ * one (a CSR handle included), a real dense handle, a non-square K where the loops' operator is asked for, a layout or conjugate
+ * outside 0 / 1, or X and Y overlapping return LCG_HIP_E_ARG with lcg_hip_last_error() naming the entry and the reason, Y untouched.
+ * Column j's bits depend on K, the handle's forced variant and column j of X (and U) alone: the same whatever k is, wherever the
+ * column stands in the block, whatever the other columns hold (NaN and Inf included), from call to call.  They need not be the bits
+ * of clcg_hip_dense_matvec on that column.  lcg_hip_dense_set_kernel's variants 1 / 2 force the k-wide row form / split row form.
+ * The k-wide table of partial sums belongs to the handle: the first call at a k larger than any before may allocate and wait, later
+ * ones only launch; lcg_hip_dense_destroy frees it.  The real k-wide entries above keep refusing complex handles. */
+/* Y = op(K).X: layout 0 K.X (X is N x k, Y is M x k), layout 1 K^T.X (X is M x k, Y is N x k); conjugate 1 takes conj(K) / K^H. */
+int clcg_hip_dense_matmat(lcg_hip_dense_t K, int k, const double *X, double *Y, int layout, int conjugate);
+/* The operator of the batched complex loops with the sum they take after it: Y = K.X for square K and, with U != NULL, the
+ * UNCONJUGATED dots[2 j], dots[2 j + 1] = re, im of sum_i Y_ij U_ij (clcg_dot; host, 2k values, after a stream synchronise; NULL
+ * dots = enqueue only).  The sum costs no pass over K: one k-wide launch over Y and U leaves at most 512 partial sums per component,
+ * added in a fixed order. */
+int clcg_hip_dense_op_multi_dot(lcg_hip_dense_t K, int k, const double *X, double *Y, const double *U, double *dots);
+/* The list of the complex k-wide kernel families (index 0, 1, ...; NULL behind the last): k_zdnm_row, k_zdnm_row_split, k_zdnm_col.
+ * lcg_hip_dense_multi_last_kernel reports them for a complex handle. */
+const char *clcg_hip_dense_multi_kernel_name(int index);
+/* Batched complex BiCG-sym and PCG on a square complex128 dense handle: clcg_hip_lbicg_sym_multi / clcg_hip_lpcg_multi's loops,
+ * contract and codes, word for word (below), with A = K: the stop rules, both "already optimised" criteria, the NaN rule with PCG's
+ * deviation, frozen-means-final, ret / iterations / residual per column, `mem`, 0 when the loop ran.  K is meant to be complex
+ * symmetric (not checked).  PCG uses the reciprocals of lcg_hip_dense_build_jacobi(K, 0, ...): none built returns
+ * LCG_NULL_PRECONDITION_MATRIX after the parameter checks.  Per iteration K is read once for all k columns.  Column j's results depend
+ * on K, the forced variant, column j of B and M and param alone, bit for bit.  lcg_hip_last_launches counts every kernel of the
+ * operator (its product, fold and the carried sum) as a product. */
+int clcg_hip_dense_lbicg_sym_multi(lcg_hip_dense_t K, int k, double *M, const double *B, const clcg_para *param,
+                                   int *ret, int *iterations, double *residual, int mem);
+int clcg_hip_dense_lpcg_multi(lcg_hip_dense_t K, int k, double *M, const double *B, const clcg_para *param,
+                              int *ret, int *iterations, double *residual, int mem);
 
 /* ---------------------------------------------------------------- kernels */
 /* Stand-alone launches of the hot-path kernels on the current stream (device pointers).

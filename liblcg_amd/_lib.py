@@ -147,6 +147,11 @@ SIGNATURES = {
     "lcg_hip_dense_multi_kernel_name": (C.c_char_p, [C.c_int]),
     "lcg_hip_dense_lcg_multi": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.POINTER(LcgPara), c_int_p, c_int_p, c_double_p, C.c_int]),
     "lcg_hip_dense_lpcg_multi": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.POINTER(LcgPara), c_int_p, c_int_p, c_double_p, C.c_int]),
+    "clcg_hip_dense_matmat": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, C.c_int]),
+    "clcg_hip_dense_op_multi_dot": (C.c_int, [vp, C.c_int, vp, vp, vp, c_double_p]),
+    "clcg_hip_dense_multi_kernel_name": (C.c_char_p, [C.c_int]),
+    "clcg_hip_dense_lbicg_sym_multi": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(ClcgPara), c_int_p, c_int_p, c_double_p, C.c_int]),
+    "clcg_hip_dense_lpcg_multi": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(ClcgPara), c_int_p, c_int_p, c_double_p, C.c_int]),
     "lcg_hip_csr_ax": (None, [vp, vp, vp, C.c_int]),
     "lcg_hip_jacobi_mx": (None, [vp, vp, vp, C.c_int]),
     "clcg_hip_csr_ax": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),

@@ -413,9 +413,33 @@ class DenseMatrix:
         _chk(L.load().lcg_hip_dense_op_multi_dot(self.h, k, int(normal), _ptr(X)[0], _ptr(Y)[0], _ptr(U)[0], out), "dense_op_multi_dot")
         return np.array(out[:], dtype=np.float64)
 
+    def cmatmat(self, X, Y, layout=0, conjugate=0):
+        """Y = op(K).X for the k = 2, 4 or 8 complex columns of X with K read once for all of them (clcg_hip_dense_matmat): layout 0
+        K.X (X (n, k), Y (m, k)), layout 1 K^T.X (X (m, k), Y (n, k)); conjugate 1: conj(K) / K^H.  C-contiguous complex128 CUDA
+        tensors, 16-byte aligned.  Complex128 matrices."""
+        k = _block_k(X, Y, cplx=True)
+        return _chk(L.load().clcg_hip_dense_matmat(self.h, k, _ptr(X)[0], _ptr(Y)[0], layout, conjugate), "dense_cmatmat")
+
+    def cop_multi_dot(self, X, Y, U):
+        """Y = K.X (square complex128 K) carrying one unconjugated sum per column (clcg_hip_dense_op_multi_dot): returns a complex128
+        array of k, [j] = sum_i Y_ij U_ij -- what the batched complex loops take after their product.  X, Y, U: (n, k) blocks."""
+        k = _block_k(X, Y, U, cplx=True)
+        out = (C.c_double * (2 * k))()
+        _chk(L.load().clcg_hip_dense_op_multi_dot(self.h, k, _ptr(X)[0], _ptr(Y)[0], _ptr(U)[0], out), "dense_cop_multi_dot")
+        return np.array(out[:], dtype=np.float64).view(np.complex128)
+
     @property
     def multi_last_kernel(self) -> str:
         return L.load().lcg_hip_dense_multi_last_kernel(self.h).decode()
+
+    @staticmethod
+    def cmulti_kernel_names():
+        lib, out, i = L.load(), [], 0
+        while True:
+            s = lib.clcg_hip_dense_multi_kernel_name(i)
+            if s is None:
+                return out
+            out.append(s.decode()); i += 1
 
     @staticmethod
     def multi_kernel_names():
@@ -600,6 +624,18 @@ def clpcg_multi(A, M, B, param) -> list:
     """Batched complex PCG with the handle's Jacobi diagonal (clcg_hip_lpcg_multi; A.build_jacobi() first).  A column whose sums
     turn NaN stops with CLCG_NAN_VALUE (the single-vector loop runs to the cap).  As clbicg_sym_multi."""
     return _multi("clcg_hip_lpcg_multi", A, M, B, param, cplx=True)
+
+
+def dense_clbicg_sym_multi(K, M, B, param) -> list:
+    """Batched BiCG on a square complex-symmetric complex128 dense matrix (clcg_hip_dense_lbicg_sym_multi): K is read once per
+    iteration for all k = 2, 4 or 8 columns.  As clbicg_sym_multi."""
+    return _multi("clcg_hip_dense_lbicg_sym_multi", K, M, B, param, cplx=True)
+
+
+def dense_clpcg_multi(K, M, B, param) -> list:
+    """Batched complex PCG on a dense matrix with the reciprocals of K.build_jacobi(normal=False)
+    (clcg_hip_dense_lpcg_multi).  As clpcg_multi."""
+    return _multi("clcg_hip_dense_lpcg_multi", K, M, B, param, cplx=True)
 
 
 def lcgs(Afp, Pfp, m, B, n_size, param, instance, *workspaces) -> SolveInfo:

@@ -1,12 +1,21 @@
-// dense.hpp -- what the dense units share (dense.hip: the single-vector products; dense_multi.hip: the k-wide ones): the handle and
-// the plans of the row and column forms.  Not installed.  DESIGN.md sections 14 and 19.
+// dense.hpp -- what the dense units share (dense.hip: the single-vector products; dense_multi.hip: the k-wide ones on real handles;
+// dense_multi_cplx.hip: those on complex128 handles): the handle and the plans of the row and column forms.  Not installed.
+// DESIGN.md sections 14, 19 and 20.
 #pragma once
 
 #include <algorithm>
 
 #include "internal.hpp"
 
-namespace lcgh { struct DenseMulti; }   // dense_multi.hip: the work memory of the k-wide products
+namespace lcgh {
+// what a handle owns for its k-wide products, sized for the largest k so far (dense_multi.hip: dnm_reserve)
+struct DenseMulti {
+    int kmax = 0;
+    double *t = nullptr;        // the M x k block between the two products of K^T.(K.X) (real handles)
+    double *part = nullptr;     // the k-wide slot table: k (complex handles: 2k) doubles per output row and slot
+    const char *last_kernel = "";
+};
+}
 
 struct lcg_hip_dense {
     uint64_t kind = lcgh::KIND_DENSE;   // internal.hpp: the word both kinds of handle begin with
@@ -75,5 +84,16 @@ int dnm_reserve(lcg_hip_dense *K, int k);
 // (multi.hpp's table format, added in index order by msum).  *launches grows by the kernels enqueued.  Checked handle, reserved k.
 int dnm_op(lcg_hip_dense *K, int k, int normal, const double *X, double *Y, hipStream_t s, const int *done, const double *U, double *dots,
            int *slots, int *launches);
+// y[j] = the sum of the table's S slots of n doubles each, in k_dnm_fold's fixed order (type-blind: the complex forms fold with it too)
+void dnm_fold_launch(const double *part, int S, int64_t n, double *y, hipStream_t s, const int *done);
+
+// dense_multi_cplx.hip
+// a complex128 dense handle, or nullptr with the entry's name and the reason in lcg_hip_last_error()
+lcg_hip_dense *zdnm_handle(const char *entry, const void *h);
+// Y = K.X for the k complex columns of a square K and, with U, column j's UNCONJUGATED Y_j . U_j as *slots <= MM_MG partial sums, re at
+// dots[(2 j) * MM_MG ...], im at dots[(2 j + 1) * MM_MG ...] (multi_cplx.hpp's table format).  *launches grows by the kernels enqueued.
+// Checked handle, reserved k.
+int zdnm_op(lcg_hip_dense *K, int k, const double *X, double *Y, hipStream_t s, const int *done, const double *U, double *dots, int *slots,
+            int *launches);
 
 } // namespace lcgh

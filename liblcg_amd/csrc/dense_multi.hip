@@ -27,14 +27,6 @@
 
 namespace lcgh {
 
-// what a handle owns for its k-wide products, sized for the largest k so far
-struct DenseMulti {
-    int kmax = 0;
-    double *t = nullptr;        // the M x k block between the two products of K^T.(K.X)
-    double *part = nullptr;     // the k-wide slot table
-    const char *last_kernel = "";
-};
-
 static const char *const DNM_NAMES[] = {"k_dnm_row", "k_dnm_row_split", "k_dnm_col", "k_dnm_ata_two_pass"};
 
 static int dnm_error(const char *fmt, ...)
@@ -273,7 +265,8 @@ __global__ __launch_bounds__(VB) void k_dnm_dots(const double *dots, int slots, 
 }
 
 // ---- work memory -------------------------------------------------------------------------------------------------------------------
-// doubles of the slot table per column of the block: the split row form under either plan, the column form
+// doubles of the slot table per column of the block: the split row form under either plan, the column form (complex handles: twice
+// that, and no M x k block -- there is no complex normal-equations operator)
 static int64_t dnm_table_doubles(int M, int N, int NP)
 {
     int64_t need = 0;
@@ -292,8 +285,8 @@ int dnm_reserve(lcg_hip_dense *K, int k)
     if (w->t) (void)hipFree(w->t);
     if (w->part) (void)hipFree(w->part);
     w->t = w->part = nullptr; w->kmax = 0;
-    HIPCHK(hipMalloc(&w->t, sizeof(double) * (size_t)K->M * k));
-    HIPCHK(hipMalloc(&w->part, sizeof(double) * (size_t)dnm_table_doubles(K->M, K->N, K->NP) * k + 16));
+    if (!K->cplx) HIPCHK(hipMalloc(&w->t, sizeof(double) * (size_t)K->M * k));
+    HIPCHK(hipMalloc(&w->part, sizeof(double) * (size_t)dnm_table_doubles(K->M, K->N, K->NP) * k * (K->cplx ? 2 : 1) + 16));
     w->kmax = k;
     return 0;
 }
@@ -315,7 +308,7 @@ static int launched(const char *what)
     return e == hipSuccess ? 0 : fail(e, what, __FILE__, __LINE__);
 }
 
-static void fold_launch(const double *part, int S, int64_t n, double *y, hipStream_t s, const int *done)
+void dnm_fold_launch(const double *part, int S, int64_t n, double *y, hipStream_t s, const int *done)
 {
     hipLaunchKernelGGL(k_dnm_fold, dim3((unsigned)cdiv(n, MFOLD_J)), dim3(MFOLD_Q * MFOLD_J), 0, s, part, S, n, y, done);
 }
@@ -339,7 +332,7 @@ static int row_product(lcg_hip_dense *D, int k, const double *X, double *Y, int 
     if (k == 2) row_dispatch<2>(D, r, X, out, s, done);
     else if (k == 4) row_dispatch<4>(D, r, X, out, s, done);
     else row_dispatch<8>(D, r, X, out, s, done);
-    if (r.S > 1) fold_launch(D->multi->part, r.S, (int64_t)D->M * k, Y, s, done);
+    if (r.S > 1) dnm_fold_launch(D->multi->part, r.S, (int64_t)D->M * k, Y, s, done);
     *launches += r.S > 1 ? 2 : 1;
     D->multi->last_kernel = r.S > 1 ? DNM_NAMES[1] : DNM_NAMES[0];
     return launched("dense k-wide row product");
@@ -355,7 +348,7 @@ static int col_product(lcg_hip_dense *D, int k, const double *X, double *Y, hipS
 #define DNM_COL(kk) hipLaunchKernelGGL((k_dnm_col<kk>), grid, dim3(256), 0, s, D->val, D->ldp, D->M, D->N, D->NP, c.CW, c.rps, X, out, n_out, done)
     if (k == 2) DNM_COL(2); else if (k == 4) DNM_COL(4); else DNM_COL(8);
 #undef DNM_COL
-    if (c.RS > 1) fold_launch(D->multi->part, c.RS, n_out, Y, s, done);
+    if (c.RS > 1) dnm_fold_launch(D->multi->part, c.RS, n_out, Y, s, done);
     *launches += c.RS > 1 ? 2 : 1;
     D->multi->last_kernel = DNM_NAMES[2];
     return launched("dense k-wide column product");

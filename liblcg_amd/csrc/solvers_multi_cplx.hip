@@ -33,6 +33,7 @@
 // for a tree (TREE bit 0); bit 1 says that `pin` holds a pass's sums, not the product's.
 #include "multi_loop.hpp"
 #include "multi_cplx.hpp"
+#include "dense.hpp"
 
 namespace lcgh {
 namespace {
@@ -169,10 +170,42 @@ inline int zm_code(int stop)
     }
 }
 
-template <int K, bool PCG>
-static int run_zm(lcg_hip_csr *A, double *M, const double *B, const clcg_para &p, int *ret, int *iterations, double *residual, int mem)
+// ---- the matrix, as the loop sees it (solvers_multi.hip's seam) ------------------------------------------------------------------------
+// rows(), invdiag() (the complex Jacobi reciprocals), big_doubles(k) (what the product's carried sum needs on its way to the table)
+// and apply(): Y = A.X for the K columns and, with U, column j's unconjugated (A.X)_j . U_j as *slots partial sums in `dots`, re in row
+// 2 j and im in row 2 j + 1 (multi_cplx.hpp's table format)
+struct ZCsrOp {
+    lcg_hip_csr *A;
+    int rows() const { return A->n_rows; }
+    const double *invdiag() const { return A->invdiag; }
+    size_t big_doubles(int k) const { return cspmm_big_doubles(A->main, k); }
+    int apply(Ctx &c, int k, const double *X, double *Y, const int *done, const double *U = nullptr, double *big = nullptr,
+              double *dots = nullptr, int *slots = nullptr) const
+    {
+        c.cnt_ax++;
+        return cspmm_launch(A->main, k, X, Y, c.stream, done, U, big, dots, slots);
+    }
+};
+// K of a square complex128 dense handle (dense_multi_cplx.hip): the product is two or three launches, all counted as products
+struct ZDenseOp {
+    lcg_hip_dense *D;
+    int rows() const { return D->N; }
+    const double *invdiag() const { return D->invdiag; }
+    size_t big_doubles(int) const { return 0; }
+    int apply(Ctx &c, int k, const double *X, double *Y, const int *done, const double *U = nullptr, double * = nullptr,
+              double *dots = nullptr, int *slots = nullptr) const
+    {
+        int launches = 0;
+        const int rc = zdnm_op(D, k, X, Y, c.stream, done, U, dots, slots, &launches);
+        c.cnt_ax += launches;
+        return rc;
+    }
+};
+
+template <int K, bool PCG, class OpA>
+static int run_zm(const OpA &A, double *M, const double *B, const clcg_para &p, int *ret, int *iterations, double *residual, int mem)
 {
-    MultiFrame<ZMState, K, K> f(A->n_rows);
+    MultiFrame<ZMState, K, K> f(A.rows());
     Ctx &c = f.c;
     TRY(f.open(mem, M, B));
     double *r = nullptr, *d = nullptr, *Ad = nullptr, *s = nullptr, *big = nullptr;
@@ -180,22 +213,19 @@ static int run_zm(lcg_hip_csr *A, double *M, const double *B, const clcg_para &p
     TRY(f.vec(d));
     TRY(f.vec(Ad));
     if (PCG) TRY(f.vec(s));
-    const size_t nbig = cspmm_big_doubles(A->main, K);
+    const size_t nbig = A.big_doubles(K);
     if (nbig) TRY(f.ws.get(big, nullptr, sizeof(double) * nbig));
     TRY(f.start(f.tree_grid(), p.epsilon, p.abs_diff));
 
     // setup: A.m for the guess, d = r (PCG: r / diag), the verdict "already optimised"
-    const CsrPart &P = A->main;
-    c.cnt_ax++;
-    TRY(cspmm_launch(P, K, M, Ad, c.stream, nullptr));
-    TRY((f.template pass<1, true>(MFinNone{}, ZMOpInit<PCG>{Ad, B, M, A->invdiag, r, d}, nullptr, 0)));
+    TRY(A.apply(c, K, M, Ad, nullptr));
+    TRY((f.template pass<1, true>(MFinNone{}, ZMOpInit<PCG>{Ad, B, M, A.invdiag(), r, d}, nullptr, 0)));
     TRY((f.template pass<3, true>(ZMFinInit<K, PCG>{}, MOpNone{}, f.tab_sum, f.grid, 1)));
 
     int g_dot = 0;
     f.run(p.max_iterations, [&]() -> int {
-        c.cnt_ax++;
-        TRY(cspmm_launch(P, K, d, Ad, c.stream, &f.cur->all_done, d, big, f.tab_dot, &g_dot));
-        TRY(f.template pass<1>(ZMFinAlpha<K>{}, ZMOpUpdate<PCG>{M, r, s, d, Ad, A->invdiag, m2d()}, f.tab_dot, g_dot));
+        TRY(A.apply(c, K, d, Ad, &f.cur->all_done, d, big, f.tab_dot, &g_dot));
+        TRY(f.template pass<1>(ZMFinAlpha<K>{}, ZMOpUpdate<PCG>{M, r, s, d, Ad, A.invdiag(), m2d()}, f.tab_dot, g_dot));
         TRY(f.template pass<3>(ZMFinClose<K, PCG>{}, ZMOpDir{d, PCG ? s : r, m2d()}, f.tab_sum, f.grid));
         return 0;
     });
@@ -213,7 +243,26 @@ static int zm_entry(const char *entry, lcg_hip_csr *A, int k, double *M, const d
     TRY(multi_para<true>(param, p, A->n_rows));
     if (PCG && A->invdiag == nullptr) return LCG_NULL_PRECONDITION_MATRIX;  // lcg_hip_csr_build_jacobi has not run
     TRY(ensure_init());
-    return multi_k(k, [&](auto K) { return run_zm<decltype(K)::value, PCG>(A, M, B, p, ret, iterations, residual, mem); });
+    const ZCsrOp op{A};
+    return multi_k(k, [&](auto K) { return run_zm<decltype(K)::value, PCG>(op, M, B, p, ret, iterations, residual, mem); });
+}
+
+// the dense entries: A = K, square; PCG with the reciprocals of lcg_hip_dense_build_jacobi(K, 0, ...)
+template <bool PCG>
+static int zm_dense_entry(const char *entry, const void *Kh, int k, double *M, const double *B, const clcg_para *param, int *ret,
+                          int *iterations, double *residual, int mem)
+{
+    clcg_para p;
+    TRY(multi_args(entry, k, M, B));
+    lcg_hip_dense *D = zdnm_handle(entry, Kh);
+    if (!D) return LCG_HIP_E_ARG;
+    TRY(multi_shape(entry, D->M == D->N, mem));
+    TRY(multi_para<true>(param, p, D->N));
+    if (PCG && D->invdiag == nullptr) return LCG_NULL_PRECONDITION_MATRIX;  // lcg_hip_dense_build_jacobi has not run
+    TRY(ensure_init());
+    TRY(dnm_reserve(D, k));
+    const ZDenseOp op{D};
+    return multi_k(k, [&](auto K) { return run_zm<decltype(K)::value, PCG>(op, M, B, p, ret, iterations, residual, mem); });
 }
 
 } // namespace
@@ -235,6 +284,18 @@ int clcg_hip_lpcg_multi(lcg_hip_csr_t A, int k, double *M, const double *B, cons
 {
     NOT_DENSE(A, LCG_HIP_E_ARG);
     return zm_entry<true>("clcg_hip_lpcg_multi", A, k, M, B, param, ret, iterations, residual, mem);
+}
+
+int clcg_hip_dense_lbicg_sym_multi(lcg_hip_dense_t K, int k, double *M, const double *B, const clcg_para *param, int *ret, int *iterations,
+                                   double *residual, int mem)
+{
+    return zm_dense_entry<false>("clcg_hip_dense_lbicg_sym_multi", K, k, M, B, param, ret, iterations, residual, mem);
+}
+
+int clcg_hip_dense_lpcg_multi(lcg_hip_dense_t K, int k, double *M, const double *B, const clcg_para *param, int *ret, int *iterations,
+                              double *residual, int mem)
+{
+    return zm_dense_entry<true>("clcg_hip_dense_lpcg_multi", K, k, M, B, param, ret, iterations, residual, mem);
 }
 
 } // extern "C"
