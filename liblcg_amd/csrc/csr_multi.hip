@@ -17,6 +17,10 @@
 //      <DOT = 2>: the same lanes also square what they write: a second partial sum per column, (A.X)_j . (A.X)_j, in rows K .. 2K - 1
 //      of the table -- the two sums BiCGStab takes after its second product (t.s, t.t).  The first has the bits of <DOT = 1>'s.
 //
+// This unit also defines what multi.hpp declares for all four k-wide product units: the CSR launch frame (multi_launch: R, wide loads,
+// folding, slots) that the complex product runs under too, the fold of the partial sums (k_mm_fold), the read-out of every *_dot entry
+// (multi_dots_read: k_mm_dots<NS>), multi_dot_run, multi_args and overlap.
+//
 // The handle's single-vector plans (packed columns, tiles, bins) are neither used nor built.
 #include "multi.hpp"
 
@@ -160,7 +164,7 @@ __global__ __launch_bounds__(VB) void k_spmm(int n, const int *__restrict__ rowp
     }
 }
 
-// more row blocks than a consumer adds up: sum f of a column = its blocks f * per .. f * per + per - 1, in order
+// more row blocks than a consumer adds up: sum f of a table row = its blocks f * per .. f * per + per - 1, in order (gridDim.y table rows)
 __global__ __launch_bounds__(VB) void k_mm_fold(const double *__restrict__ big, int nb, int per, int nf, double *__restrict__ out)
 {
     const int f = blockIdx.x * VB + threadIdx.x, j = blockIdx.y;
@@ -172,13 +176,36 @@ __global__ __launch_bounds__(VB) void k_mm_fold(const double *__restrict__ big, 
     out[j * MM_MG + f] = t;
 }
 
-// the k dots of lcg_hip_spmm_dot (the 2k of lcg_hip_spmm_dot2: K = 2k) out of their partial sums
-template <int K>
+// the NS results of a *_dot entry out of their partial sums
+template <int NS>
 __global__ __launch_bounds__(VB) void k_mm_dots(const double *dots, int slots, double *out)
 {
-    __shared__ double sums[K];
-    msum<K>(dots, slots, sums);
-    if (threadIdx.x < K) out[threadIdx.x] = sums[threadIdx.x];
+    __shared__ double sums[NS];
+    msum<NS>(dots, slots, sums);
+    if (threadIdx.x < NS) out[threadIdx.x] = sums[threadIdx.x];
+}
+
+int multi_fold_launch(const double *big, int nb, int ns, double *out, hipStream_t s)
+{
+    const int per = (nb + MM_MG - 1) / MM_MG, nf = (nb + per - 1) / per;
+    hipLaunchKernelGGL(k_mm_fold, dim3((nf + VB - 1) / VB, ns), dim3(VB), 0, s, big, nb, per, nf, out);
+    return nf;
+}
+
+int multi_dots_read(Ctx &c, int ns, int slots, double *dots)
+{
+    // (outside a solve the k-wide table of the loops is free: partials_pair[0] holds the partial sums, ax_partials the results)
+    const double *tab = c.partials_pair[0];
+    if (ns == 2) hipLaunchKernelGGL((k_mm_dots<2>), dim3(1), dim3(VB), 0, c.stream, tab, slots, c.ax_partials);
+    else if (ns == 4) hipLaunchKernelGGL((k_mm_dots<4>), dim3(1), dim3(VB), 0, c.stream, tab, slots, c.ax_partials);
+    else if (ns == 8) hipLaunchKernelGGL((k_mm_dots<8>), dim3(1), dim3(VB), 0, c.stream, tab, slots, c.ax_partials);
+    else hipLaunchKernelGGL((k_mm_dots<16>), dim3(1), dim3(VB), 0, c.stream, tab, slots, c.ax_partials);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(c.scratch_host, c.ax_partials, sizeof(double) * ns, hipMemcpyDeviceToHost, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (e != hipSuccess) return fail(e, "multi_dots_read", __FILE__, __LINE__);
+    for (int j = 0; j < ns; j++) dots[j] = c.scratch_host[j];
+    return 0;
 }
 
 static int rows_per_block(const CsrPart &P)
@@ -186,59 +213,75 @@ static int rows_per_block(const CsrPart &P)
     const double mean = P.n_rows > 0 ? (double)P.nnz / P.n_rows : 0.0;
     return mean <= 48.0 ? 64 : (mean <= 256.0 ? 16 : 4);      // lanes per row: 4, 16, 64
 }
-static long spmm_blocks(const CsrPart &P) { const int R = rows_per_block(P); return ((long)P.n_rows + R - 1) / R; }
+static long multi_blocks(const CsrPart &P) { const int R = rows_per_block(P); return ((long)P.n_rows + R - 1) / R; }
 
-size_t spmm_big_doubles(const CsrPart &P, int k, bool dot2)
+size_t multi_big_doubles(const CsrPart &P, int ns)
 {
-    const long nb = spmm_blocks(P);
-    return nb > MM_MG ? (size_t)nb * k * (dot2 ? 2 : 1) : 0;
+    const long nb = multi_blocks(P);
+    return nb > MM_MG ? (size_t)nb * ns : 0;
 }
 
-template <int K, int R>
-static void spmm_go(const CsrPart &P, const double *X, double *Y, hipStream_t s, const int *done, bool wide, const double *U, double *part,
-                    int pstride, bool dot2)
+int multi_launch(const CsrPart &P, int k, int tab, MultiGo go, const double *X, double *Y, hipStream_t s, const int *done, const double *U,
+                 double *big, double *dots, int *slots)
 {
-    const unsigned nb = (unsigned)(((long)P.n_rows + R - 1) / R);
-    if (U && dot2) hipLaunchKernelGGL((k_spmm<K, R, 2>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
-    else if (U) hipLaunchKernelGGL((k_spmm<K, R, 1>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
-    else hipLaunchKernelGGL((k_spmm<K, R, 0>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
+    const int R = rows_per_block(P);
+    const long nb = multi_blocks(P);
+    if (nb <= 0) return 0;
+    const bool wide = P.padded && (((uintptr_t)P.col | (uintptr_t)P.val) & 15) == 0;
+    const bool folded = U != nullptr && nb > MM_MG;
+    if (U && (!dots || !slots || (folded && !big))) return LCG_HIP_E_ARG;
+    go(P, k, R, X, Y, s, done, wide, U, folded ? big : dots, folded ? (int)nb : MM_MG, tab);
+    HIPCHK(hipGetLastError());
+    if (U) *slots = (int)nb;
+    if (folded) {
+        // (the fold runs whatever the stop flag says: after a stop it adds up what the last live product left, and nobody reads it)
+        *slots = multi_fold_launch(big, (int)nb, tab * k, dots, s);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
 }
-template <int K>
-static void spmm_k(const CsrPart &P, int R, const double *X, double *Y, hipStream_t s, const int *done, bool wide, const double *U, double *part,
-                   int pstride, bool dot2)
+
+int multi_dot_run(const CsrPart &P, int k, int tab, MultiGo go, const double *X, double *Y, const double *U, double *dots)
 {
-    if (R == 64) spmm_go<K, 64>(P, X, Y, s, done, wide, U, part, pstride, dot2);
-    else if (R == 16) spmm_go<K, 16>(P, X, Y, s, done, wide, U, part, pstride, dot2);
-    else spmm_go<K, 4>(P, X, Y, s, done, wide, U, part, pstride, dot2);
+    TRY(ensure_init());
+    Ctx &c = ctx();
+    double *big = nullptr;
+    const size_t nbig = multi_big_doubles(P, tab * k);
+    if (nbig) HIPCHK(hipMalloc(&big, sizeof(double) * nbig));
+    int slots = 0;
+    int rc = multi_launch(P, k, tab, go, X, Y, c.stream, nullptr, U, big, c.partials_pair[0], &slots);
+    if (!rc) rc = multi_dots_read(c, tab * k, slots, dots);
+    if (big) (void)hipFree(big);
+    return rc;
+}
+
+// k_spmm<k, R, DOT> with DOT = 0 without U, else the table rows per column
+static void spmm_go(const CsrPart &P, int k, int R, const double *X, double *Y, hipStream_t s, const int *done, bool wide, const double *U,
+                    double *part, int pstride, int tab)
+{
+    multi_k(k, [&](auto K) {
+        return multi_r(R, [&](auto RR) {
+            constexpr int KK = decltype(K)::value, RV = decltype(RR)::value;
+            const unsigned nb = (unsigned)(((long)P.n_rows + RV - 1) / RV);
+            if (U && tab == 2) hipLaunchKernelGGL((k_spmm<KK, RV, 2>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
+            else if (U) hipLaunchKernelGGL((k_spmm<KK, RV, 1>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
+            else hipLaunchKernelGGL((k_spmm<KK, RV, 0>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
+            return 0;
+        });
+    });
 }
 
 int spmm_launch(const CsrPart &P, int k, const double *X, double *Y, hipStream_t s, const int *done, const double *U, double *big,
                 double *dots, int *slots, bool dot2)
 {
-    const int R = rows_per_block(P);
-    const long nb = spmm_blocks(P);
-    if (nb <= 0) return 0;
-    const bool wide = P.padded && (((uintptr_t)P.col | (uintptr_t)P.val) & 15) == 0;
-    const bool folded = U != nullptr && nb > MM_MG;
-    if (U && (!dots || !slots || (folded && !big))) return LCG_HIP_E_ARG;
     if (dot2 && !U) return LCG_HIP_E_ARG;
-    double *part = folded ? big : dots;
-    const int pstride = folded ? (int)nb : MM_MG;
-    if (k == 2) spmm_k<2>(P, R, X, Y, s, done, wide, U, part, pstride, dot2);
-    else if (k == 4) spmm_k<4>(P, R, X, Y, s, done, wide, U, part, pstride, dot2);
-    else spmm_k<8>(P, R, X, Y, s, done, wide, U, part, pstride, dot2);
-    HIPCHK(hipGetLastError());
-    if (U) {
-        *slots = (int)nb;
-        if (folded) {
-            // (the fold runs whatever the stop flag says: after a stop it adds up what the last live product left, and nobody reads it)
-            const int per = (int)((nb + MM_MG - 1) / MM_MG), nf = (int)((nb + per - 1) / per);
-            hipLaunchKernelGGL(k_mm_fold, dim3((nf + VB - 1) / VB, dot2 ? 2 * k : k), dim3(VB), 0, s, big, (int)nb, per, nf, dots);
-            HIPCHK(hipGetLastError());
-            *slots = nf;
-        }
-    }
-    return 0;
+    return multi_launch(P, k, dot2 ? 2 : 1, spmm_go, X, Y, s, done, U, big, dots, slots);
+}
+
+bool overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+    const uintptr_t a0 = (uintptr_t)a, a1 = a0 + na, b0 = (uintptr_t)b, b1 = b0 + nb;
+    return a0 < b1 && b0 < a1;
 }
 
 int multi_args(const char *entry, int k, const void *a, const void *b, const void *c)
@@ -271,30 +314,7 @@ static int spmm_dot_entry(const char *entry, lcg_hip_csr *A, int k, const double
     TRY(multi_args(entry, k, X, Y, U));
     TRY(multi_handle(entry, A));
     if (!dots) { ctx().err = std::string(entry) + ": the result array is a null pointer"; return LCG_HIP_E_ARG; }
-    TRY(ensure_init());
-    Ctx &c = ctx();
-    // (outside a solve the k-wide table of the loops is free: partials_pair[0] holds the partial sums, ax_partials the results)
-    const int ns = dot2 ? 2 * k : k;
-    double *big = nullptr;
-    const size_t nbig = spmm_big_doubles(A->main, k, dot2);
-    if (nbig) HIPCHK(hipMalloc(&big, sizeof(double) * nbig));
-    int slots = 0;
-    int rc = spmm_launch(A->main, k, X, Y, c.stream, nullptr, U, big, c.partials_pair[0], &slots, dot2);
-    hipError_t e = hipSuccess;
-    if (!rc) {
-        if (ns == 2) hipLaunchKernelGGL((k_mm_dots<2>), dim3(1), dim3(VB), 0, c.stream, c.partials_pair[0], slots, c.ax_partials);
-        else if (ns == 4) hipLaunchKernelGGL((k_mm_dots<4>), dim3(1), dim3(VB), 0, c.stream, c.partials_pair[0], slots, c.ax_partials);
-        else if (ns == 8) hipLaunchKernelGGL((k_mm_dots<8>), dim3(1), dim3(VB), 0, c.stream, c.partials_pair[0], slots, c.ax_partials);
-        else hipLaunchKernelGGL((k_mm_dots<16>), dim3(1), dim3(VB), 0, c.stream, c.partials_pair[0], slots, c.ax_partials);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(c.scratch_host, c.ax_partials, sizeof(double) * ns, hipMemcpyDeviceToHost, c.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    }
-    if (big) (void)hipFree(big);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(e, "spmm_dot", __FILE__, __LINE__);
-    for (int j = 0; j < ns; j++) dots[j] = c.scratch_host[j];
-    return 0;
+    return multi_dot_run(A->main, k, dot2 ? 2 : 1, spmm_go, X, Y, U, dots);
 }
 
 } // namespace lcgh

@@ -12,9 +12,10 @@
 //      Column j's sum is therefore added in an order fixed by the matrix alone: the same bits whatever the other columns hold, whatever
 //      k is, from call to call.  No atomics.
 //      <DOT>: the lanes that write Y multiply it with U (unconjugated: clcg_dot, cublasZdotu) on the way out and the block leaves one
-//      partial sum per column and component (more than MM_MG blocks: k_cmm_fold adds runs of consecutive blocks, in order).
+//      partial sum per column and component (more than MM_MG blocks: k_mm_fold adds runs of consecutive blocks, in order).
 //
-// The handle's single-vector plans are neither used nor built.
+// The host side is multi.hpp's frame (csr_multi.hip: multi_launch, multi_dot_run) with two table rows per column; this unit adds the
+// kernel, its launcher and the handle's check.  The handle's single-vector plans are neither used nor built.
 #include "multi_cplx.hpp"
 
 namespace lcgh {
@@ -155,83 +156,25 @@ __global__ __launch_bounds__(VB) void k_cspmm(int n, const int *__restrict__ row
     }
 }
 
-// more row blocks than a consumer adds up: sum f of a table row = its blocks f * per .. f * per + per - 1, in order (k_mm_fold's rule)
-__global__ __launch_bounds__(VB) void k_cmm_fold(const double *__restrict__ big, int nb, int per, int nf, double *__restrict__ out)
+// k_cspmm<k, R, DOT> for multi.hpp's frame (two table rows per column: `tab` is not looked at)
+static void cspmm_go(const CsrPart &P, int k, int R, const double *X, double *Y, hipStream_t s, const int *done, bool wide, const double *U,
+                     double *part, int pstride, int)
 {
-    const int f = blockIdx.x * VB + threadIdx.x, j = blockIdx.y;
-    if (f >= nf) return;
-    const double *src = big + (size_t)j * nb;
-    const int b0 = f * per, b1 = min(nb, b0 + per);
-    double t = 0.0;
-    for (int b = b0; b < b1; b++) t += src[b];
-    out[j * MM_MG + f] = t;
-}
-
-// the k complex dots of clcg_hip_spmm_dot out of their partial sums (NS = 2k table rows)
-template <int NS>
-__global__ __launch_bounds__(VB) void k_cmm_dots(const double *dots, int slots, double *out)
-{
-    __shared__ double sums[NS];
-    msum<NS>(dots, slots, sums);
-    if (threadIdx.x < NS) out[threadIdx.x] = sums[threadIdx.x];
-}
-
-static int crows_per_block(const CsrPart &P)
-{
-    const double mean = P.n_rows > 0 ? (double)P.nnz / P.n_rows : 0.0;
-    return mean <= 48.0 ? 64 : (mean <= 256.0 ? 16 : 4);      // lanes per row: 4, 16, 64 (csr_multi.hip: rows_per_block)
-}
-static long cspmm_blocks(const CsrPart &P) { const int R = crows_per_block(P); return ((long)P.n_rows + R - 1) / R; }
-
-size_t cspmm_big_doubles(const CsrPart &P, int k)
-{
-    const long nb = cspmm_blocks(P);
-    return nb > MM_MG ? (size_t)nb * 2 * k : 0;
-}
-
-template <int K, int R>
-static void cspmm_go(const CsrPart &P, const double *X, double *Y, hipStream_t s, const int *done, bool wide, const double *U, double *part,
-                     int pstride)
-{
-    const unsigned nb = (unsigned)(((long)P.n_rows + R - 1) / R);
-    if (U) hipLaunchKernelGGL((k_cspmm<K, R, true>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
-    else hipLaunchKernelGGL((k_cspmm<K, R, false>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
-}
-template <int K>
-static void cspmm_k(const CsrPart &P, int R, const double *X, double *Y, hipStream_t s, const int *done, bool wide, const double *U, double *part,
-                    int pstride)
-{
-    if (R == 64) cspmm_go<K, 64>(P, X, Y, s, done, wide, U, part, pstride);
-    else if (R == 16) cspmm_go<K, 16>(P, X, Y, s, done, wide, U, part, pstride);
-    else cspmm_go<K, 4>(P, X, Y, s, done, wide, U, part, pstride);
+    multi_k(k, [&](auto K) {
+        return multi_r(R, [&](auto RR) {
+            constexpr int KK = decltype(K)::value, RV = decltype(RR)::value;
+            const unsigned nb = (unsigned)(((long)P.n_rows + RV - 1) / RV);
+            if (U) hipLaunchKernelGGL((k_cspmm<KK, RV, true>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
+            else hipLaunchKernelGGL((k_cspmm<KK, RV, false>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
+            return 0;
+        });
+    });
 }
 
 int cspmm_launch(const CsrPart &P, int k, const double *X, double *Y, hipStream_t s, const int *done, const double *U, double *big,
                  double *dots, int *slots)
 {
-    const int R = crows_per_block(P);
-    const long nb = cspmm_blocks(P);
-    if (nb <= 0) return 0;
-    const bool wide = P.padded && (((uintptr_t)P.col | (uintptr_t)P.val) & 15) == 0;
-    const bool folded = U != nullptr && nb > MM_MG;
-    if (U && (!dots || !slots || (folded && !big))) return LCG_HIP_E_ARG;
-    double *part = folded ? big : dots;
-    const int pstride = folded ? (int)nb : MM_MG;
-    if (k == 2) cspmm_k<2>(P, R, X, Y, s, done, wide, U, part, pstride);
-    else if (k == 4) cspmm_k<4>(P, R, X, Y, s, done, wide, U, part, pstride);
-    else cspmm_k<8>(P, R, X, Y, s, done, wide, U, part, pstride);
-    HIPCHK(hipGetLastError());
-    if (U) {
-        *slots = (int)nb;
-        if (folded) {
-            // (the fold runs whatever the stop flag says: after a stop it adds up what the last live product left, and nobody reads it)
-            const int per = (int)((nb + MM_MG - 1) / MM_MG), nf = (int)((nb + per - 1) / per);
-            hipLaunchKernelGGL(k_cmm_fold, dim3((nf + VB - 1) / VB, 2 * k), dim3(VB), 0, s, big, (int)nb, per, nf, dots);
-            HIPCHK(hipGetLastError());
-            *slots = nf;
-        }
-    }
-    return 0;
+    return multi_launch(P, k, 2, cspmm_go, X, Y, s, done, U, big, dots, slots);
 }
 
 int cmulti_handle(const char *entry, const lcg_hip_csr *A)
@@ -270,34 +213,7 @@ int clcg_hip_spmm_dot(lcg_hip_csr_t A, int k, const double *X, double *Y, const 
     TRY(multi_args(entry, k, X, Y, U));
     if (!dots) { ctx().err = std::string(entry) + ": the result array is a null pointer"; return LCG_HIP_E_ARG; }
     TRY(cmulti_handle(entry, A));
-    TRY(ensure_init());
-    Ctx &c = ctx();
-    // (outside a solve the k-wide table of the loops is free: partials_pair[0] holds the partial sums, ax_partials the results)
-    const int ns = 2 * k;
-    double *big = nullptr;
-    const size_t nbig = cspmm_big_doubles(A->main, k);
-    if (nbig) HIPCHK(hipMalloc(&big, sizeof(double) * nbig));
-    int slots = 0;
-    int rc = cspmm_launch(A->main, k, X, Y, c.stream, nullptr, U, big, c.partials_pair[0], &slots);
-    hipError_t e = hipSuccess;
-    if (!rc && slots == 0) {                    // no rows: nothing was launched
-        if (big) (void)hipFree(big);
-        for (int j = 0; j < ns; j++) dots[j] = 0.0;
-        return 0;
-    }
-    if (!rc) {
-        if (ns == 4) hipLaunchKernelGGL((k_cmm_dots<4>), dim3(1), dim3(VB), 0, c.stream, c.partials_pair[0], slots, c.ax_partials);
-        else if (ns == 8) hipLaunchKernelGGL((k_cmm_dots<8>), dim3(1), dim3(VB), 0, c.stream, c.partials_pair[0], slots, c.ax_partials);
-        else hipLaunchKernelGGL((k_cmm_dots<16>), dim3(1), dim3(VB), 0, c.stream, c.partials_pair[0], slots, c.ax_partials);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(c.scratch_host, c.ax_partials, sizeof(double) * ns, hipMemcpyDeviceToHost, c.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    }
-    if (big) (void)hipFree(big);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(e, "cspmm_dot", __FILE__, __LINE__);
-    for (int j = 0; j < ns; j++) dots[j] = c.scratch_host[j];
-    return 0;
+    return multi_dot_run(A->main, k, 2, cspmm_go, X, Y, U, dots);
 }
 
 } // extern "C"

@@ -8,7 +8,6 @@
 // A sweep sums a row exactly so, reads one vector and writes another: a row whose inputs are final has the exact solve's bits,
 // and after `levels` sweeps every row has.
 #include <chrono>
-#include <cstdarg>
 
 #include "csr_tri.hpp"
 
@@ -255,17 +254,6 @@ void tri_factor_free(TriFactor *&F)
     if (F->zp) hipFree(F->zp);
     delete F;
     F = nullptr;
-}
-
-int arg_error(const char *fmt, ...)
-{
-    char buf[256];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    ctx().err = buf;
-    return LCG_HIP_E_ARG;
 }
 
 void park(int rc) { if (rc && !ctx().ax_rc) ctx().ax_rc = rc; }

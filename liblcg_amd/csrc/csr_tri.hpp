@@ -184,7 +184,6 @@ static int run_levels(const IcTri &t, Row row, const int *done, hipStream_t s)
 // grouping set for test survives a rebuild), `build` run on the library's stream, the pivot's verdict (`pivot_rule`: what the
 // message says a usable pivot is not).  tri_schedule: both triangles' level sets into their schedules.  pivot_arm / pivot_read:
 // the pivot word before the factor's launches, and F->zero_pivot after them (drains the stream).
-int arg_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));     // LCG_HIP_E_ARG, the text into the error string
 int tri_build(lcg_hip_csr *A, TriSlot slot, const char *name, int dg_lo, const char *pivot_rule,
               int (*build)(lcg_hip_csr *, TriFactor *, hipStream_t));
 int tri_schedule(TriFactor *F, const std::vector<int> &level_fw, int nfw, const std::vector<int> &level_bw, int nbw);

@@ -8,12 +8,11 @@
 // bit-identical from call to call.
 //
 //   k_dn_row         y_i = sum_j K(i,j) x_j      W lanes per row (4 .. 64), butterfly sum over the lanes
-//   k_dn_row_split   the same with the columns cut into strips over gridDim.y (few rows, long rows) + k_dn_fold
-//   k_dn_col         y_j = sum_i K(i,j) x_i      a lane owns one pack of columns and walks a strip of rows + k_dn_fold
+//   k_dn_row_split   the same with the columns cut into strips over gridDim.y (few rows, long rows) + k_dnm_fold (dense_multi.hip)
+//   k_dn_col         y_j = sum_i K(i,j) x_i      a lane owns one pack of columns and walks a strip of rows + k_dnm_fold
 //   k_dn_ata1        y = K^T.(K.x) in one pass   a workgroup keeps whole rows in registers between the two products
 //                                                (rows of <= 1024 packs); forced to one workgroup: k_dn_ata_small
 #include <cmath>
-#include <cstdarg>
 #include <cstring>
 
 #include "dense.hpp"
@@ -22,14 +21,6 @@ namespace lcgh {
 
 static const char *const DN_NAMES[] = {"k_dn_row", "k_dn_row_split", "k_dn_col", "k_dn_ata_two_pass", "k_dn_ata_one_pass",
                                        "k_dn_ata_small"};
-
-static int dn_error(const char *fmt, ...)
-{
-    char buf[400];
-    va_list ap; va_start(ap, fmt); std::vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    ctx().err = buf;
-    return LCG_HIP_E_ARG;
-}
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double2 ldpack(const double2 *p) { return *p; }
@@ -79,37 +70,6 @@ __global__ __launch_bounds__(256) void k_dn_row(const double2 *__restrict__ K, i
         const int64_t at = (int64_t)blockIdx.y * M + i;
         if (CX) { out[2 * at] = acc.x; out[2 * at + 1] = acc.y; }
         else out[at] = acc.x;
-    }
-}
-
-// y[j] = the sum of the table's S slots of n doubles each, in a fixed order: the slots are cut into FOLD_Q runs of consecutive
-// slots, thread (q, j) adds run q's slots in index order (eight independent loads at a time), and the runs' sums are added in
-// run order.  16 outputs per workgroup.
-constexpr int FOLD_Q = 16, FOLD_J = 16;
-__global__ __launch_bounds__(FOLD_Q * FOLD_J) void k_dn_fold(const double *__restrict__ part, int S, int64_t n, double *__restrict__ y)
-{
-    __shared__ double sh[FOLD_Q][FOLD_J];
-    const int jj = threadIdx.x % FOLD_J, q = threadIdx.x / FOLD_J;
-    const int64_t j = (int64_t)blockIdx.x * FOLD_J + jj;
-    const int L = (S + FOLD_Q - 1) / FOLD_Q;
-    const int k0 = q * L, k1 = min(S, k0 + L);
-    double s = 0.0;
-    if (j < n) {
-        int k = k0;
-        for (; k + 7 < k1; k += 8) {
-            double v[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) v[u] = part[(int64_t)(k + u) * n + j];
-#pragma unroll
-            for (int u = 0; u < 8; u++) s += v[u];
-        }
-        for (; k < k1; k++) s += part[(int64_t)k * n + j];
-    }
-    sh[q][jj] = s;
-    __syncthreads();
-    if (q == 0 && j < n) {
-        for (int g = 1; g < FOLD_Q; g++) s += sh[g][jj];
-        y[j] = s;
     }
 }
 
@@ -312,16 +272,8 @@ static int64_t table_doubles(int M, int N, int NP, bool cplx)
 }
 
 // ---- launches --------------------------------------------------------------------------------------------------------------
-static int launched(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail(e, what, __FILE__, __LINE__);
-}
-
-static void fold_launch(const double *part, int S, int64_t n, double *y, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_dn_fold, dim3((unsigned)cdiv(n, FOLD_J)), dim3(FOLD_Q * FOLD_J), 0, s, part, S, n, y);
-}
+// the slots of a table added in k_dnm_fold's fixed order (dense_multi.hip: the one fold of the dense units; no batch to stop here)
+static void fold_launch(const double *part, int S, int64_t n, double *y, hipStream_t s) { dnm_fold_launch(part, S, n, y, s, nullptr); }
 
 template <bool CX, bool CONJ>
 static void row_dispatch(const lcg_hip_dense *K, const RowPlan &r, const double *x, double *out, hipStream_t s)
@@ -384,7 +336,7 @@ static int ata_product(lcg_hip_dense *K, const double *x, double *y, hipStream_t
 {
     int v = K->variant;
     if (v == DN_ATA1 || v == DN_ATA_SMALL) {
-        if (K->NP > 1024) return dn_error("lcg_hip_dense_ata_ax: the one-pass forms keep a row in one workgroup's registers: N <= 2048 (N = %d)", K->N);
+        if (K->NP > 1024) return arg_error("lcg_hip_dense_ata_ax: the one-pass forms keep a row in one workgroup's registers: N <= 2048 (N = %d)", K->N);
         return ata_one_pass(K, x, y, v == DN_ATA_SMALL, s);
     }
     if (v != DN_ATA2) {
@@ -401,7 +353,7 @@ static int ata_product(lcg_hip_dense *K, const double *x, double *y, hipStream_t
 static lcg_hip_dense *dense_of(const void *h, const char *entry)
 {
     if (dense_handle(h)) return static_cast<lcg_hip_dense *>(const_cast<void *>(h));
-    dn_error("%s: the handle is not a dense matrix (lcg_hip_dense_create)", entry);
+    arg_error("%s: the handle is not a dense matrix (lcg_hip_dense_create)", entry);
     return nullptr;
 }
 
@@ -449,12 +401,12 @@ extern "C" {
 
 int lcg_hip_dense_create(lcg_hip_dense_t *K, int m_rows, int n_cols, const double *val, int64_t ld, int is_complex, int mem)
 {
-    if (!K) return dn_error("lcg_hip_dense_create: the handle pointer is NULL");
+    if (!K) return arg_error("lcg_hip_dense_create: the handle pointer is NULL");
     *K = nullptr;
-    if (!val) return dn_error("lcg_hip_dense_create: val is NULL");
-    if (m_rows <= 0 || n_cols <= 0) return dn_error("lcg_hip_dense_create: M = %d, N = %d (both must be positive)", m_rows, n_cols);
-    if (ld < n_cols) return dn_error("lcg_hip_dense_create: ld = %lld < N = %d", (long long)ld, n_cols);
-    if (mem != LCG_HIP_MEM_HOST && mem != LCG_HIP_MEM_DEVICE) return dn_error("lcg_hip_dense_create: mem = %d", mem);
+    if (!val) return arg_error("lcg_hip_dense_create: val is NULL");
+    if (m_rows <= 0 || n_cols <= 0) return arg_error("lcg_hip_dense_create: M = %d, N = %d (both must be positive)", m_rows, n_cols);
+    if (ld < n_cols) return arg_error("lcg_hip_dense_create: ld = %lld < N = %d", (long long)ld, n_cols);
+    if (mem != LCG_HIP_MEM_HOST && mem != LCG_HIP_MEM_DEVICE) return arg_error("lcg_hip_dense_create: mem = %d", mem);
     int rc = ensure_init(); if (rc) return rc;
     lcg_hip_dense *D = nullptr;
     rc = dense_alloc(&D, m_rows, n_cols, is_complex != 0); if (rc) return rc;
@@ -468,11 +420,11 @@ int lcg_hip_dense_create(lcg_hip_dense_t *K, int m_rows, int n_cols, const doubl
 
 int lcg_hip_dense_create_rows(lcg_hip_dense_t *K, int m_rows, int n_cols, const double *const *rows, int is_complex)
 {
-    if (!K) return dn_error("lcg_hip_dense_create_rows: the handle pointer is NULL");
+    if (!K) return arg_error("lcg_hip_dense_create_rows: the handle pointer is NULL");
     *K = nullptr;
-    if (!rows) return dn_error("lcg_hip_dense_create_rows: rows is NULL");
-    if (m_rows <= 0 || n_cols <= 0) return dn_error("lcg_hip_dense_create_rows: M = %d, N = %d (both must be positive)", m_rows, n_cols);
-    for (int i = 0; i < m_rows; i++) if (!rows[i]) return dn_error("lcg_hip_dense_create_rows: row %d is NULL", i);
+    if (!rows) return arg_error("lcg_hip_dense_create_rows: rows is NULL");
+    if (m_rows <= 0 || n_cols <= 0) return arg_error("lcg_hip_dense_create_rows: M = %d, N = %d (both must be positive)", m_rows, n_cols);
+    for (int i = 0; i < m_rows; i++) if (!rows[i]) return arg_error("lcg_hip_dense_create_rows: row %d is NULL", i);
     int rc = ensure_init(); if (rc) return rc;
     lcg_hip_dense *D = nullptr;
     rc = dense_alloc(&D, m_rows, n_cols, is_complex != 0); if (rc) return rc;
@@ -503,11 +455,11 @@ const char *lcg_hip_dense_kernel_name(int index)
 int lcg_hip_dense_set_kernel(lcg_hip_dense_t K, int variant)
 {
     if (!dense_of(K, "lcg_hip_dense_set_kernel")) return LCG_HIP_E_ARG;
-    if (variant < DN_AUTO || variant > DN_ATA_SMALL) return dn_error("lcg_hip_dense_set_kernel: variant = %d (0 .. %d)", variant, (int)DN_ATA_SMALL);
+    if (variant < DN_AUTO || variant > DN_ATA_SMALL) return arg_error("lcg_hip_dense_set_kernel: variant = %d (0 .. %d)", variant, (int)DN_ATA_SMALL);
     if ((variant == DN_ATA1 || variant == DN_ATA_SMALL) && (K->cplx || K->NP > 1024))
-        return dn_error("lcg_hip_dense_set_kernel: the one-pass K^T.K.x serves real matrices of N <= 2048");
+        return arg_error("lcg_hip_dense_set_kernel: the one-pass K^T.K.x serves real matrices of N <= 2048");
     if (variant == DN_ROW_SPLIT && row_plan(K->M, K->NP, true, true).S < 2)
-        return dn_error("lcg_hip_dense_set_kernel: k_dn_row_split needs rows of >= 32 packs and M < 8192 (M = %d, N = %d): nothing to split", K->M, K->N);
+        return arg_error("lcg_hip_dense_set_kernel: k_dn_row_split needs rows of >= 32 packs and M < 8192 (M = %d, N = %d): nothing to split", K->M, K->N);
     K->variant = variant;
     return 0;
 }
@@ -515,10 +467,10 @@ int lcg_hip_dense_set_kernel(lcg_hip_dense_t K, int variant)
 static int dense_matvec(lcg_hip_dense_t K, const double *x, double *y, int layout, int conjugate, bool want_cplx, const char *entry)
 {
     if (!dense_of(K, entry)) return LCG_HIP_E_ARG;
-    if (K->cplx != want_cplx) return dn_error("%s: the matrix is %s", entry, K->cplx ? "complex (clcg_hip_dense_matvec)" : "real (lcg_hip_dense_matvec)");
-    if (!x || !y) return dn_error("%s: x or y is NULL", entry);
-    if (x == y) return dn_error("%s: x and y are the same vector", entry);
-    if (layout < 0 || layout > 1 || conjugate < 0 || conjugate > 1) return dn_error("%s: layout = %d, conjugate = %d", entry, layout, conjugate);
+    if (K->cplx != want_cplx) return arg_error("%s: the matrix is %s", entry, K->cplx ? "complex (clcg_hip_dense_matvec)" : "real (lcg_hip_dense_matvec)");
+    if (!x || !y) return arg_error("%s: x or y is NULL", entry);
+    if (x == y) return arg_error("%s: x and y are the same vector", entry);
+    if (layout < 0 || layout > 1 || conjugate < 0 || conjugate > 1) return arg_error("%s: layout = %d, conjugate = %d", entry, layout, conjugate);
     return layout ? col_product(K, x, y, conjugate, false, ctx().stream) : row_product(K, x, y, conjugate, K->variant, ctx().stream);
 }
 
@@ -535,9 +487,9 @@ int clcg_hip_dense_matvec(lcg_hip_dense_t K, const double *x, double *y, int lay
 int lcg_hip_dense_ata(lcg_hip_dense_t K, const double *x, double *y)
 {
     if (!dense_of(K, "lcg_hip_dense_ata")) return LCG_HIP_E_ARG;
-    if (K->cplx) return dn_error("lcg_hip_dense_ata: the matrix is complex");
-    if (!x || !y) return dn_error("lcg_hip_dense_ata: x or y is NULL");
-    if (x == y) return dn_error("lcg_hip_dense_ata: x and y are the same vector");
+    if (K->cplx) return arg_error("lcg_hip_dense_ata: the matrix is complex");
+    if (!x || !y) return arg_error("lcg_hip_dense_ata: x or y is NULL");
+    if (x == y) return arg_error("lcg_hip_dense_ata: x and y are the same vector");
     return ata_product(K, x, y, ctx().stream);
 }
 
@@ -546,7 +498,7 @@ int lcg_hip_dense_ata(lcg_hip_dense_t K, const double *x, double *y)
 static void dn_park(int rc) { if (rc && !ctx().ax_rc) ctx().ax_rc = rc; }
 static int dn_size(const lcg_hip_dense *K, int n, int want, const char *entry)
 {
-    return n == want ? 0 : dn_error("%s: n_size = %d, the matrix has %d %s", entry, n, want, K->M == K->N ? "rows" : "columns");
+    return n == want ? 0 : arg_error("%s: n_size = %d, the matrix has %d %s", entry, n, want, K->M == K->N ? "rows" : "columns");
 }
 
 void lcg_hip_dense_ata_ax(void *instance, const double *x, double *y, const int n)
@@ -561,7 +513,7 @@ void lcg_hip_dense_ax(void *instance, const double *x, double *y, const int n)
 {
     lcg_hip_dense *K = dense_of(instance, "lcg_hip_dense_ax");
     if (!K) return dn_park(LCG_HIP_E_ARG);
-    if (K->M != K->N) return dn_park(dn_error("lcg_hip_dense_ax: the matrix is %d x %d, not square (lcg_hip_dense_ata_ax multiplies by K^T.K)", K->M, K->N));
+    if (K->M != K->N) return dn_park(arg_error("lcg_hip_dense_ax: the matrix is %d x %d, not square (lcg_hip_dense_ata_ax multiplies by K^T.K)", K->M, K->N));
     if (dn_size(K, n, K->N, "lcg_hip_dense_ax")) return dn_park(LCG_HIP_E_ARG);
     dn_park(lcg_hip_dense_matvec(K, x, y, 0));
 }
@@ -570,7 +522,7 @@ void clcg_hip_dense_ax(void *instance, const double *x, double *y, const int n, 
 {
     lcg_hip_dense *K = dense_of(instance, "clcg_hip_dense_ax");
     if (!K) return dn_park(LCG_HIP_E_ARG);
-    if (K->M != K->N) return dn_park(dn_error("clcg_hip_dense_ax: the matrix is %d x %d, not square", K->M, K->N));
+    if (K->M != K->N) return dn_park(arg_error("clcg_hip_dense_ax: the matrix is %d x %d, not square", K->M, K->N));
     if (dn_size(K, n, K->N, "clcg_hip_dense_ax")) return dn_park(LCG_HIP_E_ARG);
     dn_park(clcg_hip_dense_matvec(K, x, y, layout, conjugate));
 }
@@ -578,9 +530,9 @@ void clcg_hip_dense_ax(void *instance, const double *x, double *y, const int n, 
 int lcg_hip_dense_build_jacobi(lcg_hip_dense_t K, int normal, double *diag_out)
 {
     if (!dense_of(K, "lcg_hip_dense_build_jacobi")) return LCG_HIP_E_ARG;
-    if (normal != 0 && normal != 1) return dn_error("lcg_hip_dense_build_jacobi: normal = %d (0: 1 / K(i,i), 1: 1 / sum_j K(j,i)^2)", normal);
-    if (normal && K->cplx) return dn_error("lcg_hip_dense_build_jacobi: the column sums of squares serve real matrices (sample1.cpp:98-107)");
-    if (!normal && K->M != K->N) return dn_error("lcg_hip_dense_build_jacobi: the matrix is %d x %d: its diagonal needs a square one", K->M, K->N);
+    if (normal != 0 && normal != 1) return arg_error("lcg_hip_dense_build_jacobi: normal = %d (0: 1 / K(i,i), 1: 1 / sum_j K(j,i)^2)", normal);
+    if (normal && K->cplx) return arg_error("lcg_hip_dense_build_jacobi: the column sums of squares serve real matrices (sample1.cpp:98-107)");
+    if (!normal && K->M != K->N) return arg_error("lcg_hip_dense_build_jacobi: the matrix is %d x %d: its diagonal needs a square one", K->M, K->N);
     Ctx &c = ctx();
     const int w = K->cplx ? 2 : 1, n = K->N;
     const size_t bytes = sizeof(double) * (size_t)w * (size_t)n;
@@ -603,12 +555,12 @@ int lcg_hip_dense_build_jacobi(lcg_hip_dense_t K, int normal, double *diag_out)
     for (int i = 0; i < n; i++) {
         if (!K->cplx) {
             if (d[i] == 0.0 || !std::isfinite(d[i])) { hipStreamSynchronize(c.stream); hipFree(K->invdiag); K->invdiag = nullptr;
-                return dn_error("lcg_hip_dense_build_jacobi: diagonal entry %d is %g", i, d[i]); }
+                return arg_error("lcg_hip_dense_build_jacobi: diagonal entry %d is %g", i, d[i]); }
             r[i] = 1.0 / d[i];
         } else {
             const double a = d[2 * (size_t)i], b = d[2 * (size_t)i + 1];
             if ((a == 0.0 && b == 0.0) || !std::isfinite(a) || !std::isfinite(b)) { hipStreamSynchronize(c.stream); hipFree(K->invdiag); K->invdiag = nullptr;
-                return dn_error("lcg_hip_dense_build_jacobi: diagonal entry %d is (%g, %g)", i, a, b); }
+                return arg_error("lcg_hip_dense_build_jacobi: diagonal entry %d is (%g, %g)", i, a, b); }
             // 1 / (a + i b) by the scaled division (Smith): no a^2 + b^2 that overflows or underflows before the quotient does
             if (std::fabs(a) >= std::fabs(b)) { const double q = b / a, den = a + b * q; r[2 * (size_t)i] = 1.0 / den; r[2 * (size_t)i + 1] = -q / den; }
             else { const double q = a / b, den = a * q + b; r[2 * (size_t)i] = q / den; r[2 * (size_t)i + 1] = -1.0 / den; }
@@ -624,10 +576,10 @@ static int dense_jacobi(void *instance, const double *x, double *z, int n, bool 
 {
     lcg_hip_dense *K = dense_of(instance, entry);
     if (!K) return LCG_HIP_E_ARG;
-    if (K->cplx != cplx) return dn_error("%s: the matrix is %s", entry, K->cplx ? "complex" : "real");
-    if (!K->invdiag) return dn_error("%s: lcg_hip_dense_build_jacobi() was not called", entry);
+    if (K->cplx != cplx) return arg_error("%s: the matrix is %s", entry, K->cplx ? "complex" : "real");
+    if (!K->invdiag) return arg_error("%s: lcg_hip_dense_build_jacobi() was not called", entry);
     if (dn_size(K, n, K->N, entry)) return LCG_HIP_E_ARG;
-    if (!x || !z) return dn_error("%s: x or z is NULL", entry);
+    if (!x || !z) return arg_error("%s: x or z is NULL", entry);
     const dim3 grid((unsigned)cdiv(n, 256));
     if (cplx) hipLaunchKernelGGL(k_dn_scale<true>, grid, dim3(256), 0, ctx().stream, K->invdiag, x, z, n);
     else hipLaunchKernelGGL(k_dn_scale<false>, grid, dim3(256), 0, ctx().stream, K->invdiag, x, z, n);

@@ -1,5 +1,6 @@
-// dense.hpp -- what the dense units share (dense.hip: the single-vector products; dense_multi.hip: the k-wide ones on real handles;
-// dense_multi_cplx.hip: those on complex128 handles): the handle and the plans of the row and column forms.  Not installed.
+// dense.hpp -- what the dense units share (dense.hip: the single-vector products; dense_multi.hip: the k-wide kernels and their host
+// flow for real and complex128 handles; dense_multi_cplx.hip: the complex entries): the handle and the plans of the row and column
+// forms.  Not installed.
 // DESIGN.md sections 14, 19 and 20.
 #pragma once
 
@@ -74,26 +75,32 @@ static inline ColPlan col_plan(int M, int NP)
     return c;
 }
 
-// dense_multi.hip
+// doubles per element of K and of a block of vectors: the one place the complex factor 2 of the k-wide slot sizes comes from
+static inline int dn_words(const lcg_hip_dense *K) { return K->cplx ? 2 : 1; }
+
+// dense_multi.hip: the k-wide host flow, written once for real and complex128 handles (it branches on K->cplx)
 void dnm_release(lcg_hip_dense *K);     // the k-wide work memory of a handle that goes (the caller has drained the device)
-// a real dense handle, or nullptr with the entry's name and the reason in lcg_hip_last_error()
-lcg_hip_dense *dnm_handle(const char *entry, const void *h);
+// a real (cplx: a complex128) dense handle, or nullptr with the entry's name and the reason in lcg_hip_last_error()
+lcg_hip_dense *dnm_handle(const char *entry, const void *h, bool cplx = false);
 // the handle's M x k block and k-wide slot table: the first call at a k larger than any before allocates and waits, later ones return
 int dnm_reserve(lcg_hip_dense *K, int k);
-// Y = (normal ? K^T.K : K).X for the k columns and, with U, column j's Y_j . U_j as *slots <= MM_MG partial sums at dots[j * MM_MG ...]
-// (multi.hpp's table format, added in index order by msum).  *launches grows by the kernels enqueued.  Checked handle, reserved k.
+// Y[M x k] = K.X and Y[N x k] = K^T.X (complex with conjugate: conj(K).X, K^H.X).  *launches grows by the kernels enqueued.  Checked
+// handle, reserved k.
+int dnm_row_product(lcg_hip_dense *K, int k, const double *X, double *Y, int conjugate, int variant, hipStream_t s, const int *done,
+                    int *launches);
+int dnm_col_product(lcg_hip_dense *K, int k, const double *X, double *Y, int conjugate, hipStream_t s, const int *done, int *launches);
+// Y = (normal ? K^T.K : K).X for the k columns and, with U, column j's Y_j . U_j as *slots <= MM_MG partial sums: real at
+// dots[j * MM_MG ...] (multi.hpp's table format), complex the UNCONJUGATED sum's re at dots[(2 j) * MM_MG ...] and im at
+// dots[(2 j + 1) * MM_MG ...] (multi_cplx.hpp's), added in index order by msum.  *launches grows by the kernels enqueued.  Checked
+// handle, reserved k; normal = 1 on real handles only.
 int dnm_op(lcg_hip_dense *K, int k, int normal, const double *X, double *Y, hipStream_t s, const int *done, const double *U, double *dots,
            int *slots, int *launches);
-// y[j] = the sum of the table's S slots of n doubles each, in k_dnm_fold's fixed order (type-blind: the complex forms fold with it too)
+// what the *_dense_op_multi_dot entries do after their checks: reserve, dnm_op, and with U and dots the read-out (multi_dots_read)
+int dnm_op_dot_run(lcg_hip_dense *K, int k, int normal, const double *X, double *Y, const double *U, double *dots);
+// y[j] = the sum of the table's S slots of n doubles each, in k_dnm_fold's fixed order.  The one fold of the dense units, type-blind:
+// dense.hip's single-vector forms (done = nullptr) and the complex forms fold with it too
 void dnm_fold_launch(const double *part, int S, int64_t n, double *y, hipStream_t s, const int *done);
-
-// dense_multi_cplx.hip
-// a complex128 dense handle, or nullptr with the entry's name and the reason in lcg_hip_last_error()
-lcg_hip_dense *zdnm_handle(const char *entry, const void *h);
-// Y = K.X for the k complex columns of a square K and, with U, column j's UNCONJUGATED Y_j . U_j as *slots <= MM_MG partial sums, re at
-// dots[(2 j) * MM_MG ...], im at dots[(2 j + 1) * MM_MG ...] (multi_cplx.hpp's table format).  *launches grows by the kernels enqueued.
-// Checked handle, reserved k.
-int zdnm_op(lcg_hip_dense *K, int k, const double *X, double *Y, hipStream_t s, const int *done, const double *U, double *dots, int *slots,
-            int *launches);
+// entry `index` of the k-wide kernel names of real (cplx: complex128) handles, or nullptr
+const char *dnm_kernel_name(bool cplx, int index);
 
 } // namespace lcgh

@@ -243,6 +243,8 @@ int ensure_init();
 // the flag a built-in product falls through on (null outside a solve)
 inline const int *ax_flag(Ctx &c) { return c.ax_skip ? c.ax_skip : (c.in_solve ? &c.state->done : nullptr); }
 int fail(hipError_t e, const char *what, const char *file, int line);
+int arg_error(const char *fmt, ...) __attribute__((format(printf, 1, 2)));     // LCG_HIP_E_ARG, the text into the error string
+int launched(const char *what);     // 0, or fail() with what the launches since the last look left in hipGetLastError()
 
 #define HIPCHK(call)                                                        \
     do {                                                                    \

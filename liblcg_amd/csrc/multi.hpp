@@ -1,4 +1,6 @@
-// multi.hpp -- what the multi-vector product (csr_multi.hip) and the batched loops (solvers_multi.hip) share.  Not installed.
+// multi.hpp -- what the k-wide products (csr_multi.hip, csr_multi_cplx.hip, dense_multi.hip, dense_multi_cplx.hip) and the batched loops
+// (solvers_multi*.hip) share: the checks of a block of vectors, the dispatch over k, the frame of the CSR products, the fold of their
+// partial sums and the read-out of a *_dot entry, each defined once in csr_multi.hip.  Not installed.
 //
 // A block of k vectors is ONE array of n * k doubles, row-major: X[i * k + j] is row i of column j (k = 2, 4, 8; the base
 // 16-byte aligned, so a row is k / 2 aligned 16-byte pieces).  DESIGN.md section 15.
@@ -19,13 +21,47 @@ int multi_args(const char *entry, int k, const void *a, const void *b, const voi
 // a CSR handle this path serves: real fp64, whole (not sharded), not dense (0, or LCG_HIP_E_ARG with the text)
 int multi_handle(const char *entry, const lcg_hip_csr *A);
 
-// Y = A.X for the k columns in one launch (P's plain CSR arrays: no plan is built or used).  With U: column j's sum
-// (A.X)_j . U_j is left as *slots <= MM_MG partial sums at dots[j * MM_MG ...], to be added in index order; with dot2 besides it
-// (A.X)_j . (A.X)_j at dots[(k + j) * MM_MG ...], the first sum's bits unchanged.  `big` holds the per-workgroup sums of a matrix
-// with more than MM_MG row blocks on their way there (spmm_big_doubles(P, k, dot2) doubles; may be null where that is 0).
+// the byte ranges [a, a + na) and [b, b + nb) meet
+bool overlap(const void *a, size_t na, const void *b, size_t nb);
+
+// f(std::integral_constant<int, k>) for the k that multi_args has let through; the same for the R = 64, 16, 4 rows of a block
+template <class F> int multi_k(int k, F f)
+{
+    if (k == 2) return f(std::integral_constant<int, 2>{});
+    if (k == 4) return f(std::integral_constant<int, 4>{});
+    return f(std::integral_constant<int, 8>{});
+}
+template <class F> int multi_r(int R, F f)
+{
+    if (R == 64) return f(std::integral_constant<int, 64>{});
+    if (R == 16) return f(std::integral_constant<int, 16>{});
+    return f(std::integral_constant<int, 4>{});
+}
+
+// The frame of the k-wide CSR products, real and complex (csr_multi.hip).  `go` launches the product kernel for R rows per block:
+// Y = A.X for the k columns in one launch (P's plain CSR arrays: no plan is built or used) and, with U, one partial sum per block
+// and table row at part[row * pstride + block].  A column owns `tab` table rows: 1 (real: (A.X)_j . U_j), 2 (real with dot2: besides it
+// (A.X)_j . (A.X)_j in rows k ..; complex: re, im of the unconjugated sum in rows 2 j, 2 j + 1).  multi_launch leaves every row's sum
+// as *slots <= MM_MG partial sums at dots[row * MM_MG ...], to be added in index order; `big` holds the per-block sums of a matrix with
+// more than MM_MG row blocks on their way there (multi_big_doubles(P, tab * k) doubles; may be null where that is 0).
+typedef void (*MultiGo)(const CsrPart &P, int k, int R, const double *X, double *Y, hipStream_t s, const int *done, bool wide,
+                        const double *U, double *part, int pstride, int tab);
+int multi_launch(const CsrPart &P, int k, int tab, MultiGo go, const double *X, double *Y, hipStream_t s, const int *done, const double *U,
+                 double *big, double *dots, int *slots);
+size_t multi_big_doubles(const CsrPart &P, int ns);
+// what a *_spmm_dot* entry does after its checks: work memory for big, multi_launch, multi_dots_read, free
+int multi_dot_run(const CsrPart &P, int k, int tab, MultiGo go, const double *X, double *Y, const double *U, double *dots);
+// out[row * MM_MG + f] = the sum of big[row * nb + f * per ...], per consecutive partial sums in order, for ns table rows; the nf <= MM_MG
+// sums per row it leaves
+int multi_fold_launch(const double *big, int nb, int ns, double *out, hipStream_t s);
+// dots[0 .. ns) = the ns running sums of the loops' table c.partials_pair[0], `slots` partial sums each, added by msum (ns = 2, 4, 8,
+// 16): launch, copy to the host, wait.  0, or the failure's code
+int multi_dots_read(Ctx &c, int ns, int slots, double *dots);
+
+// the real product: with U column j's (A.X)_j . U_j, with dot2 besides it (A.X)_j . (A.X)_j, the first sum's bits unchanged
 int spmm_launch(const CsrPart &P, int k, const double *X, double *Y, hipStream_t s, const int *done, const double *U = nullptr,
                 double *big = nullptr, double *dots = nullptr, int *slots = nullptr, bool dot2 = false);
-size_t spmm_big_doubles(const CsrPart &P, int k, bool dot2 = false);
+inline size_t spmm_big_doubles(const CsrPart &P, int k, bool dot2 = false) { return multi_big_doubles(P, dot2 ? 2 * k : k); }
 
 // Sum the g <= MM_MG partials of each of NS running sums (table row r = pin + r * MM_MG) into sums[r] (LDS), the whole block taking
 // part: per lane its partials in index order, the lanes by wave_sum, the wavefronts in order -- the same bits wherever and

@@ -17,9 +17,10 @@ int cmulti_handle(const char *entry, const lcg_hip_csr *A);
 // Y = A.X for the k complex columns in one launch (P's plain CSR arrays, val = interleaved (re, im): no plan is built or used).  With
 // U: column j's UNCONJUGATED sum (A.X)_j . U_j is left as *slots <= MM_MG partial sums, re at dots[(2 j) * MM_MG ...], im at
 // dots[(2 j + 1) * MM_MG ...], to be added in index order.  `big` holds the per-workgroup sums of a matrix with more than MM_MG row
-// blocks on their way there (cspmm_big_doubles(P, k) doubles; may be null where that is 0).
+// blocks on their way there (cspmm_big_doubles(P, k) doubles; may be null where that is 0).  multi.hpp's frame with two table rows per
+// column.
 int cspmm_launch(const CsrPart &P, int k, const double *X, double *Y, hipStream_t s, const int *done, const double *U = nullptr,
                  double *big = nullptr, double *dots = nullptr, int *slots = nullptr);
-size_t cspmm_big_doubles(const CsrPart &P, int k);
+inline size_t cspmm_big_doubles(const CsrPart &P, int k) { return multi_big_doubles(P, 2 * k); }
 
 } // namespace lcgh

@@ -329,12 +329,4 @@ inline int multi_precond(const char *entry, const lcg_hip_csr *A, int precond, b
     m.built = m.jac ? !need_diag || A->invdiag != nullptr : precond == LCG_HIP_M_NONE || (m.F && m.F->ok);
     return 0;
 }
-// f(std::integral_constant<int, k>) for the k that multi_args has let through
-template <class F> int multi_k(int k, F f)
-{
-    if (k == 2) return f(std::integral_constant<int, 2>{});
-    if (k == 4) return f(std::integral_constant<int, 4>{});
-    return f(std::integral_constant<int, 8>{});
-}
-
 } // namespace lcgh

@@ -22,6 +22,20 @@ int fail(hipError_t e, const char *what, const char *file, int line)
     return e == hipErrorNoDevice || e == hipErrorInvalidDevice ? LCG_HIP_E_NO_DEVICE : LCG_HIP_E_RUNTIME;
 }
 
+int arg_error(const char *fmt, ...)
+{
+    char buf[400];
+    va_list ap; va_start(ap, fmt); std::vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+    ctx().err = buf;
+    return LCG_HIP_E_ARG;
+}
+
+int launched(const char *what)
+{
+    hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : fail(e, what, __FILE__, __LINE__);
+}
+
 int ensure_init()
 {
     Ctx &c = ctx();

@@ -186,7 +186,7 @@ struct ZCsrOp {
         return cspmm_launch(A->main, k, X, Y, c.stream, done, U, big, dots, slots);
     }
 };
-// K of a square complex128 dense handle (dense_multi_cplx.hip): the product is two or three launches, all counted as products
+// K of a square complex128 dense handle (dense_multi.hip: dnm_op): the product is two or three launches, all counted as products
 struct ZDenseOp {
     lcg_hip_dense *D;
     int rows() const { return D->N; }
@@ -196,7 +196,7 @@ struct ZDenseOp {
               double *dots = nullptr, int *slots = nullptr) const
     {
         int launches = 0;
-        const int rc = zdnm_op(D, k, X, Y, c.stream, done, U, dots, slots, &launches);
+        const int rc = dnm_op(D, k, 0, X, Y, c.stream, done, U, dots, slots, &launches);
         c.cnt_ax += launches;
         return rc;
     }
@@ -254,7 +254,7 @@ static int zm_dense_entry(const char *entry, const void *Kh, int k, double *M, c
 {
     clcg_para p;
     TRY(multi_args(entry, k, M, B));
-    lcg_hip_dense *D = zdnm_handle(entry, Kh);
+    lcg_hip_dense *D = dnm_handle(entry, Kh, true);
     if (!D) return LCG_HIP_E_ARG;
     TRY(multi_shape(entry, D->M == D->N, mem));
     TRY(multi_para<true>(param, p, D->N));

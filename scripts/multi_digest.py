@@ -2,8 +2,15 @@
 the C ABI only: run on two builds of the library, the two outputs are identical line for line when the builds compute the same bits
 and enqueue the same launches.
 
-Entries: lcg_hip_lcg_multi, lcg_hip_lpcg_multi, lcg_hip_lpcg_multi_m (Jacobi, IC(0), ILU(0)), lcg_hip_lbicgstab_multi (none, Jacobi,
-IC(0), ILU(0)), clcg_hip_lbicg_sym_multi, clcg_hip_lpcg_multi, lcg_hip_dense_lcg_multi and lcg_hip_dense_lpcg_multi (normal = 1, 0).
+Entries, the loops: lcg_hip_lcg_multi, lcg_hip_lpcg_multi, lcg_hip_lpcg_multi_m (Jacobi, IC(0), ILU(0)), lcg_hip_lbicgstab_multi (none, Jacobi,
+IC(0), ILU(0)), clcg_hip_lbicg_sym_multi, clcg_hip_lpcg_multi, lcg_hip_dense_lcg_multi and lcg_hip_dense_lpcg_multi (normal = 1, 0),
+clcg_hip_dense_lbicg_sym_multi and clcg_hip_dense_lpcg_multi.  The products under them: lcg_hip_spmm, _spmm_dot, _spmm_dot2 and
+clcg_hip_spmm, _spmm_dot on the same CSR systems (the CLASS lists hold a system of more than MM_MG row blocks per class, so the
+fold of the partial sums runs); lcg_hip_dense_matmat (both layouts), lcg_hip_dense_ata_multi and lcg_hip_dense_op_multi_dot on the
+real dense shapes, clcg_hip_dense_matmat (both layouts, both conjugations) and clcg_hip_dense_op_multi_dot on the sizes of
+tests/dense_multi_cplx_cases.py, each under the automatic variant and under the forced row forms (lcg_hip_dense_set_kernel 1, 2; a
+refused variant leaves its code and text), with lcg_hip_dense_multi_last_kernel after every call.  Per product: the return code and
+one hash over the block it wrote and the sums it returned.
 Systems: the CLASS lists of tests/multi_cases.py, multi_bicg_cases.py and multi_cplx_cases.py with the k of their EDGE_CASES, the
 shapes of tests/dense_multi_cases.py.  Per system and k: runs capped at 6 iterations under both stop rules in device memory and
 under the relative rule in host memory; a converged run (cap 2000) and a run with max_iterations = 0 where the system has at most
@@ -11,7 +18,8 @@ CONVERGED_ROWS rows; for k >= 4 a batch of mixed verdicts (a column already opti
 ILU(0) as M on the systems of at most FACTOR_ROWS rows.  Per run: the return code, one hash over the solution block, ret,
 iterations and the bits of residual, and the four counts of lcg_hip_last_launches -- those where a column ran to the cap; a batch
 that stops earlier leaves counts that depend on how far ahead of the device the host had enqueued (see solve()).  Last, the code and
-text of every refusal of every entry, with nothing built, then Jacobi, then IC(0), then everything.
+text of every refusal of every entry, with nothing built, then Jacobi, then IC(0), then everything; and of the product entries,
+each also with two faults at once, so that the order of their checks is part of the digest.
 
 What is printed and written is ONE line per entry and system (per entry and state of the handles for the refusals): the SHA-256 of
 the runs' lines.  --detail prints those lines too, to find what differs.
@@ -68,6 +76,7 @@ def main():
         _lib.SO_PATH = os.path.abspath(args.lib)
     from liblcg_amd import api
     import dense_multi_cases as DC
+    import dense_multi_cplx_cases as ZD
     import multi_bicg_cases as BC
     import multi_cases as MC
     import multi_cplx_cases as ZC
@@ -127,6 +136,41 @@ def main():
             for rule, para in MC.RULES.items():
                 one(f"mixed verdicts {rule}", Mm, Bm, "device", max_iterations=CAP, **para)
 
+    def block(rows, k, seed, cplx=False):
+        """A (rows, k) block of seeded values on the device, float64 or complex128."""
+        r = np.random.default_rng(seed)
+        a = r.uniform(-1.0, 1.0, (rows, k)) + (1j * r.uniform(-1.0, 1.0, (rows, k)) if cplx else 0.0)
+        return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+    def product(tag, what, fn, h, k, args, Y, ndots=0, last=None):
+        """One product call: Y is what it writes, ndots the doubles it returns, last the handle whose kernel name follows."""
+        Y.fill_(-7.0)
+        dots = (C.c_double * max(ndots, 1))(*([-7.0] * max(ndots, 1)))
+        rc = fn(h, k, *[a.data_ptr() if hasattr(a, "data_ptr") else a for a in args], *([dots] if ndots else []))
+        torch.cuda.synchronize()
+        name = (" " + lib.lcg_hip_dense_multi_last_kernel(last).decode()) if last is not None else ""
+        say(tag, f"{tag} k={k} {what}: rc {rc} {sha(Y.cpu().numpy(), np.array(list(dots)[:ndots]).view(np.uint64))}{name}")
+
+    def csr_products(tag, A, n, k, cplx):
+        X, U, Y = block(n, k, 11 * n + k, cplx), block(n, k, 13 * n + k, cplx), block(n, k, 1, cplx)
+        if cplx:
+            product(f"clcg_hip_spmm {tag}", "A.X", lib.clcg_hip_spmm, A.h, k, (X, Y), Y)
+            product(f"clcg_hip_spmm_dot {tag}", "A.X, sums", lib.clcg_hip_spmm_dot, A.h, k, (X, Y, U), Y, 2 * k)
+        else:
+            product(f"lcg_hip_spmm {tag}", "A.X", lib.lcg_hip_spmm, A.h, k, (X, Y), Y)
+            product(f"lcg_hip_spmm_dot {tag}", "A.X, sums", lib.lcg_hip_spmm_dot, A.h, k, (X, Y, U), Y, k)
+            product(f"lcg_hip_spmm_dot2 {tag}", "A.X, both sums", lib.lcg_hip_spmm_dot2, A.h, k, (X, Y, U), Y, 2 * k)
+
+    def variants(tag, D):
+        """The automatic variant, then the forced row forms the handle accepts (a refusal leaves its code and text)."""
+        for v in (0, 1, 2):
+            rc = lib.lcg_hip_dense_set_kernel(D.h, v)
+            if rc:
+                say(tag, f"{tag} variant {v}: refused {rc}: {err()}")
+            else:
+                yield v
+        lib.lcg_hip_dense_set_kernel(D.h, 0)
+
     def ks_of(mod, key):
         return sorted(k for (kind, n, k) in mod.EDGE_CASES if (kind, n) == key) or list(mod.KS)     # (no edge: a module's main system)
 
@@ -143,6 +187,7 @@ def main():
                 if extra in ((BC.M_IC0,), (BC.M_ILU0,)) and S["n"] > FACTOR_ROWS:
                     continue
                 cases(f"{name} {key[0]}-{key[1]}", fn, A.h, extra, S["n"], k, False, MC.columns(S["n"], S["b"], k), MC.guesses(S, k), S["xt"], S["b"])
+            csr_products(f"{key[0]}-{key[1]}", A, S["n"], k, False)
         A.destroy()
     bicg_entries = [(f"lcg_hip_lbicgstab_multi {name}", lib.lcg_hip_lbicgstab_multi, (code,))
                     for name, code in (("none", BC.M_NONE), ("jacobi", BC.M_JACOBI), ("ic0", BC.M_IC0), ("ilu0", BC.M_ILU0))]
@@ -167,6 +212,7 @@ def main():
             for name, fn in (("clcg_hip_lbicg_sym_multi", lib.clcg_hip_lbicg_sym_multi), ("clcg_hip_lpcg_multi", lib.clcg_hip_lpcg_multi)):
                 cases(f"{name} {key[0]}-{key[1]}", fn, A.h, (), S["n"], k, True, ZC.columns(S["n"], S["b"], k), ZC.guesses(S, k), S["xt"], S["b"],
                       converge=key[0] != "case1kc")                  # (case1kc: capped runs only)
+            csr_products(f"{key[0]}-{key[1]}", A, S["n"], k, True)
         A.destroy()
 
     # ---- dense -----------------------------------------------------------------------------------------------------------------------------
@@ -178,6 +224,36 @@ def main():
             for name, fn in (("lcg_hip_dense_lcg_multi", lib.lcg_hip_dense_lcg_multi), ("lcg_hip_dense_lpcg_multi", lib.lcg_hip_dense_lpcg_multi)):
                 B = DC.columns(S, k)
                 cases(f"{name} normal={int(shape[2])} {shape[0]}x{shape[1]}", fn, D.h, (int(shape[2]),), S["n"], k, False, B, np.zeros_like(B), S["xt"], S["b"])
+        m, n = shape[0], shape[1]
+        tag = f"{m}x{n}"
+        for v in variants(f"lcg_hip_dense_set_kernel {tag}", D):
+            for k in DC.KS:
+                Xn, Xm, U, Yn, Ym = block(n, k, 17 * n + k), block(m, k, 19 * m + k), block(n, k, 23 * n + k), block(n, k, 1), block(m, k, 1)
+                product(f"lcg_hip_dense_matmat {tag}", f"variant {v} K.X", lib.lcg_hip_dense_matmat, D.h, k, (Xn, Ym, 0), Ym, last=D.h)
+                product(f"lcg_hip_dense_matmat {tag}", f"variant {v} K^T.X", lib.lcg_hip_dense_matmat, D.h, k, (Xm, Yn, 1), Yn, last=D.h)
+                product(f"lcg_hip_dense_ata_multi {tag}", f"variant {v}", lib.lcg_hip_dense_ata_multi, D.h, k, (Xn, Yn), Yn, last=D.h)
+                for normal in (1, 0) if m == n else (1,):
+                    product(f"lcg_hip_dense_op_multi_dot {tag}", f"variant {v} normal={normal}", lib.lcg_hip_dense_op_multi_dot, D.h, k,
+                            (normal, Xn, Yn, U), Yn, k, last=D.h)
+        D.destroy()
+
+    # ---- complex dense -------------------------------------------------------------------------------------------------------------------
+    for n in ZD.SIZES:
+        S = ZD.system(n)
+        D = api.DenseMatrix.from_array(S["K"])
+        D.build_jacobi(False)
+        tag = f"{n}x{n}"
+        for v in variants(f"lcg_hip_dense_set_kernel complex {tag}", D):
+            for k in ZD.KS:
+                X, U, Y = block(n, k, 29 * n + k, True), block(n, k, 31 * n + k, True), block(n, k, 1, True)
+                for layout in (0, 1):
+                    for conj in (0, 1):
+                        product(f"clcg_hip_dense_matmat {tag}", f"variant {v} layout={layout} conjugate={conj}", lib.clcg_hip_dense_matmat, D.h, k,
+                                (X, Y, layout, conj), Y, last=D.h)
+                product(f"clcg_hip_dense_op_multi_dot {tag}", f"variant {v}", lib.clcg_hip_dense_op_multi_dot, D.h, k, (X, Y, U), Y, 2 * k, last=D.h)
+                B = ZD.columns(S, k)
+                for name, fn in (("clcg_hip_dense_lbicg_sym_multi", lib.clcg_hip_dense_lbicg_sym_multi), ("clcg_hip_dense_lpcg_multi", lib.clcg_hip_dense_lpcg_multi)):
+                    cases(f"{name} variant {v} {tag}", fn, D.h, (), n, k, True, B, np.zeros_like(B), S["xt"], S["b"])
         D.destroy()
 
     # ---- the refusals: code and text -----------------------------------------------------------------------------------------------------------
@@ -217,6 +293,48 @@ def main():
                 torch.cuda.synchronize()
                 say(f"refusals ({state}) {name}", f"refusal ({state}) {name} {what}: {rc}: {err()}")
 
+    def product_refusals():
+        """The product entries: every fault alone and two at once (which of the two is named says where the checks stand)."""
+        dots = (C.c_double * 16)()
+        px, py, pu = pm, pb, pm + 16 * n * 4          # X, Y in different tensors; U in X's tensor, behind a complex block of k = 4 columns
+        csr = [("lcg_hip_spmm", lib.lcg_hip_spmm, A, Ac, False, 0), ("lcg_hip_spmm_dot", lib.lcg_hip_spmm_dot, A, Ac, False, 1),
+               ("lcg_hip_spmm_dot2", lib.lcg_hip_spmm_dot2, A, Ac, False, 1), ("clcg_hip_spmm", lib.clcg_hip_spmm, Ac, A, True, 0),
+               ("clcg_hip_spmm_dot", lib.clcg_hip_spmm_dot, Ac, A, True, 1)]
+        for name, fn, good, other, cplx, dotted in csr:
+            for what, kw in (("k=3", dict(kk=3)), ("X misaligned", dict(x=px + 8)), ("Y null", dict(y=None)), ("no handle", dict(h=None)),
+                             ("other type's handle", dict(h=other.h)), ("dense handle", dict(h=D.h)), ("null dots", dict(d=None)),
+                             ("other type's handle and null dots", dict(h=other.h, d=None)), ("no handle and null dots", dict(h=None, d=None)),
+                             ("k=3 and null dots", dict(kk=3, d=None)), ("U misaligned and other type's handle", dict(u=pu + 8, h=other.h)),
+                             ("as it is", {})):
+                a = dict(h=good.h, kk=k, x=px, y=py, u=pu, d=dots)
+                a.update(kw)
+                rc = fn(a["h"], a["kk"], a["x"], a["y"], *((a["u"], a["d"]) if dotted else ()))
+                torch.cuda.synchronize()
+                say(f"refusals products {name}", f"refusal {name} {what}: {rc}: {err()}")
+        dense = [("lcg_hip_dense_matmat", lib.lcg_hip_dense_matmat, D, Dc, (0,), 0), ("lcg_hip_dense_ata_multi", lib.lcg_hip_dense_ata_multi, D, Dc, (), 0),
+                 ("lcg_hip_dense_op_multi_dot", lib.lcg_hip_dense_op_multi_dot, D, Dc, (1,), 1),
+                 ("clcg_hip_dense_matmat", lib.clcg_hip_dense_matmat, Dc, D, (0, 0), 0),
+                 ("clcg_hip_dense_op_multi_dot", lib.clcg_hip_dense_op_multi_dot, Dc, D, (), 1)]
+        for name, fn, good, other, extra, dotted in dense:
+            for what, kw in (("k=3", dict(kk=3)), ("X misaligned", dict(x=px + 8)), ("Y null", dict(y=None)), ("no handle", dict(h=None)),
+                             ("other type's handle", dict(h=other.h)), ("CSR handle", dict(h=A.h)), ("X and Y overlap", dict(y=px + 16)),
+                             ("X misaligned and X and Y overlap", dict(x=px + 8, y=px + 16)), ("other type's handle and X and Y overlap", dict(h=other.h, y=px + 16)),
+                             ("bad flag", dict(extra=tuple(7 for _ in extra))), ("bad flag and X and Y overlap", dict(extra=tuple(7 for _ in extra), y=px + 16)),
+                             ("not square", dict(h=Dr.h)), ("dots without U", dict(u=None)), ("Y overlaps U and dots without U", dict(u=None, y=px + 16)),
+                             ("other type's handle and null dots", dict(h=other.h, d=None)), ("as it is", {})):
+                a = dict(h=good.h, kk=k, x=px, y=py, u=pu, d=dots, extra=extra)
+                a.update(kw)
+                if name.startswith("lcg_hip_dense_op"):
+                    args = (a["h"], a["kk"], *a["extra"], a["x"], a["y"], a["u"], a["d"])
+                elif dotted:
+                    args = (a["h"], a["kk"], a["x"], a["y"], a["u"], a["d"])
+                else:
+                    args = (a["h"], a["kk"], a["x"], a["y"], *a["extra"])
+                rc = fn(*args)
+                torch.cuda.synchronize()
+                say(f"refusals products {name}", f"refusal {name} {what}: {rc}: {err()}")
+
+    product_refusals()
     refusals("nothing built")
     A.build_jacobi(); Ac.build_jacobi(); D.build_jacobi(True)
     refusals("Jacobi built, the dense one for K^T.K")

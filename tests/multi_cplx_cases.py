@@ -2,7 +2,7 @@
 tests/test_gpu_multi_cplx_solvers.py, tests/test_gpu_multi_cplx_product.py and tests/test_multi_cplx_cases_cpu.py, which shows with
 the oracle alone that the cases are what they claim.  Modelled on tests/multi_cases.py; a helper of the tests, not a conftest.
 
-Systems, all complex-symmetric and non-Hermitian, by the class of crows_per_block (csr_multi_cplx.hip: mean row length <= 48 -> R = 64
+Systems, all complex-symmetric and non-Hermitian, by the class of rows_per_block (csr_multi.hip, the frame both products share: mean row length <= 48 -> R = 64
 rows per block, <= 256 -> 16, more -> 4):
   * "helm", nx: the nx x nx five-point Laplacian plus a diagonal 0.05 + 0.3i (0.2 + u), u uniform from a fixed seed; b = A.xt.
     helm 40 is the issue's helm40 (n = 1600); helm 182 (n = 33124) has 518 row blocks of 64 (the folded d.Ad) and rows beyond
@@ -14,7 +14,7 @@ rows per block, <= 256 -> 16, more -> 4):
     (R = 4, 66 row blocks, the last of one row);
   * "case1kc": tests/golden/case_1K_cA, 1.2 entries per row; the oracle needs 310-514 iterations: capped runs only.
 Each system carries its mean row length, its class R and its block count ceil(n / R); more than MM_MG = 512 blocks: d.Ad goes
-through k_cmm_fold.
+through k_mm_fold.
 
 Columns: b = A.xt (|m|^2 ends well above 1), 1e-2 b (|m|^2 stays below 1: the clamp decides; 1e-6 b would be "already optimised" under
 BiCG-sym's 4th-power rule), a seeded random complex vector, a
@@ -38,7 +38,7 @@ CMM_W = 1536                        # multi_cplx.hpp: entries per LDS window of 
 SMALL = 1e-2                        # the scale of the column whose |m|^2 stays below 1
 TREE_CAP = 32 * MM_MG               # multi.hpp: tree_leaves' cap for complex blocks -- rows beyond it are a thread's second piece
 
-rows_per_block = mc.rows_per_block  # csr_multi_cplx.hpp: crows_per_block has csr_multi.hip's classes
+rows_per_block = mc.rows_per_block  # the complex product runs under csr_multi.hip's frame: the same classes
 
 
 # ---------------------------------------------------------------------------------------------------------------- systems

@@ -59,7 +59,7 @@ def _random_rows(rng, n, ncols, lens):
     return rp, col
 
 
-# the class of crows_per_block each window shape is there for (the product sets no kernel name: the mean row length is the statement)
+# the class of rows_per_block (csr_multi.hip) each window shape is there for (the product sets no kernel name: the mean row length is the statement)
 WINDOW_CLASS = {"win_exact": 64, "win_plus1": 64, "win_minus1": 64, "win_row_end_1": 64, "win_row_end_2": 64, "win_row_end_3": 64,
                 "three_windows": 16, "three_windows_r64": 64, "one_row": 4, "r4_partial": 4, "r16_partial": 16}
 
@@ -119,7 +119,7 @@ def _fold_shape(kind, n, R):
     return S["n"], S["n"], S["rp"], S["ci"]
 
 
-# more than MM_MG row blocks: the dots go through k_cmm_fold, at every class
+# more than MM_MG row blocks: the dots go through k_mm_fold, at every class
 MANY_BLOCKS = {"fold_r64": lambda: _fold_shape("helm", 182, 64), "fold_r16": lambda: _fold_shape("band30", 8197, 16),
                "fold_r4": lambda: _fold_shape("band140", 2051, 4)}
 
