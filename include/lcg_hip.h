@@ -319,6 +319,30 @@ int lcg_hip_csr_set_run_stretches(lcg_hip_csr_t A, int mode);
 /* Stretches the packed kernel runs from (0 before the first product built them, when switched off or when there are none);
  * *blocks_out (may be NULL) = the blocks they cover. */
 int64_t lcg_hip_csr_run_stretches(lcg_hip_csr_t A, int64_t *blocks_out);
+/* SYMMETRIC run stretches: a stretch whose row length is 2p + 1 with the diagonal in slot p, whose offsets column - row are
+ * antisymmetric and whose values mirror each other BIT FOR BIT (val(i, k) == val(i + off[k], 2p - k): +-0, a NaN's payload or one ulp
+ * refuse it) keeps a HALF STORE beside the CSR arrays: per block of 64 rows one tile of its diagonal and p upper diagonals, (p + 1) x 512
+ * bytes, laid out in the order the product's workgroups are dispatched.  The blocks of the stretch's inner range (the stretch minus
+ * the ceil(largest offset / 64) + 1 blocks in front, from the next multiple of eight blocks on) are multiplied by k_spmv_ldsp_sym, which
+ * reads a lower entry as its partner row's upper entry: half the value stream from memory, bit-identical y and carried sums.  The
+ * longest qualifying stretch of a real fp64 matrix on one GPU is taken (not a sharded handle, not a transposed copy, not a row range).
+ * mode: -1 automatic, 0 off, 1 forced (any qualifying stretch whose inner range has as many blocks as slices); LCG_HIP_SYM_RUNS=-1/0/1
+ * overrides for the whole process.  The automatic mode (the default) takes such a stretch where the product streams >= 512 MB: 1619-1632
+ * against 1463-1551 CG iterations/s on the 10M-row, 33-diagonal system (profiles/sym_runs_ab.txt).  MEMORY: the half store is about half
+ * the value array again (1.33 GB for that system); the CSR arrays stay as they are; lcg_hip_csr_plan_info counts it.  Setting the mode frees the half store or has the plan built
+ * again at the next product.  The half store is a copy of VALUES (the rest of the packed form copies columns only): in the rewrite
+ * protocol below (lcg_hip_csr_set_binned) it goes, like the op(A) copies, with any of set_packed / set_tiled / set_binned / set_ranges (A, 0)
+ * and with set_sym_runs itself (a device synchronisation; the packed plan is built again at the next product, which checks the new
+ * values and builds the half store again -- or refuses them).  The offsets must ascend in storage order (sorted rows).  No reference counterpart. */
+int lcg_hip_csr_set_sym_runs(lcg_hip_csr_t A, int mode);
+/* Slices of the inner range: 1 (blocks in row order: the default, and what was measured fastest -- DESIGN 3.1), 2, 4 or 8 (workgroup w takes
+ * block (w % slices) * S + w / slices of it: with 8 a contiguous eighth of the rows per XCD, the tiles interleaved in dispatch order);
+ * 0 = the default, one.  LCG_HIP_SYM_NX=1/2/4/8 overrides for the whole process, as LCG_HIP_SYM_RUNS does the mode.  A change has the
+ * plan built again at the next product. */
+int lcg_hip_csr_set_sym_slices(lcg_hip_csr_t A, int slices);
+/* Slices of the symmetric stretch the product runs from (0: none); *blocks_out (may be NULL) = the blocks k_spmv_ldsp_sym multiplies,
+ * *status_out (may be NULL) = "taken", or why the latest plan refused ("refused: ..."), or "not tried" (a static string). */
+int64_t lcg_hip_csr_sym_runs(lcg_hip_csr_t A, int64_t *blocks_out, const char **status_out);
 /* Blocks of 64 rows the packed form stores as TEMPLATE blocks: every entry on one of <= 64 diagonals (the union of the rows'), rows of
  * <= 32 entries, and a 64-bit mask per row saying which diagonals the row has -- what a stencil's blocks look like where grid boundaries pass
  * through them.  Like run blocks they stream values only and are bit-identical to the plain row-block kernel.
@@ -336,7 +360,7 @@ int64_t lcg_hip_csr_packed_templates(lcg_hip_csr_t A);
  * LCG_HIP_BINNED=0/1 overrides for the whole process.  y differs from the row-block kernels' y in the last
  * bits (products are rounded before the add); on gfx950 it is bit-identical from call to call and from plan to plan
  * (lanes of one ds_add_f64 that meet in a row are serialised by the LDS in lane order: verified by test, not an ISA promise).
- * The packed, tiled and binned forms, the row ranges and the op(A) copies of lcg_hip_spmv_op / clcg_hip_csr_ax are COPIES of
+ * The packed, tiled and binned forms, the row ranges, a symmetric stretch's half store and the op(A) copies of lcg_hip_spmv_op / clcg_hip_csr_ax are COPIES of
  * the matrix made at their first use: a caller who rewrites the VALUES or COLUMNS of an adopted matrix (lcg_hip_csr_create with
  * adopt != 0; same row pointers, columns in range) afterwards drops them with set_packed / set_tiled / set_binned /
  * set_ranges(A, 0) -- any one of them frees the op(A) copies, each frees its own plan -- and re-arms the automatic choice with

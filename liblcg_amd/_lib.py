@@ -89,6 +89,9 @@ SIGNATURES = {
     "lcg_hip_csr_packed_runs": (C.c_int64, [vp, C.POINTER(C.c_int64)]),
     "lcg_hip_csr_set_run_stretches": (C.c_int, [vp, C.c_int]),
     "lcg_hip_csr_run_stretches": (C.c_int64, [vp, C.POINTER(C.c_int64)]),
+    "lcg_hip_csr_set_sym_runs": (C.c_int, [vp, C.c_int]),
+    "lcg_hip_csr_set_sym_slices": (C.c_int, [vp, C.c_int]),
+    "lcg_hip_csr_sym_runs": (C.c_int64, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_char_p)]),
     "lcg_hip_csr_packed_templates": (C.c_int64, [vp]),
     "lcg_hip_csr_set_binned": (C.c_int, [vp, C.c_int]),
     "lcg_hip_csr_set_tiled": (C.c_int, [vp, C.c_int]),

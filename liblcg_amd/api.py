@@ -168,6 +168,17 @@ class CsrMatrix:
     def set_kernel(self, variant: int):
         _chk(L.load().lcg_hip_csr_set_kernel(self.h, variant), "set_kernel")
 
+    def set_sym_runs(self, mode: int, slices: int = 0):
+        """Symmetric run stretches (lcg_hip_csr_set_sym_runs): mode -1 automatic, 0 off, 1 forced; slices 0 (the default: one), 1, 2, 4 or 8."""
+        _chk(L.load().lcg_hip_csr_set_sym_slices(self.h, slices), "set_sym_slices")
+        _chk(L.load().lcg_hip_csr_set_sym_runs(self.h, mode), "set_sym_runs")
+
+    def sym_runs(self):
+        """(slices in use or 0, blocks the symmetric kernel multiplies, status text) of the latest plan (lcg_hip_csr_sym_runs)."""
+        blocks, why = C.c_int64(0), C.c_char_p()
+        nx = L.load().lcg_hip_csr_sym_runs(self.h, C.byref(blocks), C.byref(why))
+        return int(nx), blocks.value, (why.value or b"").decode()
+
     def build_jacobi(self, diag_out=None):
         p = None if diag_out is None else _ptr(diag_out)[0]
         _chk(L.load().lcg_hip_csr_build_jacobi(self.h, p), "build_jacobi")

@@ -729,6 +729,8 @@ void dist_free(lcg_hip_csr *A)
     A->rem_rows = nullptr; A->rem_y = nullptr;
     if (A->xfull) hipFree(A->xfull);
     A->xfull = nullptr; A->distributed = false;
+    A->main.sym_whole = !A->is_complex && !A->c64;
+    sym_runs_reset(A->main);        // (a packed plan that stayed resident under the shard holds no half store: built again at the next product)
     // transposes made for the sharded product have the padded global height: not the unsharded matrix's
     for (int i = 1; i < 4; i++) free_part(A->op[i]);
     if (A->op_z) hipFree(A->op_z);
@@ -802,6 +804,7 @@ int dist_split(lcg_hip_csr *A, int64_t n_global, int nranks, int rank)
     HIPCHK(hipMemsetAsync(A->xfull, 0, sizeof(double) * (A->is_complex ? 2 : 1) * (size_t)(rpr * nranks), c.stream));
     HIPCHK(hipStreamSynchronize(c.stream));
     A->distributed = true;
+    A->main.sym_whole = false; sym_runs_free(A->main);     // (a shard multiplies with loc / rem: the whole matrix's half store is of no use any more)
     return 0;
 }
 

@@ -602,19 +602,7 @@ __global__ __launch_bounds__(64) void k_pk_stretch_fill(RunStretches rs, const i
 // NS > 8: the FIRST batch is predicated (slots past the row's end read entry 0 with a zero
 // coefficient), so rows of up to NS*T entries -- 33 entries on 4 lanes are 9 for one lane, 8 for the
 // others -- are done in one round without a serial tail (0.706 vs 0.722 ms on the headline system).
-// end of a block of k_spmv_ldsp<DOT>: the first wavefront holds the finished rows (vfin) and their u; one sum per block
-__device__ __forceinline__ void ldsp_dot_tail(const DotPlan &dp, int bid, int j0, double vfin, double uv)
-{
-    if (threadIdx.x >= 64) return;      // uniform per wavefront: the finished rows sit in wavefront 0 (all of it at 64 rows per block,
-    if (j0 != 0) vfin = 0.0;            // its first 32 / 16 lanes at 32 / 16 -- the other lanes add zeros)
-    const double a0 = wave_sum(vfin * uv);
-    if ((threadIdx.x & 63) == WSUM_LANE) dp.part[bid] = a0;
-    if (dp.yy) {                        // uniform
-        const double a1 = wave_sum(vfin * vfin);
-        if ((threadIdx.x & 63) == WSUM_LANE) dp.part[dp.stride + bid] = a1;
-    }
-}
-
+// (end of a block of k_spmv_ldsp<DOT>: ldsp_dot_tail, csr_plan.hpp)
 // DOT: the block also leaves its rows' share of y.u (and y.y) in dp.part[block] (dp.part[dp.stride + block]): the dot the
 // Krylov loops take right after the product, without a pass of its own over two 80 MB vectors (see k_spmv_lds1d; here one
 // partial per block of 64 rows, folded to <= 512 by k_axp_fold before the scalar step adds them up).
@@ -634,15 +622,21 @@ static int pk_window(int max_slice)
 // RR: rows per block.  64 (T = 4 lanes per row) for rows of up to ~34 entries; 32 / 16 (T = 8 / 16) for longer rows -- packed columns
 // only, the first batch predicated for ANY NS (round 3, late: 27-point stencils with 2 / 3 unknowns per point, 54 / 81 entries per row,
 // took the 12-byte k_spmv_lds1 before).
-template <bool PUSH, int NS, int BITS, bool DOT = false, int CHE = LdsCfg<double>::CH, int RR = PK_R>
+// SKIP: the grid leaves out the blocks [st.skip_from, st.skip_from + st.skip) -- the sliced range of a symmetric stretch, which
+// k_spmv_ldsp_sym multiplies (csr_sym.hip) -- so that ONE launch takes the blocks in front of it and behind it.  Instances of their
+// own: those without it are the code they were.
+struct RunStretchesSkip : RunStretches { int skip_from = 0, skip = 0; };
+template <bool PUSH, int NS, int BITS, bool DOT = false, int CHE = LdsCfg<double>::CH, int RR = PK_R, bool SKIP = false>
 __global__ __launch_bounds__(VB) void k_spmv_ldsp(int n, const int *__restrict__ rowptr, const v4i *__restrict__ packed,
                                                   const int *__restrict__ pofs, const int *__restrict__ pbase,
                                                   const double *__restrict__ val, const double *__restrict__ x,
-                                                  double *__restrict__ y, const int *done, PushPlan pp, DotPlan dp, RunStretches st)
+                                                  double *__restrict__ y, const int *done, PushPlan pp, DotPlan dp,
+                                                  typename std::conditional<SKIP, RunStretchesSkip, RunStretches>::type st)
 {
     if (PUSH && (int)blockIdx.x < pp.nblocks) { push_block(pp, blockIdx.x); return; }
     if (PUSH && pp.nrecv > 0 && (int)blockIdx.x >= (int)gridDim.x - pp.nrecv) { recv_block(pp, (int)blockIdx.x - ((int)gridDim.x - pp.nrecv)); return; }
-    const int bid = PUSH ? blockIdx.x - pp.nblocks : blockIdx.x;
+    int bid = PUSH ? blockIdx.x - pp.nblocks : blockIdx.x;
+    if constexpr (SKIP) { if (bid >= st.skip_from) bid += st.skip; }
     constexpr int R = RR;
     constexpr int T = VB / R;
     constexpr int UNR = NS;
@@ -1306,7 +1300,8 @@ static bool packed_build(const CsrPart &P, hipStream_t s, bool runs_only, int R 
     const int nb = (n + R - 1) / R;
     int *ngr = nullptr, *span = nullptr, *sflag = nullptr;
     std::vector<int> hflag;
-    const bool stretches = !runs_only && R == PK_R && run_stretches_on(P);      // (looked for only where they are switched on)
+    const bool sym = !runs_only && R == PK_R && sym_runs_wanted(P);      // (a symmetric stretch is a stretch: looked for whatever the stretches' switch says)
+    const bool stretches = !runs_only && R == PK_R && (run_stretches_on(P) || sym);      // (looked for only where they are switched on)
     long total = 0;
     int hspan[4] = {0, 0, 0, 0};
     int dof = 1;
@@ -1371,6 +1366,7 @@ static bool packed_build(const CsrPart &P, hipStream_t s, bool runs_only, int R 
     P.pk_dof = dof;
     P.pk_state = runs_only ? 2 : 1;
     if (!hflag.empty() && hspan[2] > 1) run_stretches_build(P, s, hflag);
+    if (sym) sym_runs_build(P, s);
     return true;
 }
 static bool packed_ready(const CsrPart &P, hipStream_t s, int R = PK_R) { return packed_build(P, s, false, R); }
@@ -1393,6 +1389,29 @@ static const char *ldsp_name(const CsrPart &P, bool dot)
                                          "k_spmv_ldsp (LDS-staged, template blocks + 21-bit packed columns)",
                                          "k_spmv_ldsp (LDS-staged, run blocks + template blocks + 21-bit packed columns)"}};
     return a[P.pk_bits == 18 ? 0 : 1][form];
+}
+
+// the same while the sliced range of a symmetric stretch goes to k_spmv_ldsp_sym (csr_sym.hip): the family's name first, as ever
+// (a symmetric stretch is made of run blocks: the forms with them only; static strings like ldsp_name's)
+static const char *sym_runs_name(const CsrPart &P, bool dot)
+{
+#define SYM_AROUND(s) " around k_spmv_ldsp_sym (symmetric run stretch: half store in dispatch order, " s ")"
+#define SYM_NAMES(base, tail) {base SYM_AROUND("one slice") tail, base SYM_AROUND("two slices") tail, base SYM_AROUND("four slices") tail, base SYM_AROUND("eight slices") tail}
+#define SYM_DOT " carrying the dot that follows the product"
+    const int nx = P.pk_sym.NX == 8 ? 3 : P.pk_sym.NX == 4 ? 2 : P.pk_sym.NX == 2 ? 1 : 0, tpl = P.pk_tpls > 0 ? 1 : 0;
+    if (dot) {
+        static const char *const d[2][4] = {SYM_NAMES("k_spmv_ldsp (LDS-staged, run blocks + packed columns)", SYM_DOT),
+                                            SYM_NAMES("k_spmv_ldsp (LDS-staged, run blocks + template blocks + packed columns)", SYM_DOT)};
+        return d[tpl][nx];
+    }
+    static const char *const a[2][2][4] = {{SYM_NAMES("k_spmv_ldsp (LDS-staged, run blocks + 18-bit packed columns)", ""),
+                                            SYM_NAMES("k_spmv_ldsp (LDS-staged, run blocks + template blocks + 18-bit packed columns)", "")},
+                                           {SYM_NAMES("k_spmv_ldsp (LDS-staged, run blocks + 21-bit packed columns)", ""),
+                                            SYM_NAMES("k_spmv_ldsp (LDS-staged, run blocks + template blocks + 21-bit packed columns)", "")}};
+#undef SYM_DOT
+#undef SYM_NAMES
+#undef SYM_AROUND
+    return a[P.pk_bits == 18 ? 0 : 1][tpl][nx];
 }
 
 // rows per block of the LDS-staged kernels so that R*mean_row entries fit one LDS window, and whether EVERY block's slice
@@ -1456,19 +1475,36 @@ template <bool PUSH, bool DOT, int RR = PK_R>
 static void ldsp_launch(const AxChoice &c, const CsrPart &P, const double *x, double *y, hipStream_t s, const int *done,
                         const PushPlan &pp, const DotPlan &dp)
 {
-    const unsigned g = (unsigned)((P.n_rows + RR - 1) / RR) + (PUSH ? (unsigned)(pp.nblocks + pp.nrecv) : 0u);
-    const auto go = [&](auto ns) {
-        pick<18, 21>(c.bits, [&](auto bits) {
-            pick<PK_CH_8, PK_CH_7, PK_CH_SMALL, LdsCfg<double>::CH>(c.win, [&](auto win) {
-                hipLaunchKernelGGL((k_spmv_ldsp<PUSH, decltype(ns)::value, decltype(bits)::value, DOT, decltype(win)::value, RR>), dim3(g),
-                                   dim3(VB), 0, s, P.n_rows, P.rowptr, static_cast<const v4i *>(P.pk_data), P.pk_ofs, P.pk_base, P.val,
-                                   x, y, done, pp, dp, run_stretches_on(P) ? P.pk_rs : RunStretches());
+    const unsigned nb = (unsigned)((P.n_rows + RR - 1) / RR);
+    // SKIP: the sliced range of a symmetric stretch goes to k_spmv_ldsp_sym (csr_sym.hip), every block in front of it and behind it to
+    // ONE launch of this kernel whose grid leaves the range out
+    const auto launch = [&](auto skip_tag, unsigned g, const auto &st) {
+        constexpr bool SKIP = decltype(skip_tag)::value;
+        const auto go = [&](auto ns) {
+            pick<18, 21>(c.bits, [&](auto bits) {
+                pick<PK_CH_8, PK_CH_7, PK_CH_SMALL, LdsCfg<double>::CH>(c.win, [&](auto win) {
+                    hipLaunchKernelGGL((k_spmv_ldsp<PUSH, decltype(ns)::value, decltype(bits)::value, DOT, decltype(win)::value, RR, SKIP>), dim3(g),
+                                       dim3(VB), 0, s, P.n_rows, P.rowptr, static_cast<const v4i *>(P.pk_data), P.pk_ofs, P.pk_base, P.val,
+                                       x, y, done, pp, dp, st);
+                });
             });
-        });
+        };
+        if constexpr (RR == PK_R) pick<6, 7, 8, 9, 10, 12>(c.ns, go);
+        else if constexpr (RR == 32) pick<7, 9>(c.ns, go);
+        else pick<6, 9>(c.ns, go);
     };
-    if constexpr (RR == PK_R) pick<6, 7, 8, 9, 10, 12>(c.ns, go);
-    else if constexpr (RR == 32) pick<7, 9>(c.ns, go);
-    else pick<6, 9>(c.ns, go);
+    const RunStretches rs = run_stretches_on(P) ? P.pk_rs : RunStretches();
+    if constexpr (!PUSH && RR == PK_R) {
+        if (sym_runs_in_use(P)) {
+            RunStretchesSkip st;
+            static_cast<RunStretches &>(st) = rs;
+            st.skip_from = P.pk_sym.inner0; st.skip = P.pk_sym.NX * P.pk_sym.S;
+            sym_runs_launch(P, DOT, x, y, s, done, dp);
+            launch(std::true_type{}, nb - (unsigned)st.skip, st);
+            return;
+        }
+    }
+    launch(std::false_type{}, nb + (PUSH ? (unsigned)(pp.nblocks + pp.nrecv) : 0u), rs);
 }
 
 // The kernel a part's A.x takes: DESIGN 3.6's rules in order, the first that holds decides.  `push`: a shard's pushing blocks ride
@@ -1589,7 +1625,7 @@ static int spmv_dispatch(const CsrPart &P, int variant, double mean_row, const V
         case Ax::ldsp:
             ldsp_launch<PUSH, false>(c, P, xd, yd, s, done, pp, DotPlan());
             HIPCHK(hipGetLastError());
-            P.last_kernel = ldsp_name(P, false);
+            P.last_kernel = sym_runs_in_use(P) ? sym_runs_name(P, false) : ldsp_name(P, false);
             return 0;
         case Ax::ldsp_long:
             if constexpr (!PUSH) {
@@ -1693,7 +1729,7 @@ static int part_dot_launch(const CsrPart &P, const AxChoice &c, const double *x,
         if (pp) ldsp_launch<true, true>(c, P, x, y, s, done, *pp, dp);
         else ldsp_launch<false, true>(c, P, x, y, s, done, PushPlan(), dp);
         HIPCHK(hipGetLastError());
-        P.last_kernel = ldsp_name(P, true);
+        P.last_kernel = (!pp && sym_runs_in_use(P)) ? sym_runs_name(P, true) : ldsp_name(P, true);
     } else
         return 0;
     if (nofold) { *nofold = nsum; *slots = 0; return 1; }
@@ -1778,8 +1814,27 @@ void free_part(CsrPart &P)
     if (P.pk_ofs) hipFree(P.pk_ofs);
     if (P.pk_data) hipFree(P.pk_data);
     run_stretches_free(P);
+    sym_runs_free(P);
     if (P.dot_part) hipFree(P.dot_part);
     P = CsrPart();
+}
+
+// A change of the symmetric stretch's switches: the half store goes, and a plan that would now be built differently is built again
+// at the next product (as lcg_hip_csr_set_run_stretches does).  Also where the part becomes eligible again (comm.hip: dist_free) and in the
+// rewrite protocol (op_copies_free below).
+void sym_runs_reset(CsrPart &P)
+{
+    ranges_free(P);
+    const bool want = sym_runs_wanted(P);
+    if (!P.pk_sym_H && !(want && P.pk_state == 1)) return;
+    if (ctx().inited) (void)hipDeviceSynchronize();
+    sym_runs_free(P);
+    if (want && P.pk_state == 1) {
+        hipFree(P.pk_base); hipFree(P.pk_ofs); hipFree(P.pk_data);
+        P.pk_base = P.pk_ofs = nullptr; P.pk_data = nullptr;
+        run_stretches_free(P);
+        P.pk_state = 0;
+    }
 }
 
 } // namespace lcgh
@@ -1799,6 +1854,7 @@ int lcg_hip_csr_create(lcg_hip_csr_t *out, int n_rows, int n_cols, int64_t nnz, 
     lcg_hip_csr *A = new lcg_hip_csr();
     A->n_rows = n_rows; A->n_cols = n_cols; A->is_complex = is_complex != 0;
     A->mean_row = (double)nnz / n_rows;
+    A->main.sym_whole = !A->is_complex;
     if (mem == LCG_HIP_MEM_DEVICE && adopt) {
         A->main.n_rows = n_rows; A->main.nnz = nnz; A->main.owned = false; A->main.padded = adopt == 2;
         A->main.n_cols = n_cols;
@@ -1859,9 +1915,12 @@ int lcg_hip_csr_set_kernel(lcg_hip_csr_t A, int variant)
 } // extern "C"
 
 // set_*(A, 0) is the first half of the rewrite protocol (lcg_hip.h): the transposed / conjugated copies (op_part) are made from the
-// arrays too, so they go with the plans and are rebuilt from the new arrays at their next use
+// arrays too, so they go with the plans and are rebuilt from the new arrays at their next use.  So is the half store of a symmetric
+// run stretch (csr_sym.hip), the one copy of VALUES the packed form keeps: it goes with ANY of the setters, and the plan it belongs
+// to is built -- and its values compared -- again at the next product.
 static void op_copies_free(lcg_hip_csr *A)
 {
+    if (A->main.pk_sym_H || std::strncmp(A->main.sym_why, "refused", 7) == 0) sym_runs_reset(A->main);      // (refused values may mirror each other now)
     if (!A->op[1].rowptr && !A->op[2].rowptr && !A->op[3].rowptr) return;
     if (ctx().inited) (void)hipDeviceSynchronize();
     for (int i = 1; i < 4; i++) free_part(A->op[i]);
@@ -1883,6 +1942,7 @@ int lcg_hip_csr_set_packed(lcg_hip_csr_t A, int mode)
             hipFree(P->pk_base); hipFree(P->pk_ofs); hipFree(P->pk_data);
             P->pk_base = P->pk_ofs = nullptr; P->pk_data = nullptr;
             run_stretches_free(*P);
+            sym_runs_free(*P);
         }
         if (P->pk_state < 0 || mode == 0) P->pk_state = 0;     // decide again at the next product
     }
@@ -2003,6 +2063,40 @@ int64_t lcg_hip_csr_run_stretches(lcg_hip_csr_t A, int64_t *blocks_out)
     return P.pk_rs.n;
 }
 
+int lcg_hip_csr_set_sym_runs(lcg_hip_csr_t A, int mode)
+{
+    NOT_DENSE(A, LCG_HIP_E_ARG);
+    if (!A || mode < -1 || mode > 1) return LCG_HIP_E_ARG;
+    TRY_C64(A, "lcg_hip_csr_set_sym_runs");
+    A->main.sym_mode = mode;
+    sym_runs_reset(A->main);
+    return 0;
+}
+
+int lcg_hip_csr_set_sym_slices(lcg_hip_csr_t A, int slices)
+{
+    NOT_DENSE(A, LCG_HIP_E_ARG);
+    if (!A || (slices != 0 && slices != 1 && slices != 2 && slices != 4 && slices != 8)) return LCG_HIP_E_ARG;
+    TRY_C64(A, "lcg_hip_csr_set_sym_slices");
+    if (A->main.sym_nx == slices) return 0;
+    A->main.sym_nx = slices;
+    sym_runs_reset(A->main);
+    return 0;
+}
+
+int64_t lcg_hip_csr_sym_runs(lcg_hip_csr_t A, int64_t *blocks_out, const char **status_out)
+{
+    NOT_DENSE(A, LCG_HIP_E_ARG);
+    if (blocks_out) *blocks_out = 0;
+    if (status_out) *status_out = "";
+    if (!A) return 0;
+    const CsrPart &P = A->distributed ? A->loc : A->main;
+    if (status_out) *status_out = P.sym_why;
+    if (!sym_runs_in_use(P)) return 0;
+    if (blocks_out) *blocks_out = (int64_t)P.pk_sym.NX * P.pk_sym.S;
+    return P.pk_sym.NX;
+}
+
 static int64_t part_traffic_model(const CsrPart &P)
 {
     const char *k = P.last_kernel;
@@ -2025,6 +2119,13 @@ static int64_t part_traffic_model(const CsrPart &P)
         if (stretches_in_use(P)) {          // their blocks read no row pointers, no two words, no columns of their own: one table per stretch instead
             b -= (4 * PK_R + 8) * (int64_t)P.pk_rs_blocks + 16 * (int64_t)P.pk_rs_groups;
             for (int i = 0; i < P.pk_rs.n; i++) b += 16 * P.pk_rs.s[i].Q;
+        }
+        if (std::strstr(k, "k_spmv_ldsp_sym") && sym_runs_in_use(P) && !stretches_in_use(P)) {     // (stretches in use: the sliced range is part of one, taken off above)
+            // the sliced range of a symmetric stretch (csr_sym.hip): as in any stretch, no plan of its own.  Its VALUES stay counted in
+            // full: this models what enters the L2s, and a lower entry still does -- as its partner's upper entry, from whichever cache
+            // holds it.  What the half store halves is the HBM side, which the counters behind this model cannot tell apart.
+            const int64_t sb = (int64_t)P.pk_sym.NX * P.pk_sym.S, p = P.pk_sym.p;
+            b -= ((4 * PK_R + 8) + 16 * ((2 * p + 1 + 1 + 3) / 4)) * sb - 16 * P.pk_sym.TQ;
         }
         return b;
     }
@@ -2060,6 +2161,7 @@ int lcg_hip_csr_plan_info(lcg_hip_csr_t A, double *build_ms, int64_t *extra_byte
     auto add = [&](const CsrPart &Q) {
         if (Q.pk_state > 0) b += 16 * ((int64_t)Q.pk_groups + 4) + 8 * (((int64_t)Q.n_rows + Q.pk_R - 1) / Q.pk_R + 1);
         for (int i = 0; i < Q.pk_rs.n; i++) b += 16 * Q.pk_rs.s[i].Q;      // the stretches' tables
+        b += sym_runs_bytes(Q);                                             // a symmetric stretch's half store
         if (Q.bn_plan) b += (int64_t)binned_plan_bytes(Q);
         if (Q.tl_plan) b += (int64_t)tiled_plan_bytes(Q);
     };

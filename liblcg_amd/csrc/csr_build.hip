@@ -535,6 +535,7 @@ int lcg_hip_csr_from_coo(lcg_hip_csr_t *out, int n, int64_t nnz, const int *row,
     const size_t vw = is_complex ? 2 : 1;
     lcg_hip_csr *A = new lcg_hip_csr();
     A->n_rows = n; A->n_cols = n; A->is_complex = is_complex != 0; A->mean_row = (double)nnz / n;
+    A->main.sym_whole = !A->is_complex;
     rc = alloc_part(A->main, n, nnz, A->is_complex);
     if (rc) { delete A; return rc; }
     A->main.n_cols = n;
@@ -702,6 +703,7 @@ int lcg_hip_csr_generate_ex(lcg_hip_csr_t *out, int64_t n, int npairs, int patte
     hipLaunchKernelGGL(k_gen_count, dim3(gb), dim3(VB), 0, c.stream, g, (long)r0, (long)r1, counts);
     lcg_hip_csr *A = new lcg_hip_csr();
     A->n_rows = nloc; A->n_cols = (int)n; A->is_complex = false;
+    A->main.sym_whole = true;
     rc = finish_generated(A, nloc, r0, counts, c.stream, [&](const int *rp, int *col, double *val) {
         hipLaunchKernelGGL(k_gen_fill, dim3(gb), dim3(VB), 0, c.stream, g, (long)r0, (long)r1, rp, col, val);
     });
@@ -733,6 +735,7 @@ int lcg_hip_csr_laplace2d(lcg_hip_csr_t *out, int nx, int ny, int64_t r0, int64_
     hipLaunchKernelGGL(k_lap_count, dim3(gb), dim3(VB), 0, c.stream, nx, ny, (long)r0, (long)r1, counts);
     lcg_hip_csr *A = new lcg_hip_csr();
     A->n_rows = nloc; A->n_cols = (int)n; A->is_complex = false;
+    A->main.sym_whole = true;
     rc = finish_generated(A, nloc, r0, counts, c.stream, [&](const int *rp, int *col, double *val) {
         hipLaunchKernelGGL(k_lap_fill, dim3(gb), dim3(VB), 0, c.stream, nx, ny, (long)r0, (long)r1, rp, col, val);
     });

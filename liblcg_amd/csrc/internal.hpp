@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "lcg_hip.h"
+#include "csr_sym.hpp"
 
 namespace lcgh {
 
@@ -279,6 +280,14 @@ struct CsrPart {
     mutable RunStretches pk_rs;                             // the (up to four) longest stretches of run blocks, found with the packed form
     mutable int *pk_rs_off = nullptr;                       // their offset tables
     mutable long pk_rs_blocks = 0, pk_rs_groups = 0;        // blocks they cover; 16-byte groups of per-block columns those blocks no longer read
+    // symmetric run stretch (csr_sym.hip): the longest stretch whose values mirror each other bit for bit reads a half store
+    mutable int sym_mode = -1;                              // -1 automatic (what the automatic mode takes), 0 off, 1 forced
+    mutable int sym_nx = 0;                                 // slices of the sliced range: 0 the process's default, 1, 2, 4, 8
+    bool sym_whole = false;                                 // the main part of a real fp64 handle while it is not sharded (set where the handle is made, cleared by lcg_hip_csr_distribute): no shard, no op(A) copy, no range
+    mutable SymRun pk_sym;                                  // NX = 0: none
+    mutable double *pk_sym_H = nullptr;                     // the half store
+    mutable long pk_sym_tiles = 0;                          // its tiles
+    mutable const char *sym_why = "not tried";              // why the stretch is (not) taken
     mutable double *dot_part = nullptr;                     // [2][dot_cap]: per-block (per-chunk) sums of a product that carries its dot (k_spmv_ldsp<DOT>, k_tile_spmv2<DOT>)
     mutable long dot_cap = 0;
     // two-pass "binned" product for scattered columns (csr_binned.hip), plan built on first use
@@ -367,6 +376,8 @@ int spmv_launch(const CsrPart &P, bool is_complex, int variant, double mean_row,
 // the same product with `pp.nblocks` pushing blocks in front of the grid (comm.hip, dist mode 2)
 int spmv_launch_push(const CsrPart &P, bool is_complex, int variant, double mean_row, const double *x, double *y,
                      hipStream_t s, const int *done_flag, const PushPlan &pp);
+void sym_runs_reset(CsrPart &P);            // csr.hip: the half store goes and, where the part's mode wants one, its packed plan is built again at the next product
+void sym_runs_free(const CsrPart &P);       // csr_sym.hip: the half store of a part's symmetric run stretch goes (the part's stream work must have ended)
 int jacobi_launch(const lcg_hip_csr *A, const double *x, double *z, int n, hipStream_t s);       // csr_build.hip
 // y = A.x with the sums y.u (and y.y) riding in the product: 1 = done, *slots partial sums wait in part[0 .. *slots) (and
 // part[AXP_CAP ..)); 0 = this matrix / kernel family cannot (nothing was launched: the caller multiplies and reduces as before); < 0 failure
