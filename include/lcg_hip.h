@@ -783,6 +783,44 @@ int clcg_hip_lpcg_multi(lcg_hip_csr_t A, int k, double *M, const double *B, cons
  * chosen at the first product of each form, whose transposed / conjugated copy is built then on the device
  * (lcg_hip_csr_last_kernel names them).  Later calls neither allocate nor synchronise. */
 int lcg_hip_spmv_c64(lcg_hip_csr_t A, const float *x, float *y, int layout, int conjugate);
+/* Y = A.X for k = 2, 4 or 8 COMPLEX64 vectors in ONE launch against a complex64 CSR handle (lcg_hip_csr_create_c64): col / val (12
+ * bytes per entry) are read once for all of them; the batched form of lcg_hip_spmv_c64, summed in fp32 as cuSPARSE's CUDA_C_32F
+ * (clcg_cudaf.cu's Afp, :254-401, :403-558).  A block of k complex64 vectors is one array of rows x k interleaved (re, im) float
+ * pairs, row-major: column j of row i is floats 2 (i k + j) and 2 (i k + j) + 1 (X: n_cols rows, Y: n_rows), its base 16-byte
+ * aligned; other counts are padded with zero columns.  Any other k, a null pointer or a misaligned base: LCG_HIP_E_ARG before the
+ * device or the handle is looked at.  Complex64 CSR handles on one GPU: real, complex128, dense and sharded handles return
+ * LCG_HIP_E_ARG (lcg_hip_last_error() says why), Y untouched; clcg_hip_spmm serves the complex128 ones.  Per entry acc = a x + acc
+ * in fp32 in lcg_hip_spmv_c64's fma order; column j's sums are added in an order fixed by the matrix alone: the same bits whatever
+ * the other columns hold (NaN and Inf included), whatever k is, wherever the column stands, from call to call.  Reads the plain
+ * CSR arrays: no single-vector plan is built or used. */
+int clcg_hip_spmm_c64(lcg_hip_csr_t A, int k, const float *X, float *Y);
+/* The same product carrying, per column, the sum the batched complex64 loops take right after it (d.Ad): dots[2 j], dots[2 j + 1] =
+ * re, im of the UNCONJUGATED sum over i of (A.X)_ij U_ij (cublasCdotu), j < k -- exact fp64 products of the fp32 values, summed in
+ * fp64 (2k doubles on the host, after a stream synchronise).  The sums ride in the product's epilogue as per-workgroup partial
+ * sums added in a fixed order: column j's sum depends on A, X_j and U_j alone, bit for bit. */
+int clcg_hip_spmm_dot_c64(lcg_hip_csr_t A, int k, const float *X, float *Y, const float *U, double *dots);
+/* Batched BiCG for complex-symmetric A (clbicg_symmetric, clcg_cudaf.cu:254-401) and PCG with the handle's reciprocal Jacobi
+ * diagonal (clpcg, clcg_cudaf.cu:403-558; needs lcg_hip_csr_build_jacobi(A)) over k = 2, 4 or 8 right-hand sides against one
+ * square complex64 CSR matrix on one GPU: M (in/out) and B are blocks of k complex64 vectors in clcg_hip_spmm_c64's layout and live
+ * where `mem` says.  Each column runs clcg_hip_solver_c64's / clcg_hip_solver_preconditioned_c64's recurrence as if it were alone
+ * -- fp32 vectors and scalars, every dot and norm an fp64 sum of exact products rounded to fp32 once, its own ak, bk and rho,
+ * unconjugated inner products, its own stop test, "already optimised" test, count and code -- while one multi-vector product per
+ * iteration reads the matrix once for all of them.  Three launches per iteration:
+ *     A.d carrying d.Ad | [ak] m += ak d; r -= ak Ad (PCG: s = inv .* r) + sums | [close] d = r + bk d (PCG: s + bk d)
+ * Stop rule of both: |r|^2 / max(|m|, 1)^2 in fp32, or |r| / n with abs_diff ("already optimised" then tests |r| / n only); a
+ * column ends with CLCG_NAN_VALUE at the first iteration whose sum |m|^2 or |r|^2 is NaN.  A column that has stopped is final: its
+ * elements of M, r, d and s are not stored to again.  ret, iterations, residual: host arrays of k (or NULL) receiving each column's
+ * code (CLCG_CONVERGENCE, LCG_REACHED_MAX_ITERATIONS (-1019, as the complex loops return at the cap), CLCG_ALREADY_OPTIMIZIED,
+ * CLCG_NAN_VALUE), iteration count and residual; lcg_hip_last_iterations / _residual report the column that ran longest.  Returns 0
+ * when the loop ran, whatever the columns' verdicts; LCG_HIP_E_ARG (k, null or misaligned M / B, a real / complex128 / dense /
+ * sharded / non-square handle; before the device is touched), CLCG_INVILAD_MAX_ITERATIONS, CLCG_INVILAD_EPSILON,
+ * LCG_NULL_PRECONDITION_MATRIX (PCG without a Jacobi diagonal), or a runtime failure.  No progress callback, no caller workspaces;
+ * column j's iterate, count, residual and code depend on A, its diagonal, column j of B and M and param alone, bit for bit:
+ * whatever the other columns hold, whatever k is, from call to call. */
+int clcg_hip_lbicg_sym_multi_c64(lcg_hip_csr_t A, int k, float *M, const float *B, const clcg_para *param,
+                                 int *ret, int *iterations, double *residual, int mem);
+int clcg_hip_lpcg_multi_c64(lcg_hip_csr_t A, int k, float *M, const float *B, const clcg_para *param,
+                            int *ret, int *iterations, double *residual, int mem);
 int lcg_hip_dot(int n, const double *a, const double *b, double *result);      /* lcg_dot, algebra.cpp:154-163; cublasDdot lcg_cuda.cu:187 */
 int lcg_hip_nrm2(int n, const double *a, double *result);                      /* cublasDznrm2-style 2-norm */
 int lcg_hip_axpy(int n, double alpha, const double *x, double *y);             /* y += alpha*x, cublasDaxpy lcg_cuda.cu:190 */

@@ -172,7 +172,11 @@ SIGNATURES = {
     "clcg_hip_spmm_dot": (C.c_int, [vp, C.c_int, vp, vp, vp, c_double_p]),
     "clcg_hip_lbicg_sym_multi": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(ClcgPara), c_int_p, c_int_p, c_double_p, C.c_int]),
     "clcg_hip_lpcg_multi": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(ClcgPara), c_int_p, c_int_p, c_double_p, C.c_int]),
-    "lcg_hip_ic0_solve_multi": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
+    "clcg_hip_spmm_c64": (C.c_int, [vp, C.c_int, vp, vp]),
+    "clcg_hip_spmm_dot_c64": (C.c_int, [vp, C.c_int, vp, vp, vp, c_double_p]),
+    "clcg_hip_lbicg_sym_multi_c64": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(ClcgPara), c_int_p, c_int_p, c_double_p, C.c_int]),
+    "clcg_hip_lpcg_multi_c64": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(ClcgPara), c_int_p, c_int_p, c_double_p, C.c_int]),
+    "lcg_hip_ic0_solve_multi":(C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
     "lcg_hip_ilu0_solve_multi": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
     "lcg_hip_dot": (C.c_int, [C.c_int, vp, vp, c_double_p]),
     "lcg_hip_nrm2": (C.c_int, [C.c_int, vp, c_double_p]),

@@ -317,6 +317,20 @@ class CsrMatrix:
         _chk(L.load().clcg_hip_spmm_dot(self.h, k, _ptr(X)[0], _ptr(Y)[0], _ptr(U)[0], out), "cspmm_dot")
         return np.array(out[:], dtype=np.float64).view(np.complex128)
 
+    def cspmm_c64(self, X, Y):
+        """Y = A.X for the k = 2, 4 or 8 complex64 columns of X in one launch (clcg_hip_spmm_c64): X (n_cols, k) and Y (n_rows, k) are
+        C-contiguous complex64 CUDA tensors, 16-byte aligned.  Complex64 matrices (from_csr_c64) on one GPU."""
+        k = _block_k(X, Y, cplx="c64")
+        _chk(L.load().clcg_hip_spmm_c64(self.h, k, _ptr(X)[0], _ptr(Y)[0]), "cspmm_c64")
+
+    def cspmm_dot_c64(self, X, Y, U):
+        """cspmm_c64 carrying one unconjugated sum per column (clcg_hip_spmm_dot_c64): returns a complex128 array of k,
+        [j] = sum_i Y_ij U_ij in fp64 -- what the batched complex64 loops take after their product.  X, Y, U as cspmm_c64's blocks."""
+        k = _block_k(X, Y, U, cplx="c64")
+        out = (C.c_double * (2 * k))()
+        _chk(L.load().clcg_hip_spmm_dot_c64(self.h, k, _ptr(X)[0], _ptr(Y)[0], _ptr(U)[0], out), "cspmm_dot_c64")
+        return np.array(out[:], dtype=np.float64).view(np.complex128)
+
     def distribute(self, n_global: int, mode: int = 0):
         _chk(L.load().lcg_hip_csr_distribute(self.h, n_global, mode), "csr_distribute")
 
@@ -548,17 +562,18 @@ def lcg(Afp, Pfp, m, B, n_size, param, instance, Gk=None, Dk=None, ADk=None) -> 
 
 
 def _block_k(*blocks, cplx=False):
-    """k of 2-D (n, k) C-contiguous float64 (cplx: complex128) blocks of vectors (numpy arrays or torch tensors), all alike."""
+    """k of 2-D (n, k) C-contiguous float64 (cplx: complex128; cplx="c64": complex64) blocks of vectors (numpy arrays or torch
+    tensors), all alike."""
+    name = "complex64" if cplx == "c64" else ("complex128" if cplx else "float64")
     k = None
     for X in blocks:
         if isinstance(X, np.ndarray):
-            ok = X.ndim == 2 and X.dtype == (np.complex128 if cplx else np.float64) and X.flags["C_CONTIGUOUS"]
+            ok = X.ndim == 2 and X.dtype == np.dtype(name) and X.flags["C_CONTIGUOUS"]
         else:
             import torch
-            ok = (isinstance(X, torch.Tensor) and X.dim() == 2 and X.dtype == (torch.complex128 if cplx else torch.float64)
-                  and X.is_contiguous())
+            ok = isinstance(X, torch.Tensor) and X.dim() == 2 and X.dtype == getattr(torch, name) and X.is_contiguous()
         if not ok:
-            raise ValueError(f"a block of vectors is a 2-D (n, k) C-contiguous {'complex128' if cplx else 'float64'} array or tensor")
+            raise ValueError(f"a block of vectors is a 2-D (n, k) C-contiguous {name} array or tensor")
         if k is not None and X.shape[1] != k:
             raise ValueError("blocks of vectors with different k")
         k = int(X.shape[1])
@@ -635,6 +650,20 @@ def clpcg_multi(A, M, B, param) -> list:
     """Batched complex PCG with the handle's Jacobi diagonal (clcg_hip_lpcg_multi; A.build_jacobi() first).  A column whose sums
     turn NaN stops with CLCG_NAN_VALUE (the single-vector loop runs to the cap).  As clbicg_sym_multi."""
     return _multi("clcg_hip_lpcg_multi", A, M, B, param, cplx=True)
+
+
+def clbicg_sym_multi_c64(A, M, B, param) -> list:
+    """Batched BiCG for a complex-symmetric complex64 matrix (clcg_hip_lbicg_sym_multi_c64; CsrMatrix.from_csr_c64): M (in/out) and
+    B are (n, k) complex64 blocks of k = 2, 4 or 8 columns, every column solved as clcg_solver_c64(CLCG_BICG_SYM) would solve it
+    alone while the matrix is read once per iteration for all of them.  param: a ClcgPara (or None).  Returns one SolveInfo per
+    column."""
+    return _multi("clcg_hip_lbicg_sym_multi_c64", A, M, B, param, cplx="c64")
+
+
+def clpcg_multi_c64(A, M, B, param) -> list:
+    """Batched complex64 PCG with the handle's Jacobi diagonal (clcg_hip_lpcg_multi_c64; A.build_jacobi() first).  As
+    clbicg_sym_multi_c64."""
+    return _multi("clcg_hip_lpcg_multi_c64", A, M, B, param, cplx="c64")
 
 
 def dense_clbicg_sym_multi(K, M, B, param) -> list:
