@@ -131,3 +131,10 @@ def cmulti64(lib, api, sid, A, M, B, mem="device", **para):
 
 def bits(a):
     return np.ascontiguousarray(a).view(np.uint64)
+
+
+def row_bound(lens, R, absax):
+    """The per-row bound of the complex64 k-wide product, 3 (len_i + 5 + T) 2^-24 (|A||x|)_i with T = 256 / R lanes per row: the
+    derivation and the expression of tests/test_gpu_multi_c64_product.py::test_rounding_bound_on_full_mantissa_data, for the tests
+    that anchor that product elsewhere (tests/test_gpu_streams_kwide.py)."""
+    return 3.0 * (np.asarray(lens) + 5 + 256 // R) * U32 * absax + 1e-30

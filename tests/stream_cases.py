@@ -1,4 +1,4 @@
-"""Helpers of tests/test_gpu_streams.py: the late-input pattern that shows on WHICH stream the library's work runs.
+"""Helpers of tests/test_gpu_streams.py and tests/test_gpu_streams_kwide.py: the late-input pattern that shows on WHICH stream the library's work runs.
 
 lcg_hip_set_stream() puts the library on a caller's stream.  The library's own stream is a blocking one, so everything the rest
 of the suite does is ordered against torch's default stream by the runtime; a torch side stream is non-blocking and has no such
@@ -180,18 +180,80 @@ class Env:
         torch.cuda.synchronize()
         return r, outs
 
-    def pair(self, inputs, call, outputs, enqueue_only, tag=(), anchor=None, on_default=False):
+    def pair(self, inputs, call, outputs, enqueue_only, tag=(), anchor=None, on_default=False, between=None):
         """(a) then (b); anchor(r, outs) holds run (a) to the exact reference first, so that the identity never compares two wrong
-        answers.  Returns run (a)."""
+        answers.  between() runs on the own stream after the anchor: where run (a) leaves the right intermediate in scratch that the
+        handle owns, it overwrites that scratch, so that a launch of run (b) that reads it too early cannot find run (a)'s.
+        Returns run (a)."""
         ra, oa = self.reference(inputs, call, outputs)
         if anchor is not None:
             anchor(ra, oa)
+        if between is not None:
+            between()
+            self.api.synchronize()
+            self.torch.cuda.synchronize()
         rb, ob = self.late(inputs, call, outputs, enqueue_only, on_default=on_default)
         assert same_scalars(ra, rb), (tag, "returned values", ra, rb)
         for i, (a, b) in enumerate(zip(oa, ob)):
             assert a.dtype == b.dtype and a.tobytes() == b.tobytes(), (tag, "output", i, "differs from the run on the own stream",
                                                                        int(np.isnan(b.view(np.float32 if b.dtype == np.complex64 else np.float64)).sum()), "NaN words")
         return ra, oa
+
+
+def make_env(torch, api, lib):
+    """The calibrated delay, the control system and the side stream the controls accepted (Env.pick_stream): what the `env` fixture
+    of either stream module wraps.  close_env() when the module is done."""
+    from test_gpu_exact_products import data
+    from test_gpu_kernels import _ragged
+    e = Env(torch, api, lib)
+    rng = np.random.default_rng(1)
+    rp, col = _ragged(rng, 3001, 3001, 30)
+    val, x = data(rng, rp, 3001, False, True)
+    A = api.CsrMatrix.from_csr(rp, col, val)
+    xs = torch.from_numpy(np.ascontiguousarray(x)).cuda(); y = torch.empty_like(xs)
+    A.spmv(xs, y); api.synchronize()            # (the first product builds the handle's plan: not inside the control)
+    e.control_system = (A, xs, rp, col, val, x)
+    e.rows = torch.from_numpy(np.flatnonzero(np.diff(rp) > 0)).cuda()
+    e.pick_stream(A, xs)
+    print(f"stream tests: accepted candidate {e.accepted}")
+    return e
+
+
+def close_env(e):
+    e.api.use_own_stream()
+    e.control_system[0].destroy()
+
+
+def pick_second(env):
+    """A second side stream that does not queue behind the first: a product on it (the library switched to it) while the FIRST runs
+    the delay and writes x late sees NaN -- otherwise the switch tests would be blind to a missing wait."""
+    torch, api = env.torch, env.api
+    S1 = env.need_stream()
+    A, xs, *_ = env.control_system
+    x, y = torch.empty_like(xs), torch.empty_like(xs)
+    for i in range(CANDIDATES):
+        S2 = torch.cuda.Stream()
+        env.kept.append(S2)
+        nan_fill(x); y.zero_()
+        torch.cuda.synchronize()
+        try:
+            with torch.cuda.stream(S1):
+                E = env.delay.enqueue()
+                x.copy_(xs, non_blocking=True)
+                assert not E.query(), PREMISE
+            with torch.cuda.stream(S2):
+                api.use_torch_stream()          # (from the idle own stream: nothing to wait for)
+                A.spmv(x, y)
+                S2.synchronize()
+            S1.synchronize()
+        finally:
+            api.use_own_stream()
+        torch.cuda.synchronize()
+        seen = env.all_nan(y)
+        print(f"stream tests: second stream, candidate {i}: {'independent of the first' if seen else 'queued behind the first'}")
+        if seen:
+            return S2
+    raise AssertionError("no second stream runs beside the first: the switch tests would be blind")
 
 
 def same_scalars(a, b):
@@ -284,3 +346,215 @@ class DevPtr:
     pointers it is handed."""
     def __init__(self, ptr, n, typestr="<f8"):
         self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+
+
+# ------------------------------------------------------------------------------------------ which test runs which entry
+# Every entry include/lcg_hip.h exports, and the stream test that runs it under the late-input pattern -- or why none does.
+# tests/test_streams_cpu.py holds the table to the header (no entry missing, none left over) and each covered entry to its test:
+#   "file::test"                  the test exists in tests/file, and the file's text names the entry;
+#   ("file::test", text)          ... the file's text holds `text`, a call of the liblcg_amd.api method that wraps the entry;
+#   ("file::test", text, helper)  ... the call is spelled in tests/helper, a module the test file uses: `text` is found there;
+#   ("exempt", reason)            no stream test: getters, host-side switches, comm / p2p (they need peers), test hooks, lcg_hip_init.
+OLD, NEW = "test_gpu_streams.py", "test_gpu_streams_kwide.py"
+_CONTRACT, _LOOPS = "test_gpu_stop_contract.py", "stop_cases.py"
+_GETTER = ("exempt", "a query answered on the host: enqueues nothing")
+_SWITCH = ("exempt", "sets a host-side switch: enqueues nothing")
+_HOOK = ("exempt", "a test or probe hook")
+_PEERS = ("exempt", "comm / p2p: needs peers (multi-GPU paths on a caller's stream are not covered)")
+_FREES = ("exempt", "frees device memory (after a device synchronise where something may be in flight): enqueues nothing")
+_GENERATED = ("exempt", "builds a matrix or a vector from a seed: no input of the caller's that could be written late")
+_SOLVERS = OLD + "::test_solver_loops"
+_FACTOR = OLD + "::test_factor_built_and_applied_on_a_side_stream"
+_CALLBACKS = NEW + "::test_ready_made_callbacks_called_directly"
+_NEW_LOOPS = NEW + "::test_batched_loops_of_the_new_families"
+_CREATED = NEW + "::test_csr_handles_made_from_device_memory_written_late"
+
+STREAM_COVERAGE = {
+    # runtime / stream
+    "lcg_hip_init": ("exempt", "selects the device"),
+    "lcg_hip_set_stream": OLD + "::test_get_stream_and_setting_the_current_stream_again",
+    "lcg_hip_get_stream": OLD + "::test_get_stream_and_setting_the_current_stream_again",
+    "lcg_hip_synchronize": OLD + "::test_back_to_the_own_stream_and_synchronize",
+    "lcg_hip_memcpy": (_FACTOR, "A.ic0_factor_to_host"),
+    "lcg_hip_last_error": _GETTER,
+    "lcg_hip_default_parameters": _GETTER,
+    "clcg_hip_default_parameters": _GETTER,
+    "lcg_hip_last_iterations": _GETTER,
+    "lcg_hip_last_residual": _GETTER,
+    "lcg_hip_set_profiling": _SWITCH,
+    "lcg_hip_last_ax_mean_us": _GETTER,
+    "lcg_hip_last_ax_calls": _GETTER,
+    "lcg_hip_last_launches": _GETTER,
+    "lcg_hip_last_finisher_steps": _GETTER,
+    "lcg_hip_trim": _FREES,
+    "lcg_hip_set_cg_schedule": _SWITCH,
+    "lcg_hip_set_placement": _SWITCH,
+    "lcg_hip_last_placement": _GETTER,
+    "lcg_hip_pool_info": _GETTER,
+    "lcg_hip_pool_add_arena_for_test": _HOOK,
+    "lcg_hip_placement_tune_for_test": _HOOK,
+    "lcg_hip_last_placement_walk": _GETTER,
+    # solver entries: every loop of stop_cases.LOOPS through Bench.solve
+    "lcg_hip_solver": (_SOLVERS, "api.lcg_solver(", _CONTRACT),
+    "lcg_hip_solver_preconditioned": (_SOLVERS, "api.lcg_solver_preconditioned(", _CONTRACT),
+    "lcg_hip_solver_constrained": (_SOLVERS, "api.lcg_solver_constrained(", _CONTRACT),
+    "lcg_hip_lcg": (_SOLVERS, "api.lcg(", _CONTRACT),
+    "lcg_hip_lcgs": (_SOLVERS, "api.lcgs(", _CONTRACT),
+    "clcg_hip_solver": (_SOLVERS, "api.clcg_solver(", _CONTRACT),
+    "clcg_hip_solver_preconditioned": (_SOLVERS, "api.clcg_solver_preconditioned(", _CONTRACT),
+    "clcg_hip_solver_c64": (_SOLVERS, "api.clcg_solver_c64(", _CONTRACT),
+    "clcg_hip_solver_preconditioned_c64": (_SOLVERS, "api.clcg_solver_preconditioned_c64(", _CONTRACT),
+    "lcg_hip_set_shadow_seed": ("exempt", "host-side state of the next complex solve"),
+    "lcg_hip_set_shadow_vector": ("exempt", "host-side state of the next complex solve (the solve uploads it on its stream)"),
+    # CSR matrices
+    "lcg_hip_csr_create": _CREATED,
+    "lcg_hip_csr_create_c64": _CREATED,
+    "lcg_hip_csr_from_coo": _CREATED,
+    "lcg_hip_csr_destroy": _FREES,
+    "lcg_hip_csr_rows": _GETTER,
+    "lcg_hip_csr_nnz": _GETTER,
+    "lcg_hip_csr_arrays": _GETTER,
+    "lcg_hip_csr_set_kernel": _SWITCH,
+    "lcg_hip_csr_set_packed": NEW + "::test_symmetric_run_stretch_adopted_values_written_late",
+    "lcg_hip_csr_packed_runs": _GETTER,
+    "lcg_hip_csr_set_run_stretches": _SWITCH,
+    "lcg_hip_csr_run_stretches": _GETTER,
+    "lcg_hip_csr_set_sym_runs": _SWITCH,
+    "lcg_hip_csr_set_sym_slices": _SWITCH,
+    "lcg_hip_csr_sym_runs": _GETTER,
+    "lcg_hip_csr_packed_templates": _GETTER,
+    "lcg_hip_csr_set_binned": _SWITCH,
+    "lcg_hip_csr_set_tiled": _SWITCH,
+    "lcg_hip_csr_tiled_status": _GETTER,
+    "lcg_hip_csr_set_ranges": _SWITCH,
+    "lcg_hip_csr_ranges": _GETTER,
+    "lcg_hip_csr_binned_status": _GETTER,
+    "lcg_hip_csr_last_kernel": _GETTER,
+    "lcg_hip_csr_last_traffic_model": _GETTER,
+    "lcg_hip_csr_plan_info": _GETTER,
+    "lcg_hip_csr_build_jacobi": OLD + "::test_jacobi",
+    # ready-made callbacks
+    "lcg_hip_csr_ax": OLD + "::test_host_vectors",
+    "lcg_hip_jacobi_mx": OLD + "::test_jacobi",
+    "clcg_hip_csr_ax": OLD + "::test_host_vectors",
+    "clcg_hip_jacobi_mx": (_SOLVERS, "clcg_hip_jacobi_mx", _LOOPS),
+    "clcg_hip_csr_ax_c64": OLD + "::test_host_vectors",
+    "clcg_hip_jacobi_mx_c64": (_SOLVERS, "clcg_hip_jacobi_mx_c64", _LOOPS),
+    # IC(0)
+    "lcg_hip_csr_build_ic0": (_FACTOR, "A.build_ic0"),
+    "lcg_hip_csr_build_ic0_c64": (_FACTOR, "A.build_ic0"),
+    "lcg_hip_csr_ic0_info": _GETTER,
+    "lcg_hip_csr_ic0_set_sweeps": ("exempt", "allocates or frees the two sweep vectors: enqueues nothing"),
+    "lcg_hip_csr_ic0_get_sweeps": _GETTER,
+    "lcg_hip_csr_ic0_factor": _GETTER,
+    "lcg_hip_ic0_solve": (_FACTOR, "A.ic0_solve"),
+    "lcg_hip_ic0_solve_c64": (_FACTOR, "A.ic0_solve"),
+    "lcg_hip_ic0_mx": (_SOLVERS, "lcg_hip_ic0_mx", _LOOPS),
+    "clcg_hip_ic0_mx": _CALLBACKS,
+    "clcg_hip_ic0_mx_c64": _CALLBACKS,
+    "lcg_hip_csr_ic0_schedule_for_test": _HOOK,
+    # ILU(0)
+    "lcg_hip_csr_build_ilu0": (_FACTOR, "A.build_ilu0"),
+    "lcg_hip_csr_ilu0_info": _GETTER,
+    "lcg_hip_csr_ilu0_set_sweeps": ("exempt", "allocates or frees the two sweep vectors: enqueues nothing"),
+    "lcg_hip_csr_ilu0_get_sweeps": _GETTER,
+    "lcg_hip_csr_ilu0_factor": _GETTER,
+    "lcg_hip_ilu0_solve": (_FACTOR, "A.ilu0_solve"),
+    "lcg_hip_ilu0_mx": (_SOLVERS, "lcg_hip_ilu0_mx", _LOOPS),
+    "clcg_hip_ilu0_mx": _CALLBACKS,
+    "lcg_hip_csr_ax_ilu0": (_SOLVERS, "lcg_hip_csr_ax_ilu0", _LOOPS),
+    "clcg_hip_csr_ax_ilu0": _CALLBACKS,
+    "lcg_hip_csr_ilu0_schedule_for_test": _HOOK,
+    # dense operators
+    "lcg_hip_dense_create": NEW + "::test_dense_handle_made_from_device_memory_written_late",
+    "lcg_hip_dense_create_rows": ("exempt", "host rows only, staged and uploaded before it returns: no input that could be written late"),
+    "lcg_hip_dense_destroy": _FREES,
+    "lcg_hip_dense_rows": _GETTER,
+    "lcg_hip_dense_cols": _GETTER,
+    "lcg_hip_dense_matvec": OLD + "::test_dense_products",
+    "clcg_hip_dense_matvec": NEW + "::test_complex_dense_block_products",
+    "lcg_hip_dense_ata": OLD + "::test_dense_products",
+    "lcg_hip_dense_ata_ax": (_SOLVERS, "lcg_hip_dense_ata_ax", _CONTRACT),
+    "lcg_hip_dense_ax": _CALLBACKS,
+    "clcg_hip_dense_ax": _CALLBACKS,
+    "lcg_hip_dense_build_jacobi": NEW + "::test_dense_jacobi_built_on_a_side_stream",
+    "lcg_hip_dense_jacobi_mx": NEW + "::test_dense_jacobi_built_on_a_side_stream",
+    "clcg_hip_dense_jacobi_mx": _CALLBACKS,
+    "lcg_hip_dense_last_kernel": _GETTER,
+    "lcg_hip_dense_kernel_name": _GETTER,
+    "lcg_hip_dense_set_kernel": _SWITCH,
+    "lcg_hip_dense_matmat": NEW + "::test_real_dense_block_products",
+    "lcg_hip_dense_ata_multi": NEW + "::test_real_dense_block_products",
+    "lcg_hip_dense_op_multi_dot": NEW + "::test_real_dense_block_products",
+    "lcg_hip_dense_multi_last_kernel": _GETTER,
+    "lcg_hip_dense_multi_kernel_name": _GETTER,
+    "lcg_hip_dense_lcg_multi": _NEW_LOOPS,
+    "lcg_hip_dense_lpcg_multi": _NEW_LOOPS,
+    "clcg_hip_dense_matmat": NEW + "::test_complex_dense_block_products",
+    "clcg_hip_dense_op_multi_dot": NEW + "::test_complex_dense_block_products",
+    "clcg_hip_dense_multi_kernel_name": _GETTER,
+    "clcg_hip_dense_lbicg_sym_multi": _NEW_LOOPS,
+    "clcg_hip_dense_lpcg_multi": _NEW_LOOPS,
+    # kernels
+    "lcg_hip_spmv": OLD + "::test_real_product_families",
+    "lcg_hip_spmv_op": OLD + "::test_spmv_op_all_forms",
+    "lcg_hip_spmv_dot": OLD + "::test_spmv_dot",
+    "lcg_hip_spmm": OLD + "::test_real_block_products",
+    "lcg_hip_spmm_dot": OLD + "::test_real_block_products",
+    "lcg_hip_spmm_dot2": OLD + "::test_real_block_products",
+    "lcg_hip_lcg_multi": OLD + "::test_batched_loops",
+    "lcg_hip_lpcg_multi": OLD + "::test_batched_loops",
+    "lcg_hip_ic0_solve_multi": OLD + "::test_batched_triangular_solves",
+    "lcg_hip_ilu0_solve_multi": OLD + "::test_batched_triangular_solves",
+    "lcg_hip_lpcg_multi_m": OLD + "::test_batched_loops",
+    "lcg_hip_lbicgstab_multi": OLD + "::test_batched_loops",
+    "clcg_hip_spmm": OLD + "::test_complex_block_products",
+    "clcg_hip_spmm_dot": OLD + "::test_complex_block_products",
+    "clcg_hip_lbicg_sym_multi": OLD + "::test_batched_loops",
+    "clcg_hip_lpcg_multi": OLD + "::test_batched_loops",
+    "lcg_hip_spmv_c64": OLD + "::test_c128_and_c64_products",
+    "clcg_hip_spmm_c64": NEW + "::test_complex64_block_products",
+    "clcg_hip_spmm_dot_c64": NEW + "::test_complex64_block_products",
+    "clcg_hip_lbicg_sym_multi_c64": _NEW_LOOPS,
+    "clcg_hip_lpcg_multi_c64": _NEW_LOOPS,
+    "lcg_hip_dot": (OLD + "::test_level_one", "api.dot("),
+    "lcg_hip_nrm2": (OLD + "::test_level_one", "api.nrm2("),
+    "lcg_hip_axpy": OLD + "::test_level_one",
+    "lcg_hip_scal": OLD + "::test_level_one",
+    "lcg_hip_set2box": OLD + "::test_level_one",
+    "lcg_hip_vecmul": OLD + "::test_level_one",
+    "lcg_hip_vecdiv": OLD + "::test_level_one",
+    "clcg_hip_dot": (OLD + "::test_level_one", "api.cdot("),
+    "clcg_hip_inner": (OLD + "::test_level_one", "api.cdot("),
+    "clcg_hip_axpy": NEW + "::test_complex_level_one",
+    "clcg_hip_vecdiv": NEW + "::test_complex_level_one",
+    # generators
+    "lcg_hip_csr_generate": _GENERATED,
+    "lcg_hip_csr_generate_ex": _GENERATED,
+    "lcg_hip_gen_xtrue": _GENERATED,
+    "lcg_hip_csr_laplace2d": _GENERATED,
+    # several GPUs
+    "lcg_hip_comm_unique_id": _PEERS,
+    "lcg_hip_comm_init": _PEERS,
+    "lcg_hip_comm_destroy": _PEERS,
+    "lcg_hip_comm_rank": _PEERS,
+    "lcg_hip_comm_size": _PEERS,
+    "lcg_hip_comm_library": _PEERS,
+    "lcg_hip_csr_distribute": _PEERS,
+    "lcg_hip_csr_exchange_volume": _PEERS,
+    "lcg_hip_allreduce_sum": _PEERS,
+    "lcg_hip_barrier": _PEERS,
+    "lcg_hip_p2p_export": _PEERS,
+    "lcg_hip_p2p_connect": _PEERS,
+    "lcg_hip_p2p_selftest": _PEERS,
+    "lcg_hip_p2p_enable": _PEERS,
+    "lcg_hip_p2p_status": _PEERS,
+    "lcg_hip_p2p_set_timeout_ms": _PEERS,
+    "lcg_hip_p2p_disconnect": _PEERS,
+    "lcg_hip_csr_split_for_test": OLD + "::test_sharded_product_on_one_gpu",
+    "lcg_hip_csr_xfull": _GETTER,
+    "lcg_hip_csr_ax_part_for_probe": _HOOK,
+    "lcg_hip_csr_direct_selfloop_for_test": _HOOK,
+    "lcg_hip_csr_local_nnz": _GETTER,
+    "lcg_hip_csr_need_ranges_for_test": _HOOK,
+}

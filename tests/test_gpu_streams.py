@@ -51,21 +51,10 @@ def seed_of(*name):
 
 @pytest.fixture(scope="module")
 def env(api, lib):
-    """The calibrated delay and the side stream the controls accepted (stream_cases.Env.pick_stream)."""
-    e = st.Env(torch, api, lib)
-    rng = np.random.default_rng(1)
-    rp, col = _ragged(rng, 3001, 3001, 30)
-    val, x = data(rng, rp, 3001, False, True)
-    A = api.CsrMatrix.from_csr(rp, col, val)
-    xs = dev(x); y = torch.empty_like(xs)
-    A.spmv(xs, y); api.synchronize()            # (the first product builds the handle's plan: not inside the control)
-    e.control_system = (A, xs, rp, col, val, x)
-    e.rows = dev(np.flatnonzero(np.diff(rp) > 0))
-    e.pick_stream(A, xs)
-    print(f"stream tests: accepted candidate {e.accepted}")
+    """The calibrated delay and the side stream the controls accepted (stream_cases.make_env)."""
+    e = st.make_env(torch, api, lib)
     yield e
-    api.use_own_stream()
-    A.destroy()
+    st.close_env(e)
 
 
 # ================================================================================================ the control
@@ -698,33 +687,8 @@ def test_default_stream_cg_solve(env, benches):
 @pytest.fixture(scope="module")
 def second(env, api):
     """A second side stream that does not queue behind the first: a product on it (the library switched to it) while the FIRST runs
-    the delay and writes x late sees NaN -- otherwise the switch tests would be blind to a missing wait."""
-    S1 = env.need_stream()
-    A, xs, *_ = env.control_system
-    x, y = torch.empty_like(xs), torch.empty_like(xs)
-    for i in range(st.CANDIDATES):
-        S2 = torch.cuda.Stream()
-        env.kept.append(S2)
-        st.nan_fill(x); y.zero_()
-        torch.cuda.synchronize()
-        try:
-            with torch.cuda.stream(S1):
-                E = env.delay.enqueue()
-                x.copy_(xs, non_blocking=True)
-                assert not E.query(), st.PREMISE
-            with torch.cuda.stream(S2):
-                api.use_torch_stream()          # (from the idle own stream: nothing to wait for)
-                A.spmv(x, y)
-                S2.synchronize()
-            S1.synchronize()
-        finally:
-            api.use_own_stream()
-        torch.cuda.synchronize()
-        seen = env.all_nan(y)
-        print(f"stream tests: second stream, candidate {i}: {'independent of the first' if seen else 'queued behind the first'}")
-        if seen:
-            return S2
-    raise AssertionError("no second stream runs beside the first: the switch tests would be blind")
+    the delay and writes x late sees NaN -- otherwise the switch tests would be blind to a missing wait (stream_cases.pick_second)."""
+    return st.pick_second(env)
 
 
 def test_switch_then_read_the_product_and_reuse_the_plan(env, api, lib, second):
