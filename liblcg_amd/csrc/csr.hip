@@ -1396,20 +1396,24 @@ static const char *ldsp_name(const CsrPart &P, bool dot)
 static const char *sym_runs_name(const CsrPart &P, bool dot)
 {
 #define SYM_AROUND(s) " around k_spmv_ldsp_sym (symmetric run stretch: half store in dispatch order, " s ")"
-#define SYM_NAMES(base, tail) {base SYM_AROUND("one slice") tail, base SYM_AROUND("two slices") tail, base SYM_AROUND("four slices") tail, base SYM_AROUND("eight slices") tail}
+#define SYM_GROUPED(s) " around k_spmv_ldsp_sym (symmetric run stretch: half store in block order, one slice, " s " consecutive blocks per XCD)"
+#define SYM_NAMES(base, tail) {base SYM_AROUND("one slice") tail, base SYM_AROUND("two slices") tail, base SYM_AROUND("four slices") tail, base SYM_AROUND("eight slices") tail, \
+                              base SYM_GROUPED("two") tail, base SYM_GROUPED("four") tail, base SYM_GROUPED("eight") tail}
 #define SYM_DOT " carrying the dot that follows the product"
-    const int nx = P.pk_sym.NX == 8 ? 3 : P.pk_sym.NX == 4 ? 2 : P.pk_sym.NX == 2 ? 1 : 0, tpl = P.pk_tpls > 0 ? 1 : 0;
+    const int G = sym_group_in_use(P);                  // (more than one: one slice only)
+    const int nx = G == 8 ? 6 : G == 4 ? 5 : G == 2 ? 4 : P.pk_sym.NX == 8 ? 3 : P.pk_sym.NX == 4 ? 2 : P.pk_sym.NX == 2 ? 1 : 0, tpl = P.pk_tpls > 0 ? 1 : 0;
     if (dot) {
-        static const char *const d[2][4] = {SYM_NAMES("k_spmv_ldsp (LDS-staged, run blocks + packed columns)", SYM_DOT),
+        static const char *const d[2][7] = {SYM_NAMES("k_spmv_ldsp (LDS-staged, run blocks + packed columns)", SYM_DOT),
                                             SYM_NAMES("k_spmv_ldsp (LDS-staged, run blocks + template blocks + packed columns)", SYM_DOT)};
         return d[tpl][nx];
     }
-    static const char *const a[2][2][4] = {{SYM_NAMES("k_spmv_ldsp (LDS-staged, run blocks + 18-bit packed columns)", ""),
+    static const char *const a[2][2][7] = {{SYM_NAMES("k_spmv_ldsp (LDS-staged, run blocks + 18-bit packed columns)", ""),
                                             SYM_NAMES("k_spmv_ldsp (LDS-staged, run blocks + template blocks + 18-bit packed columns)", "")},
                                            {SYM_NAMES("k_spmv_ldsp (LDS-staged, run blocks + 21-bit packed columns)", ""),
                                             SYM_NAMES("k_spmv_ldsp (LDS-staged, run blocks + template blocks + 21-bit packed columns)", "")}};
 #undef SYM_DOT
 #undef SYM_NAMES
+#undef SYM_GROUPED
 #undef SYM_AROUND
     return a[P.pk_bits == 18 ? 0 : 1][tpl][nx];
 }

@@ -37,6 +37,7 @@ bool sym_runs_wanted(const CsrPart &P);                     // the mode, the par
 void sym_runs_build(const CsrPart &P, hipStream_t s);       // from the part's run stretches (csr.hip: run_stretches_build), once per plan
 inline bool sym_runs_in_use(const CsrPart &P) { return P.pk_state == 1 && P.pk_sym.NX > 0; }
 int64_t sym_runs_bytes(const CsrPart &P);                   // the half store
+int sym_group_in_use(const CsrPart &P);                     // consecutive blocks per XCD its kernel's workgroups are dealt in: 1, 2, 4 or 8 (one slice only)
 // y = A.x for the rows of the sliced range; the other blocks are the caller's (csr.hip: ldsp_launch)
 void sym_runs_launch(const CsrPart &P, bool dot, const double *x, double *y, hipStream_t s, const int *done, const DotPlan &dp);
 

@@ -17,6 +17,11 @@ namespace lcgh {
 // (profiles/sym_runs_ab.txt): one slice 1619-1632 CG iterations/s against the parent's 1463-1551 in the job that ran the shipped form;
 // in the jobs of the first form one slice 1613-1632, two / four / eight slices 1585-1600 / 1565-1571 / 1576-1617, parent 1498-1581.
 constexpr int SYM_NX_DEFAULT = 1;
+// Consecutive blocks per XCD of the one slice where LCG_HIP_SYM_GROUP names no count (1 / 2 / 4 / 8, for the whole process): four.
+// Measured on the same system (profiles/sym_group_ab.txt): FETCH_SIZE of the kernel 1590.5 -> 1505.4 / 1478.2 / 1502.5 MB with
+// two / four / eight, 1653-1658 / 1655-1657 / 1648-1651 CG iterations/s against the parent's 1632-1634 in one job.
+// (tests/test_gpu_sym_groups.py holds the kernel string to this count: DEFAULT there changes with it.)
+constexpr int SYM_GROUP_DEFAULT = 4;
 constexpr int SYM_MAXL = 36;        // entries per row k_spmv_ldsp_sym is instantiated for (nine slots per lane; a block of 64 rows fits the LDS window up to 35)
 
 static int sym_mode_of(const CsrPart &P)
@@ -79,11 +84,17 @@ __global__ __launch_bounds__(VB) void k_sym_pack(SymRun sr, int b0, int s0, cons
     for (int idx = threadIdx.x; idx < PK_R * (p + 1); idx += VB) dst[idx] = val[e0 + (long)(idx % PK_R) * L + p + idx / PK_R];
 }
 
-// Workgroup w of the sliced range: block sym_block_of(w), own tile Q + w.  Lane (row r, wavefront j0) takes slots k = j0, j0 + 4, ...
+// Workgroup w of the sliced range: block sym_block_of(w), own tile Q + w (one slice: block sym_group_block_of(w), own tile
+// Q + block - inner0: see below).  Lane (row r, wavefront j0) takes slots k = j0, j0 + 4, ...
 // as in a run block (csr.hip: run_block).  A slot k >= p reads H[own tile][k - p][r]; a slot k < p reads the partner row's upper
 // entry, H[tile of row i + off[k]][p - k][(i + off[k]) & 63] -- the wavefront's 64 partner rows lie in two consecutive blocks, whose
 // tiles are scalar arithmetic; a lane only selects between the two bases.  Values and x gathers go out together; the additions run
 // in run_block's order, the carried dot's partial keeps the BLOCK's slot and its u comes from the gather of slot p.
+// One slice: which block workgroup w takes is sym_group_block_of's permutation (sr.G consecutive blocks per XCD; the identity at
+// G = 1) and the block's tile is Q + its number in the range, wherever it was dispatched.  A lower slot's 512-byte partner run
+// starts at row off[k] & 63 of a tile row and ends in the next tile's: unless that is a multiple of 16 rows, the 128-byte line it
+// ends in is the line the NEXT block's run starts in, and the x gathers straddle likewise.  Neighbouring blocks dealt to different
+// XCDs fetch such a line into two L2s; on one XCD the second reader finds it there.  Per block nothing else changes: the same bits.
 template <int NS, bool DOT>
 __global__ __launch_bounds__(VB) void k_spmv_ldsp_sym(SymRun sr, const double *__restrict__ x, double *__restrict__ y, const int *done, DotPlan dp)
 {
@@ -95,12 +106,13 @@ __global__ __launch_bounds__(VB) void k_spmv_ldsp_sym(SymRun sr, const double *_
     const int rl = tid % PK_R, j0 = tid / PK_R;
     const int w = __builtin_amdgcn_readfirstlane(j0);
     const int wg = blockIdx.x;
-    const int bid = sym_block_of(wg, sr.inner0, sr.S, sr.NX);
+    const int bid = sr.NX == 1 ? sym_group_block_of(wg, sr.inner0, sr.S, sr.G) : sym_block_of(wg, sr.inner0, sr.S, sr.NX);
+    const int wt = sr.NX == 1 ? bid - sr.inner0 : wg;   // own tile = Q + wt.  One slice: the block's number in the range, whichever workgroup takes it; slices: dispatch order
     const int row0 = bid * PK_R;
     const int p = sr.p, L = 2 * p + 1;
     const long TS = (long)(p + 1) * PK_R;
     const double *__restrict__ H = sr.H;
-    const double *own = H + (long)(sr.Q + wg) * TS;
+    const double *own = H + (long)(sr.Q + wt) * TS;
     const int *__restrict__ tw = sr.off + w * sr.TQ;    // this wavefront's slots side by side, zeros behind the L-th
     int stop = 0, cs[NS];
     if (done) stop = *done;
@@ -111,10 +123,10 @@ __global__ __launch_bounds__(VB) void k_spmv_ldsp_sym(SymRun sr, const double *_
     if (DOT && kd < 0) uv = dp.u[j0 == 0 ? row0 + rl : 0];
     // tile of block b <= bid (uniform): NX tiles per block back while b stays in this block's slice -- all but the first Q blocks of
     // a slice look no further -- else the map's division (across a slice's front, or into the apron)
-    const int jown = wg >> (sr.NX == 8 ? 3 : sr.NX == 4 ? 2 : sr.NX == 2 ? 1 : 0);
+    const int jown = wt >> (sr.NX == 8 ? 3 : sr.NX == 4 ? 2 : sr.NX == 2 ? 1 : 0);
     const auto tile_of = [&](int b) {
         const int jb = jown - (bid - b);
-        return jb >= 0 ? sr.Q + wg - sr.NX * (bid - b) : sym_tile_of(b, sr.inner0, sr.S, sr.NX, sr.Q);
+        return jb >= 0 ? sr.Q + wt - sr.NX * (bid - b) : sym_tile_of(b, sr.inner0, sr.S, sr.NX, sr.Q);
     };
     double xv[NS], av[NS];
 #pragma unroll
@@ -157,9 +169,18 @@ __global__ __launch_bounds__(VB) void k_spmv_ldsp_sym(SymRun sr, const double *_
     if (DOT) ldsp_dot_tail(dp, bid, j0, vfin, uv);
 }
 
+int sym_group_in_use(const CsrPart &P)
+{
+    static const int env = [] { const char *e = std::getenv("LCG_HIP_SYM_GROUP"); return e ? atoi(e) : 0; }();     // A/B runs: 1 / 2 / 4 / 8 for the whole process
+    const auto ok = [](int v) { return v == 1 || v == 2 || v == 4 || v == 8; };
+    if (P.pk_sym.NX != 1) return 1;                     // (slices have their own placement)
+    return ok(env) ? env : SYM_GROUP_DEFAULT;
+}
+
 void sym_runs_launch(const CsrPart &P, bool dot, const double *x, double *y, hipStream_t s, const int *done, const DotPlan &dp)
 {
-    const SymRun &sr = P.pk_sym;
+    SymRun sr = P.pk_sym;
+    sr.G = sym_group_in_use(P);
     const dim3 g((unsigned)(sr.NX * sr.S));
     const bool small = 2 * sr.p + 1 <= 24;
     if (dot) {

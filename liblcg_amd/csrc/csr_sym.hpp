@@ -15,7 +15,7 @@ namespace lcgh {
 // only lend their tiles to the partner reads of the blocks behind them.  Blocks [inner0, inner0 + NX * S) are the SLICED RANGE:
 // NX slices of S consecutive blocks; dispatched workgroup w of the range works on block inner0 + (w % NX) * S + w / NX, so that
 // workgroups w, w + NX, w + 2 NX ... (one XCD when NX = 8, two when NX = 4: workgroups are dealt round-robin over the eight) walk
-// one slice front to back.
+// one slice front to back.  (One slice: the tiles are in block order and the workgroups are dealt by sym_group_block_of below.)
 // Tile t of the half store holds one block's diagonal and p upper diagonals, diagonal-major: H[t][k][r], k = 0 .. p, r = 0 .. 63.
 // The apron's tiles come first, in block order; block inner0 + e * S + j has tile Q + NX * j + e -- dispatch order, so the
 // slices interleave in memory and the value stream stays one front in address space.
@@ -23,6 +23,7 @@ struct SymRun {
     int inner0 = 0;     // first block of the sliced range
     int S = 0;          // blocks per slice
     int NX = 0;         // slices: 1, 2, 4 or 8 (0: no symmetric stretch)
+    int G = 1;          // one slice: consecutive blocks per XCD (sym_group_block_of), set where the product is launched
     int Q = 0;          // apron blocks = tiles in front of the sliced range's
     int p = 0;          // pairs of diagonals: L = 2 p + 1 entries per row, slot p the diagonal
     int TQ = 0;         // the offset of slot k lies at off[(k % 4) * TQ + k / 4] (the stretch's table: RunStretch::off, Q)
@@ -64,6 +65,19 @@ LCG_SYM_HD inline int sym_block_of(int w, int inner0, int S, int NX)
 {
     const int lg = NX == 8 ? 3 : NX == 4 ? 2 : NX == 2 ? 1 : 0;        // (NX is 1, 2, 4 or 8: no division in the kernel)
     return inner0 + (w & (NX - 1)) * S + (w >> lg);
+}
+
+// One slice, G consecutive blocks per XCD (G is 1, 2, 4 or 8): block of dispatched workgroup w.  Workgroups are dealt round-robin
+// over the eight XCDs, so within every full window of 8 G blocks workgroup r of the window (XCD r % 8) takes block (r % 8) * G + r / 8
+// of it: an XCD's G consecutive blocks are dispatched eight workgroups apart, and the 128-byte lines that two neighbouring blocks
+// both read -- where a partner run or an x gather straddles them -- are fetched into ONE L2, once.  The blocks behind the last full
+// window keep their order.  A permutation of the range; the tiles stay where they are (block b: tile Q + b - inner0).
+LCG_SYM_HD inline int sym_group_block_of(int w, int inner0, int S, int G)
+{
+    const int lg = G == 8 ? 3 : G == 4 ? 2 : G == 2 ? 1 : 0, win = 8 << lg;
+    if (w >= (S & ~(win - 1))) return inner0 + w;
+    const int r = w & (win - 1);
+    return inner0 + (w - r) + ((r & 7) << lg) + (r >> 3);
 }
 
 // tile of block b (an apron block or one of the sliced range)
