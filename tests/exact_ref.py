@@ -228,9 +228,24 @@ def bound_c64(lens, absax):
     return 3.0 * (np.asarray(lens, np.float64) + 5) * U32 * absax + 1e-30
 
 
-def bad_rows(y, rp, col, val, x, ref=None, lens=None):
+def select_rows(rp, col, val, rows):
+    """The CSR arrays of the rows `rows` alone (in that order; the columns stay what they are): rowptr from 0, col, val."""
+    rp = np.asarray(rp, np.int64); rows = np.asarray(rows, np.int64)
+    lens = rp[rows + 1] - rp[rows]
+    srp = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    idx = np.repeat(rp[rows] - srp[:-1], lens) + np.arange(srp[-1])
+    return srp, np.asarray(col)[idx], np.asarray(val)[idx]
+
+
+def bad_rows(y, rp, col, val, x, ref=None, lens=None, rows=None):
     """Rows of y outside the per-row bound of the value type (fp64 or c128) against the extended-precision reference.
-    lens: terms per row when they are not the CSR row lengths (COO duplicates, a transposed product)."""
+    lens: terms per row when they are not the CSR row lengths (COO duplicates, a transposed product).
+    rows: check these rows only (y stays the whole product) -- each against the same reference sum, in the same entry order, and
+    the same bound as the full call gives it; a ref / lens passed with it belong to the selection."""
+    if rows is not None:
+        rows = np.asarray(rows, np.int64)
+        srp, scol, sval = select_rows(rp, col, val, rows)
+        return rows[bad_rows(np.asarray(y)[rows], srp, scol, sval, x, ref=ref, lens=lens)]
     ref = hp_product(rp, col, val, x) if ref is None else ref
     lens = lengths(rp) if lens is None else lens
     cplx = ref[1] is not None
@@ -239,7 +254,11 @@ def bad_rows(y, rp, col, val, x, ref=None, lens=None):
     return np.flatnonzero(~(err <= b))
 
 
-def assert_rows(y, rp, col, val, x, tag=(), lens=None, ref=None):
+def assert_rows(y, rp, col, val, x, tag=(), lens=None, ref=None, rows=None):
+    if rows is not None:
+        rows = np.asarray(rows, np.int64)
+        srp, scol, sval = select_rows(rp, col, val, rows)
+        return assert_rows(np.asarray(y)[rows], srp, scol, sval, x, tuple(tag) + ("selected rows",), lens=lens, ref=ref)
     bad = bad_rows(y, rp, col, val, x, ref=ref, lens=lens)
     if len(bad):
         ref = hp_product(rp, col, val, x) if ref is None else ref

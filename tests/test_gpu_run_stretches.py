@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import exact_ref as X
+from sym_cases import expected_stretches
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -51,36 +52,6 @@ def _break(rows, r):
     c[k] = c[k - 1] + 1 if c[k - 1] + 1 < c[k] else c[k] - 1
     assert not np.array_equal(c, rows[r]) and np.all(np.diff(c) > 0)
     rows[r] = c
-
-
-def expected_stretches(rp, col, n):
-    """Lengths (in blocks) of the stretches in use, from the CSR arrays: the four longest maximal sequences of >= 2 consecutive full
-    run blocks with the same L, the same offsets of row 0 from the block's first row and entries that follow each other."""
-    rp = np.asarray(rp, np.int64); col = np.asarray(col, np.int64)
-    lens = np.diff(rp)
-    key = []            # per full block: None (no run block) or (L, offsets, first entry)
-    for b in range(n // 64):
-        r0 = 64 * b
-        L = int(lens[r0])
-        s = int(rp[r0])
-        run = L > 0 and bool(np.all(lens[r0:r0 + 64] == L))
-        if run:
-            blk = col[s:s + 64 * L].reshape(64, L)
-            run = bool(np.array_equal(blk, blk[0][None, :] + np.arange(64)[:, None]))
-        key.append((L, tuple((blk[0] - r0).tolist()), s) if run else None)
-    found = []
-    b = 0
-    while b < len(key):
-        if key[b] is None:
-            b += 1
-            continue
-        e = b + 1
-        while e < len(key) and key[e] is not None and key[e][:2] == key[b][:2] and key[e][2] == key[b][2] + (e - b) * 64 * key[b][0]:
-            e += 1
-        if e - b >= 2:
-            found.append(e - b)
-        b = e
-    return sorted(found, reverse=True)[:4]
 
 
 def _count(top):

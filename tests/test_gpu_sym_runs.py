@@ -2,7 +2,8 @@
 values mirror each other bit for bit multiplies the blocks of its sliced range from a half store, a lower entry read as its partner
 row's upper entry.  Nothing of the result may change by a bit: every product here is compared, as 64-bit integers, with the same
 handle's product with the mode off, and that product is held to exact row sums (exact_ref).  Forced mode throughout: the automatic
-mode looks only at products of >= 512 MB."""
+mode looks only at products of >= 512 MB (tests/test_gpu_sym_mixed.py runs it, and the stretch inside mixed matrices, with the
+systems and helpers of this file)."""
 import ctypes as C
 import hashlib
 
