@@ -1,4 +1,4 @@
-"""ctypes view of the C ABI in ``include/lcg_hip.h`` (liblcg_amd/lib/liblcg_hip.so).
+"""ctypes view of the C ABI in ``include/lcg_hip.h`` and ``include/lcg_hip_staging.h`` (liblcg_amd/lib/liblcg_hip.so).
 
 No compute happens in Python: every function here forwards to the HIP library.  If the
 shared object is missing the import fails loudly -- there is no fallback path.
@@ -217,6 +217,13 @@ SIGNATURES = {
     "lcg_hip_csr_need_ranges_for_test": (C.c_int, [vp, C.c_int, vp]),
 }
 
+# every symbol include/lcg_hip_staging.h declares: entries that wait there for their line in the tests' stream-coverage table
+STAGING_SIGNATURES = {
+    "clcg_hip_spmm_inner": (C.c_int, [vp, C.c_int, vp, vp, vp, c_double_p]),
+    "clcg_hip_spmm_dot2": (C.c_int, [vp, C.c_int, vp, vp, vp, c_double_p]),
+    "clcg_hip_lbicgstab_multi": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.POINTER(ClcgPara), c_int_p, c_int_p, c_double_p, C.c_int]),
+}
+
 _lib = None
 
 
@@ -245,7 +252,7 @@ def load():
     # the SAME runtime objects instead of mapping a second HIP runtime into the process.
     import torch  # noqa: F401
     lib = C.CDLL(SO_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in {**SIGNATURES, **STAGING_SIGNATURES}.items():
         fn = getattr(lib, name)     # AttributeError = header/library drift: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -317,6 +317,31 @@ class CsrMatrix:
         _chk(L.load().clcg_hip_spmm_dot(self.h, k, _ptr(X)[0], _ptr(Y)[0], _ptr(U)[0], out), "cspmm_dot")
         return np.array(out[:], dtype=np.float64).view(np.complex128)
 
+    def cspmm_inner(self, X, Y, u):
+        """cspmm carrying one conjugated sum per column against ONE vector (clcg_hip_spmm_inner): returns a complex128 array of k,
+        [j] = sum_i conj(u_i) Y_ij -- what the batched complex BiCGStab takes after its first product.  X, Y as cspmm's blocks; u a
+        contiguous 1-D complex128 vector of n_rows elements shared by all columns, 16-byte aligned."""
+        k = _block_k(X, Y, cplx=True)
+        if isinstance(u, np.ndarray):
+            ok = u.ndim == 1 and u.dtype == np.complex128 and u.flags["C_CONTIGUOUS"]
+        else:
+            import torch
+            ok = isinstance(u, torch.Tensor) and u.dim() == 1 and u.dtype == torch.complex128 and u.is_contiguous()
+        if not ok or u.shape[0] != Y.shape[0]:
+            raise ValueError("u is a contiguous 1-D complex128 vector with one element per row of Y")
+        out = (C.c_double * (2 * k))()
+        _chk(L.load().clcg_hip_spmm_inner(self.h, k, _ptr(X)[0], _ptr(Y)[0], _ptr(u)[0], out), "cspmm_inner")
+        return np.array(out[:], dtype=np.float64).view(np.complex128)
+
+    def cspmm_dot2(self, X, Y, U):
+        """cspmm carrying two sums per column (clcg_hip_spmm_dot2): returns (a complex128 array of k, [j] = sum_i conj(Y_ij) U_ij;
+        a float64 array of k, [j] = sum_i |Y_ij|^2) -- what the batched complex BiCGStab takes after its second product.  X, Y, U as
+        cspmm's blocks."""
+        k = _block_k(X, Y, U, cplx=True)
+        out = (C.c_double * (3 * k))()
+        _chk(L.load().clcg_hip_spmm_dot2(self.h, k, _ptr(X)[0], _ptr(Y)[0], _ptr(U)[0], out), "cspmm_dot2")
+        return np.array(out[:2 * k], dtype=np.float64).view(np.complex128), np.array(out[2 * k:], dtype=np.float64)
+
     def cspmm_c64(self, X, Y):
         """Y = A.X for the k = 2, 4 or 8 complex64 columns of X in one launch (clcg_hip_spmm_c64): X (n_cols, k) and Y (n_rows, k) are
         C-contiguous complex64 CUDA tensors, 16-byte aligned.  Complex64 matrices (from_csr_c64) on one GPU."""
@@ -644,6 +669,16 @@ def clbicg_sym_multi(A, M, B, param) -> list:
     blocks of k = 2, 4 or 8 columns, every column solved as if it were alone while the matrix is read once per iteration for all
     of them.  param: a ClcgPara (or None).  Returns one SolveInfo per column."""
     return _multi("clcg_hip_lbicg_sym_multi", A, M, B, param, cplx=True)
+
+
+def clbicgstab_multi(A, M, B, param, precond=None) -> list:
+    """Batched BiCGStab for a square complex128 matrix, symmetric or not (clcg_hip_lbicgstab_multi).  precond None: plain; "jacobi":
+    right-preconditioned in x-space with the handle's diagonal (A.build_jacobi() first) -- M holds the solution itself, nothing is
+    applied afterwards.  The shadow residual is the next complex solve's (lcg_hip_set_shadow_seed / _vector), one vector for all
+    columns.  As clbicg_sym_multi."""
+    if precond not in (None, "jacobi"):
+        raise ValueError('precond is None or "jacobi"')
+    return _multi("clcg_hip_lbicgstab_multi", A, M, B, param, M_NONE if precond is None else PRECONDS[precond], cplx=True)
 
 
 def clpcg_multi(A, M, B, param) -> list:

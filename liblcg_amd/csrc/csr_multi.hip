@@ -196,10 +196,16 @@ int multi_dots_read(Ctx &c, int ns, int slots, double *dots)
 {
     // (outside a solve the k-wide table of the loops is free: partials_pair[0] holds the partial sums, ax_partials the results)
     const double *tab = c.partials_pair[0];
-    if (ns == 2) hipLaunchKernelGGL((k_mm_dots<2>), dim3(1), dim3(VB), 0, c.stream, tab, slots, c.ax_partials);
-    else if (ns == 4) hipLaunchKernelGGL((k_mm_dots<4>), dim3(1), dim3(VB), 0, c.stream, tab, slots, c.ax_partials);
-    else if (ns == 8) hipLaunchKernelGGL((k_mm_dots<8>), dim3(1), dim3(VB), 0, c.stream, tab, slots, c.ax_partials);
-    else hipLaunchKernelGGL((k_mm_dots<16>), dim3(1), dim3(VB), 0, c.stream, tab, slots, c.ax_partials);
+    switch (ns) {           // (6, 12, 24: three table rows per column, clcg_hip_spmm_dot2)
+    case 2: hipLaunchKernelGGL((k_mm_dots<2>), dim3(1), dim3(VB), 0, c.stream, tab, slots, c.ax_partials); break;
+    case 4: hipLaunchKernelGGL((k_mm_dots<4>), dim3(1), dim3(VB), 0, c.stream, tab, slots, c.ax_partials); break;
+    case 6: hipLaunchKernelGGL((k_mm_dots<6>), dim3(1), dim3(VB), 0, c.stream, tab, slots, c.ax_partials); break;
+    case 8: hipLaunchKernelGGL((k_mm_dots<8>), dim3(1), dim3(VB), 0, c.stream, tab, slots, c.ax_partials); break;
+    case 12: hipLaunchKernelGGL((k_mm_dots<12>), dim3(1), dim3(VB), 0, c.stream, tab, slots, c.ax_partials); break;
+    case 16: hipLaunchKernelGGL((k_mm_dots<16>), dim3(1), dim3(VB), 0, c.stream, tab, slots, c.ax_partials); break;
+    case 24: hipLaunchKernelGGL((k_mm_dots<24>), dim3(1), dim3(VB), 0, c.stream, tab, slots, c.ax_partials); break;
+    default: return LCG_HIP_E_ARG;
+    }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(c.scratch_host, c.ax_partials, sizeof(double) * ns, hipMemcpyDeviceToHost, c.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c.stream);

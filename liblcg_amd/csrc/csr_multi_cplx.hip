@@ -1,4 +1,5 @@
-// csr_multi_cplx.hip -- Y = A.X for k = 2, 4, 8 complex vectors at once (complex128 CSR, one GPU): clcg_hip_spmm, clcg_hip_spmm_dot.
+// csr_multi_cplx.hip -- Y = A.X for k = 2, 4, 8 complex vectors at once (complex128 CSR, one GPU): clcg_hip_spmm, clcg_hip_spmm_dot,
+// clcg_hip_spmm_inner, clcg_hip_spmm_dot2.
 //
 // A complex entry costs 20 bytes (4 B column + 16 B value) and the single-vector complex product has nothing cheaper to offer: k
 // vectors interleaved row by row (multi_cplx.hpp) share ONE pass over col / val, and every gather of x fetches k * 16 contiguous bytes.
@@ -11,12 +12,18 @@
 //      four columns, 256 x 8 x 16 B do not fit it); Y is written as whole rows.
 //      Column j's sum is therefore added in an order fixed by the matrix alone: the same bits whatever the other columns hold, whatever
 //      k is, from call to call.  No atomics.
-//      <DOT>: the lanes that write Y multiply it with U (unconjugated: clcg_dot, cublasZdotu) on the way out and the block leaves one
-//      partial sum per column and component (more than MM_MG blocks: k_mm_fold adds runs of consecutive blocks, in order).
+//      <MODE>: the lanes that write Y multiply it on the way out and the block leaves one partial sum per column and component (more
+//      than MM_MG blocks: k_mm_fold adds runs of consecutive blocks, in order).  Mapping, windows, the order of the row sums and the
+//      bits of Y are the same in every mode.
+//        CSPMM_DOT    with the block U, unconjugated (clcg_dot, cublasZdotu): what BiCG-sym and PCG take (d.Ad);
+//        CSPMM_INNER  conj(u_i) Y_ij with ONE vector u of n elements for all columns, 16 bytes per row: BiCGStab's <rbar0, A.p>;
+//        CSPMM_DOT2   conj(Y_ij) U_ij with the block U and, as a third, real sum, |Y_ij|^2: BiCGStab's <A.s, s> and <A.s, A.s>.
+//      The conjugated products are formed as acc_inner forms them (solvers_cplx.hip).
 //
-// The host side is multi.hpp's frame (csr_multi.hip: multi_launch, multi_dot_run) with two table rows per column; this unit adds the
-// kernel, its launcher and the handle's check.  The handle's single-vector plans are neither used nor built.
+// The host side is multi.hpp's frame (csr_multi.hip: multi_launch, multi_dot_run) with two table rows per column (CSPMM_DOT2: three);
+// this unit adds the kernel, its launcher and the handle's check.  The handle's single-vector plans are neither used nor built.
 #include "multi_cplx.hpp"
+#include "lcg_hip_staging.h"
 
 namespace lcgh {
 
@@ -30,7 +37,7 @@ __device__ __forceinline__ m2d cmac(m2d a, m2d x, m2d acc)     // a * x + acc, c
     return r;
 }
 
-template <int K, int R, bool DOT>
+template <int K, int R, int MODE>     // MODE: 0, or multi_cplx.hpp's CSPMM_DOT, CSPMM_INNER, CSPMM_DOT2
 __global__ __launch_bounds__(VB) void k_cspmm(int n, const int *__restrict__ rowptr, const int *__restrict__ col,
                                               const double *__restrict__ val, const double *__restrict__ X, double *__restrict__ Y,
                                               const int *done, bool wide, const double *__restrict__ U, double *__restrict__ part,
@@ -124,7 +131,9 @@ __global__ __launch_bounds__(VB) void k_cspmm(int n, const int *__restrict__ row
         __syncthreads();
     }
     // the T partial sums of a row meet in LDS (the value window reused; [column][slot][row]: consecutive lanes, consecutive 16 bytes)
-    double dre[K], dim[K];
+    double dre[K], dim[K], dsq[K];
+    m2d us = (m2d)(0.0);                                    // CSPMM_INNER: the shared vector's element of this row, read once
+    if (MODE == CSPMM_INNER && mine) us = reinterpret_cast<const m2d *>(U)[row0 + rl];
 #pragma unroll
     for (int h0 = 0; h0 < K; h0 += XC) {
 #pragma unroll
@@ -136,27 +145,43 @@ __global__ __launch_bounds__(VB) void k_cspmm(int n, const int *__restrict__ row
                 m2d v = sval[(h * T) * R + rl];
                 for (int j = 1; j < T; j++) v += sval[(h * T + j) * R + rl];
                 reinterpret_cast<m2d *>(Y)[(long)(row0 + rl) * K + h0 + h] = v;
-                if (DOT) {
+                if (MODE == CSPMM_DOT) {
                     const m2d u = reinterpret_cast<const m2d *>(U)[(long)(row0 + rl) * K + h0 + h];
                     dre[h0 + h] = v.x * u.x - v.y * u.y; dim[h0 + h] = v.x * u.y + v.y * u.x;
                 }
+                if (MODE == CSPMM_INNER) {                  // conj(u) y: acc_inner's products (solvers_cplx.hip)
+                    dre[h0 + h] = us.x * v.x + us.y * v.y; dim[h0 + h] = us.x * v.y - us.y * v.x;
+                }
+                if (MODE == CSPMM_DOT2) {                   // conj(y) u the same way, and |y|^2 (cnorm)
+                    const m2d u = reinterpret_cast<const m2d *>(U)[(long)(row0 + rl) * K + h0 + h];
+                    dre[h0 + h] = v.x * u.x + v.y * u.y; dim[h0 + h] = v.x * u.y - v.y * u.x;
+                    dsq[h0 + h] = v.x * v.x + v.y * v.y;
+                }
             }
-        } else if (DOT) {
+        } else if (MODE) {
 #pragma unroll
-            for (int h = 0; h < XC; h++) { dre[h0 + h] = 0.0; dim[h0 + h] = 0.0; }
+            for (int h = 0; h < XC; h++) { dre[h0 + h] = 0.0; dim[h0 + h] = 0.0; dsq[h0 + h] = 0.0; }
         }
         if (h0 + XC < K) __syncthreads();
     }
-    if (DOT && tid < 64) {
+    if (MODE && tid < 64) {
 #pragma unroll
         for (int j = 0; j < K; j++) {
             const double tr = wave_sum(dre[j]), ti = wave_sum(dim[j]);
             if (tid == WSUM_LANE) { part[(size_t)(2 * j) * pstride + blockIdx.x] = tr; part[(size_t)(2 * j + 1) * pstride + blockIdx.x] = ti; }
         }
     }
+    if (MODE == CSPMM_DOT2 && tid < 64) {
+#pragma unroll
+        for (int j = 0; j < K; j++) {
+            const double tq = wave_sum(dsq[j]);
+            if (tid == WSUM_LANE) part[(size_t)(2 * K + j) * pstride + blockIdx.x] = tq;
+        }
+    }
 }
 
-// k_cspmm<k, R, DOT> for multi.hpp's frame (two table rows per column: `tab` is not looked at)
+// k_cspmm<k, R, MODE> for multi.hpp's frame (`tab` is not looked at: MODE fixes the table rows per column); without U the plain product
+template <int MODE>
 static void cspmm_go(const CsrPart &P, int k, int R, const double *X, double *Y, hipStream_t s, const int *done, bool wide, const double *U,
                      double *part, int pstride, int)
 {
@@ -164,17 +189,18 @@ static void cspmm_go(const CsrPart &P, int k, int R, const double *X, double *Y,
         return multi_r(R, [&](auto RR) {
             constexpr int KK = decltype(K)::value, RV = decltype(RR)::value;
             const unsigned nb = (unsigned)(((long)P.n_rows + RV - 1) / RV);
-            if (U) hipLaunchKernelGGL((k_cspmm<KK, RV, true>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
-            else hipLaunchKernelGGL((k_cspmm<KK, RV, false>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
+            if (U) hipLaunchKernelGGL((k_cspmm<KK, RV, MODE>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
+            else hipLaunchKernelGGL((k_cspmm<KK, RV, 0>), dim3(nb), dim3(VB), 0, s, P.n_rows, P.rowptr, P.col, P.val, X, Y, done, wide, U, part, pstride);
             return 0;
         });
     });
 }
+static MultiGo cspmm_go_of(int mode) { return mode == CSPMM_INNER ? cspmm_go<CSPMM_INNER> : mode == CSPMM_DOT2 ? cspmm_go<CSPMM_DOT2> : cspmm_go<CSPMM_DOT>; }
 
 int cspmm_launch(const CsrPart &P, int k, const double *X, double *Y, hipStream_t s, const int *done, const double *U, double *big,
-                 double *dots, int *slots)
+                 double *dots, int *slots, int mode)
 {
-    return multi_launch(P, k, 2, cspmm_go, X, Y, s, done, U, big, dots, slots);
+    return multi_launch(P, k, cspmm_tab(mode), cspmm_go_of(mode), X, Y, s, done, U, big, dots, slots);
 }
 
 int cmulti_handle(const char *entry, const lcg_hip_csr *A)
@@ -213,7 +239,27 @@ int clcg_hip_spmm_dot(lcg_hip_csr_t A, int k, const double *X, double *Y, const 
     TRY(multi_args(entry, k, X, Y, U));
     if (!dots) { ctx().err = std::string(entry) + ": the result array is a null pointer"; return LCG_HIP_E_ARG; }
     TRY(cmulti_handle(entry, A));
-    return multi_dot_run(A->main, k, 2, cspmm_go, X, Y, U, dots);
+    return multi_dot_run(A->main, k, 2, cspmm_go<CSPMM_DOT>, X, Y, U, dots);
+}
+
+int clcg_hip_spmm_inner(lcg_hip_csr_t A, int k, const double *X, double *Y, const double *u, double *dots)
+{
+    static const char *entry = "clcg_hip_spmm_inner";
+    NOT_DENSE(A, LCG_HIP_E_ARG);
+    TRY(multi_args(entry, k, X, Y, u));
+    if (!dots) { ctx().err = std::string(entry) + ": the result array is a null pointer"; return LCG_HIP_E_ARG; }
+    TRY(cmulti_handle(entry, A));
+    return multi_dot_run(A->main, k, 2, cspmm_go<CSPMM_INNER>, X, Y, u, dots);
+}
+
+int clcg_hip_spmm_dot2(lcg_hip_csr_t A, int k, const double *X, double *Y, const double *U, double *dots3)
+{
+    static const char *entry = "clcg_hip_spmm_dot2";
+    NOT_DENSE(A, LCG_HIP_E_ARG);
+    TRY(multi_args(entry, k, X, Y, U));
+    if (!dots3) { ctx().err = std::string(entry) + ": the result array is a null pointer"; return LCG_HIP_E_ARG; }
+    TRY(cmulti_handle(entry, A));
+    return multi_dot_run(A->main, k, 3, cspmm_go<CSPMM_DOT2>, X, Y, U, dots3);
 }
 
 } // extern "C"

@@ -41,7 +41,7 @@ template <class F> int multi_r(int R, F f)
 // The frame of the k-wide CSR products, real and complex (csr_multi.hip).  `go` launches the product kernel for R rows per block:
 // Y = A.X for the k columns in one launch (P's plain CSR arrays: no plan is built or used) and, with U, one partial sum per block
 // and table row at part[row * pstride + block].  A column owns `tab` table rows: 1 (real: (A.X)_j . U_j), 2 (real with dot2: besides it
-// (A.X)_j . (A.X)_j in rows k ..; complex: re, im of the unconjugated sum in rows 2 j, 2 j + 1).  multi_launch leaves every row's sum
+// (A.X)_j . (A.X)_j in rows k ..; complex: re, im of one sum in rows 2 j, 2 j + 1), 3 (complex with a real second sum in rows 2 k ..: multi_cplx.hpp).  multi_launch leaves every row's sum
 // as *slots <= MM_MG partial sums at dots[row * MM_MG ...], to be added in index order; `big` holds the per-block sums of a matrix with
 // more than MM_MG row blocks on their way there (multi_big_doubles(P, tab * k) doubles; may be null where that is 0).
 typedef void (*MultiGo)(const CsrPart &P, int k, int R, const double *X, double *Y, hipStream_t s, const int *done, bool wide,
@@ -55,7 +55,7 @@ int multi_dot_run(const CsrPart &P, int k, int tab, MultiGo go, const double *X,
 // sums per row it leaves
 int multi_fold_launch(const double *big, int nb, int ns, double *out, hipStream_t s);
 // dots[0 .. ns) = the ns running sums of the loops' table c.partials_pair[0], `slots` partial sums each, added by msum (ns = 2, 4, 8,
-// 16): launch, copy to the host, wait.  0, or the failure's code
+// 16; 6, 12, 24 with three table rows per column): launch, copy to the host, wait.  0, or the failure's code
 int multi_dots_read(Ctx &c, int ns, int slots, double *dots);
 
 // the real product: with U column j's (A.X)_j . U_j, with dot2 besides it (A.X)_j . (A.X)_j, the first sum's bits unchanged

@@ -13,6 +13,7 @@
 #include <functional>
 
 #include "driver.hpp"
+#include "multi_cplx.hpp"
 
 namespace lcgh {
 
@@ -535,8 +536,9 @@ static int ccheck_args(const clcg_para &p, int n, const double *m, const double 
 
 using ClxSolve = Solve<true>;
 
-// rbar0 in [1,2] + 0i: lcg_complex.cpp:118-127 with an explicit seed; or the caller's vector
-static int make_shadow(Ctx &c, int n, double *dev)
+// rbar0 in [1,2] + 0i: lcg_complex.cpp:118-127 with an explicit seed; or the caller's vector (declared in multi_cplx.hpp: the batched
+// BiCGStab draws the same one)
+int make_shadow(Ctx &c, int n, double *dev)
 {
     std::vector<double> h(2 * (size_t)n);
     if (c.shadow_vec.size() == h.size()) { h = c.shadow_vec; c.shadow_vec.clear(); }

@@ -38,66 +38,9 @@
 namespace lcgh {
 namespace {
 
-struct ZMState : MultiHead {
-    double ak[2 * MM_MAXK], bk[2 * MM_MAXK], rho[2 * MM_MAXK];      // complex: re at [2 j], im at [2 j + 1]; rho = r.r (PCG: r.s)
-    double m2[MM_MAXK], r2[MM_MAXK], residual[MM_MAXK];              // sum |m|^2, sum |r|^2 as they were last added up
-};
+// ZMState, the z-helpers, zm_residual, the setup step ZMFinInit and the first step ZMFinAlpha: multi_cplx.hpp (solvers_multi_cbicg.hip
+// runs them too)
 
-__device__ __forceinline__ m2d zmul(m2d a, m2d b) { m2d r; r.x = a.x * b.x - a.y * b.y; r.y = a.x * b.y + a.y * b.x; return r; }
-__device__ __forceinline__ m2d zfma(m2d a, m2d b, m2d c)     // a * b + c, cfma's order (devcommon.hpp)
-{
-    m2d r; r.x = fma(a.x, b.x, fma(-a.y, b.y, c.x)); r.y = fma(a.x, b.y, fma(a.y, b.x, c.y)); return r;
-}
-__device__ __forceinline__ m2d znorms(m2d a, m2d b) { m2d r; r.x = a.x * a.x + a.y * a.y; r.y = b.x * b.x + b.y * b.y; return r; }
-__device__ __forceinline__ void zst(double *p, long e, m2d v) { reinterpret_cast<m2d *>(p)[e] = v; }
-
-// ---- scalar steps: sum[(s * K + j) * 2 + c] ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ double2 zld(const double *p, int j) { return make_double2(p[2 * j], p[2 * j + 1]); }
-__device__ __forceinline__ void zsts(double *p, int j, double2 v) { p[2 * j] = v.x; p[2 * j + 1] = v.y; }
-// the residual of the loop's stop rule out of sum |r|^2 and sum |m|^2
-template <bool PCG> __device__ __forceinline__ double zm_residual(const ZMState *st, double r2, double mm)
-{
-    if (PCG) return st->abs_diff ? sqrt(r2) / st->n_global : r2 / clamp1(mm);               // clcg_cuda.cu:459,472,478
-    const double m4 = clamp1(mm * mm), r4 = r2 * r2;                                        // clcg.cpp:262-270
-    return st->abs_diff ? sqrt(r4) / st->n_global : r4 / m4;                                // clcg.cpp:295-296
-}
-
-// setup.  Sums |m|^2, |r|^2, rho (BiCG-sym: r.r; PCG: r.s).  BiCG-sym tries BOTH "already optimised" criteria in abs_diff mode, in the
-// reference's order (clcg.cpp:273-290); PCG only its mode's own (clcg_cuda.cu:456-466)
-template <int K, bool PCG> struct ZMFinInit {
-    static constexpr int NS = 4;
-    __device__ void operator()(ZMState *st, const double *sum) const
-    {
-#pragma unroll
-        for (int j = 0; j < K; j++) {
-            const double mm = sum[2 * j], r2 = sum[2 * j + 1];
-            st->m2[j] = mm; st->r2[j] = r2;
-            zsts(st->rho, j, make_double2(sum[(K + j) * 2], sum[(K + j) * 2 + 1]));
-            double r = zm_residual<PCG>(st, r2, mm);
-            bool already = r <= st->eps;
-            if (!PCG && !already && st->abs_diff) {
-                const double rel = (r2 * r2) / clamp1(mm * mm);
-                if (rel <= st->eps) { r = rel; already = true; }
-            }
-            st->residual[j] = r;
-            st->stop[j] = already ? ST_ALREADY : ST_RUNNING;
-        }
-        all_stopped<K>(st);
-        mpublish(st);
-    }
-};
-// first step of a body: counts it; ak = rho / d.Ad per running column (clcg.cpp:320-321, clcg_cuda.cu:501-502).  Sums: the product's
-template <int K> struct ZMFinAlpha {
-    static constexpr int NS = 2;
-    __device__ void operator()(ZMState *st, const double *sum) const
-    {
-        st->it++;
-        if (st->all_done) return;
-#pragma unroll
-        for (int j = 0; j < K; j++)
-            if (st->stop[j] == ST_RUNNING) zsts(st->ak, j, cdiv(zld(st->rho, j), make_double2(sum[2 * j], sum[2 * j + 1])));
-    }
-};
 // closing step of a body, per running column (clcg.cpp:330-347 and the next loop head :295-318; clcg_cuda.cu:507-517, :478-480)
 template <int K, bool PCG> struct ZMFinClose {
     static constexpr int NS = 4;
@@ -159,17 +102,7 @@ struct ZMOpDir {        // d = z + bk d (z: r, PCG: s)                          
     __device__ void apply(long e, long, bool, bool, m2d *) { zst(d, e, zfma(bk, ld2(d, e), ld2(z, e))); }
 };
 
-// ---- host side ------------------------------------------------------------------------------------------------------------------------
-inline int zm_code(int stop)
-{
-    switch (stop) {
-    case ST_ALREADY: return CLCG_ALREADY_OPTIMIZIED;
-    case ST_NAN: return CLCG_NAN_VALUE;
-    case ST_CONVERGED: return CLCG_CONVERGENCE;
-    default: return LCG_REACHED_MAX_ITERATIONS;     // (-1019 from the real enum, as the complex loops return at the cap: SURVEY quirk 5)
-    }
-}
-
+// ---- host side (a column's stop word -> its code: zm_code, multi_cplx.hpp) ------------------------------------------------------------
 // ---- the matrix, as the loop sees it (solvers_multi.hip's seam) ------------------------------------------------------------------------
 // rows(), invdiag() (the complex Jacobi reciprocals), big_doubles(k) (what the product's carried sum needs on its way to the table)
 // and apply(): Y = A.X for the K columns and, with U, column j's unconjugated (A.X)_j . U_j as *slots partial sums in `dots`, re in row
