@@ -237,6 +237,13 @@ class CsrMatrix:
         k = _block_k(X, Y)
         _chk(L.load().lcg_hip_ic0_solve_multi(self.h, k, which, _ptr(X)[0], _ptr(Y)[0]), "ic0_solve_multi")
 
+    def ic0_solve_multi_c64(self, X, Y, which=2):
+        """ic0_solve of a complex64 matrix for the k = 2, 4 or 8 columns of X at once (clcg_hip_ic0_solve_multi_c64): X, Y (n, k)
+        C-contiguous complex64 CUDA tensors, 16-byte aligned.  Column j has the bits of ic0_solve on column j; the fp32 factor
+        is read once for all of them."""
+        k = _block_k(X, Y, cplx="c64")
+        _chk(L.load().clcg_hip_ic0_solve_multi_c64(self.h, k, which, _ptr(X)[0], _ptr(Y)[0]), "ic0_solve_multi_c64")
+
     # -- ILU(0) preconditioner (csr_ilu0.hip) -----------------------------------------------
     def build_ilu0(self):
         """Factor A ~ L.U (unit lower L) with zero fill on the device, fp64 and complex128 matrices; pass "lcg_hip_ilu0_mx" /
@@ -695,10 +702,15 @@ def clbicg_sym_multi_c64(A, M, B, param) -> list:
     return _multi("clcg_hip_lbicg_sym_multi_c64", A, M, B, param, cplx="c64")
 
 
-def clpcg_multi_c64(A, M, B, param) -> list:
-    """Batched complex64 PCG with the handle's Jacobi diagonal (clcg_hip_lpcg_multi_c64; A.build_jacobi() first).  As
-    clbicg_sym_multi_c64."""
-    return _multi("clcg_hip_lpcg_multi_c64", A, M, B, param, cplx="c64")
+def clpcg_multi_c64(A, M, B, param, precond="jacobi") -> list:
+    """Batched complex64 PCG.  precond "jacobi": the handle's Jacobi diagonal (clcg_hip_lpcg_multi_c64; A.build_jacobi() first);
+    "ic0": the handle's fp32 IC(0) factor (A.build_ic0() first) applied to all columns at once at its sweeps setting
+    (clcg_hip_lpcg_multi_m_c64).  As clbicg_sym_multi_c64."""
+    if precond not in ("jacobi", "ic0"):
+        raise ValueError('precond is "jacobi" or "ic0"')
+    if precond == "jacobi":
+        return _multi("clcg_hip_lpcg_multi_c64", A, M, B, param, cplx="c64")
+    return _multi("clcg_hip_lpcg_multi_m_c64", A, M, B, param, PRECONDS[precond], cplx="c64")
 
 
 def dense_clbicg_sym_multi(K, M, B, param) -> list:

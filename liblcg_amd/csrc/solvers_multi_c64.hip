@@ -30,10 +30,15 @@
 // s * K + j.  A complex sum takes two accumulators (re, im); a scalar step reads sum[s * K + j].  The product's d.Ad lies in the
 // complex frame's order instead: rows 2 j, 2 j + 1.
 //
+// clcg_hip_lpcg_multi_m_c64 with LCG_HIP_M_IC0: the multiply leaves the update pass, as in solvers_multi.hip:
+//     A.d carrying d.Ad  |  [ak] m += ak d; r -= ak Ad  |  s = (L.L^T)^-1 r (the k-wide apply's launches)  |  |m|^2, |r|^2, r.s  |  [close] d = s + bk d
+// The apply forms s for every column, stopped ones too (nothing reads theirs: s is scratch); every one of its launches honours all_done.
+//
 // Kernel functors carry a C64M prefix: k_mvecf is instantiated per translation unit (tests/test_abi.py).
 #include "c64common.hpp"
 #include "multi_loop.hpp"
 #include "multi_c64.hpp"
+#include "lcg_hip_staging_ic0_c64.h"
 
 namespace lcgh {
 namespace {
@@ -188,6 +193,48 @@ struct C64MOpDir {      // d = bk d + z (z: r, PCG: s)   (Cscal + Caxpy: :381-38
     }
 };
 
+// a factor as M (IC(0), applied k wide by csr_tri_multi.hip): the update and the sums are two passes with the apply's launches between them
+struct C64MOpFRes {     // r = B - Ad
+    static constexpr int NS = 0;
+    const float *Ad, *B; float *r;
+    __device__ void prep(const C64MState &, int) {}
+    __device__ void apply(long e, long, bool r0, bool r1, m2d *)
+    {
+        const float2 m1 = make_float2(-1.f, 0.f);
+        const c64v4 av = c64m_ld(Ad, e), bv = c64m_ld(B, e);
+        c64m_st(r, e, c64m_join(c64m_axpy(m1, c64m_lo(av), c64m_lo(bv)), c64m_axpy(m1, c64m_hi(av), c64m_hi(bv))), r0, r1);
+    }
+};
+struct C64MOpFInit {    // d = z; |m|^2, |r|^2, r.z
+    static constexpr int NS = 4;
+    const float *m, *r, *z; float *d;
+    __device__ void prep(const C64MState &, int) {}
+    __device__ void apply(long e, long, bool r0, bool r1, m2d *acc)
+    {
+        const c64v4 zv = c64m_ld(z, e);
+        c64m_st(d, e, zv, r0, r1);
+        c64m_sums(acc, c64m_ld(m, e), c64m_ld(r, e), zv);
+    }
+};
+struct C64MOpFUpdate {  // m += ak d; r -= ak Ad
+    static constexpr int NS = 0;
+    float *m, *r; const float *d, *Ad; float2 ak0, ak1;
+    __device__ void prep(const C64MState &L, int c) { ak0 = c64m_get(L.ak, c); ak1 = c64m_get(L.ak, c + 1); }
+    __device__ void apply(long e, long, bool r0, bool r1, m2d *)
+    {
+        const c64v4 dv = c64m_ld(d, e), av = c64m_ld(Ad, e), mo = c64m_ld(m, e), ro = c64m_ld(r, e);
+        const float2 n0 = make_float2(-ak0.x, -ak0.y), n1 = make_float2(-ak1.x, -ak1.y);
+        c64m_st(m, e, c64m_join(c64m_axpy(ak0, c64m_lo(dv), c64m_lo(mo)), c64m_axpy(ak1, c64m_hi(dv), c64m_hi(mo))), r0, r1);
+        c64m_st(r, e, c64m_join(c64m_axpy(n0, c64m_lo(av), c64m_lo(ro)), c64m_axpy(n1, c64m_hi(av), c64m_hi(ro))), r0, r1);
+    }
+};
+struct C64MOpFSums {    // |m|^2, |r|^2, r.s
+    static constexpr int NS = 4;
+    const float *m, *r, *s;
+    __device__ void prep(const C64MState &, int) {}
+    __device__ void apply(long e, long, bool, bool, m2d *acc) { c64m_sums(acc, c64m_ld(m, e), c64m_ld(r, e), c64m_ld(s, e)); }
+};
+
 // ---- host side --------------------------------------------------------------------------------------------------------------------------
 inline int c64m_code(int stop)
 {
@@ -199,8 +246,9 @@ inline int c64m_code(int stop)
     }
 }
 
+// F: the complex64 IC(0) factor that is M (PCG only; its k-wide work vectors reserved by the caller), nullptr: the Jacobi reciprocals inv
 template <int K, bool PCG>
-static int run_c64m(lcg_hip_csr *A, const float *inv, float *M, const float *B, const clcg_para &p, int *ret, int *iterations,
+static int run_c64m(lcg_hip_csr *A, const float *inv, const TriFactor *F, float *M, const float *B, const clcg_para &p, int *ret, int *iterations,
                     double *residual, int mem)
 {
     MultiFrame<C64MState, K, K / 2> f(A->n_rows);
@@ -228,13 +276,28 @@ static int run_c64m(lcg_hip_csr *A, const float *inv, float *M, const float *B, 
 
     // setup: A.m for the guess, d = r (PCG: inv .* r), the verdict "already optimised"
     TRY(product(M, Ad, nullptr, nullptr, nullptr, nullptr));
-    TRY((f.template pass<1, true>(MFinNone{}, C64MOpInit<PCG>{Ad, B, M, inv, r, d}, nullptr, 0)));
+    const int m_launches = PCG && F ? tri_apply_launches(F, 2) : 0;         // counted as vector passes (lcg_hip_last_launches)
+    auto factor = [&](const int *done) -> int {                              // s = (L.L^T)^-1 r for all K columns
+        c.cnt_vec += m_launches;
+        return tri_apply_multi(F, K, 2, reinterpret_cast<const double *>(r), reinterpret_cast<double *>(s), c.stream, done);
+    };
+    if (PCG && F) {
+        TRY((f.template pass<0, true>(MFinNone{}, C64MOpFRes{Ad, B, r}, nullptr, 0)));
+        TRY(factor(nullptr));
+        TRY((f.template pass<1, true>(MFinNone{}, C64MOpFInit{M, r, s, d}, nullptr, 0)));
+    } else
+        TRY((f.template pass<1, true>(MFinNone{}, C64MOpInit<PCG>{Ad, B, M, inv, r, d}, nullptr, 0)));
     TRY((f.template pass<3, true>(C64MFinInit<K>{}, MOpNone{}, f.tab_sum, f.grid, 1)));
 
     int g_dot = 0;
     f.run(p.max_iterations, [&]() -> int {
         TRY(product(d, Ad, &f.cur->all_done, d, f.tab_dot, &g_dot));
-        TRY(f.template pass<1>(C64MFinAlpha<K>{}, C64MOpUpdate<PCG>{M, r, s, d, Ad, inv, float2(), float2()}, f.tab_dot, g_dot));
+        if (PCG && F) {
+            TRY(f.template pass<0>(C64MFinAlpha<K>{}, C64MOpFUpdate{M, r, d, Ad, float2(), float2()}, f.tab_dot, g_dot));
+            TRY(factor(&f.cur->all_done));
+            TRY(f.template pass<1>(MFinNone{}, C64MOpFSums{M, r, s}, nullptr, 0));
+        } else
+            TRY(f.template pass<1>(C64MFinAlpha<K>{}, C64MOpUpdate<PCG>{M, r, s, d, Ad, inv, float2(), float2()}, f.tab_dot, g_dot));
         TRY(f.template pass<3>(C64MFinClose<K>{}, C64MOpDir{d, PCG ? s : r, float2(), float2()}, f.tab_sum, f.grid));
         return 0;
     });
@@ -253,7 +316,26 @@ static int c64m_entry(const char *entry, lcg_hip_csr *A, int k, float *M, const 
     const float *inv = PCG ? c64_builtin_invdiag((const void *)clcg_hip_jacobi_mx_c64, A, A->n_rows) : nullptr;
     if (PCG && inv == nullptr) return LCG_NULL_PRECONDITION_MATRIX;     // lcg_hip_csr_build_jacobi has not run
     TRY(ensure_init());
-    return multi_k(k, [&](auto K) { return run_c64m<decltype(K)::value, PCG>(A, inv, M, B, p, ret, iterations, residual, mem); });
+    return multi_k(k, [&](auto K) { return run_c64m<decltype(K)::value, PCG>(A, inv, nullptr, M, B, p, ret, iterations, residual, mem); });
+}
+
+// precond: LCG_HIP_M_JACOBI (clcg_hip_lpcg_multi_c64 itself) or LCG_HIP_M_IC0 (the handle's complex64 factor)
+static int c64m_entry_m(const char *entry, lcg_hip_csr *A, int k, int precond, float *M, const float *B, const clcg_para *param, int *ret,
+                        int *iterations, double *residual, int mem)
+{
+    clcg_para p;
+    TRY(multi_args(entry, k, M, B));
+    TRY(c64multi_handle(entry, A));
+    TRY(multi_shape(entry, A->n_rows == A->n_cols, mem));
+    if (precond != LCG_HIP_M_JACOBI && precond != LCG_HIP_M_IC0)
+        return arg_error("%s: precond = %d is neither LCG_HIP_M_JACOBI nor LCG_HIP_M_IC0 (there is no complex64 ILU(0), and PCG needs an M)", entry, precond);
+    if (precond == LCG_HIP_M_JACOBI) return c64m_entry<true>(entry, A, k, M, B, param, ret, iterations, residual, mem);
+    TRY(multi_para<true>(param, p, A->n_rows));
+    TriFactor *F = A->ic0;
+    if (!F || !F->ok || !F->c64) return LCG_NULL_PRECONDITION_MATRIX;   // lcg_hip_csr_build_ic0_c64 has not run (or its pivot failed)
+    TRY(ensure_init());
+    TRY(tri_multi_reserve(F, k, 2));
+    return multi_k(k, [&](auto K) { return run_c64m<decltype(K)::value, true>(A, nullptr, F, M, B, p, ret, iterations, residual, mem); });
 }
 
 } // namespace
@@ -275,6 +357,13 @@ int clcg_hip_lpcg_multi_c64(lcg_hip_csr_t A, int k, float *M, const float *B, co
 {
     NOT_DENSE(A, LCG_HIP_E_ARG);
     return c64m_entry<true>("clcg_hip_lpcg_multi_c64", A, k, M, B, param, ret, iterations, residual, mem);
+}
+
+int clcg_hip_lpcg_multi_m_c64(lcg_hip_csr_t A, int k, int precond, float *M, const float *B, const clcg_para *param, int *ret,
+                              int *iterations, double *residual, int mem)
+{
+    NOT_DENSE(A, LCG_HIP_E_ARG);
+    return c64m_entry_m("clcg_hip_lpcg_multi_m_c64", A, k, precond, M, B, param, ret, iterations, residual, mem);
 }
 
 } // extern "C"
