@@ -1,4 +1,4 @@
-"""ctypes view of the C ABI in ``include/lcg_hip.h``, ``include/lcg_hip_staging.h`` and ``include/lcg_hip_staging_ic0_c64.h`` (liblcg_amd/lib/liblcg_hip.so).
+"""ctypes view of the C ABI in ``include/lcg_hip.h``, ``include/lcg_hip_staging.h``, ``include/lcg_hip_staging_ic0_c64.h`` and ``include/lcg_hip_staging_box_multi.h`` (liblcg_amd/lib/liblcg_hip.so).
 
 No compute happens in Python: every function here forwards to the HIP library.  If the
 shared object is missing the import fails loudly -- there is no fallback path.
@@ -231,6 +231,13 @@ STAGING_IC0_C64_SIGNATURES = {
     "clcg_hip_lpcg_multi_m_c64": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.POINTER(ClcgPara), c_int_p, c_int_p, c_double_p, C.c_int]),
 }
 
+# every symbol include/lcg_hip_staging_box_multi.h declares: the batched box-constrained entries (that header says why they have a
+# file and a dict of their own)
+STAGING_BOX_MULTI_SIGNATURES = {
+    "lcg_hip_solver_constrained_multi": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(LcgPara), c_int_p, c_int_p, c_int_p, c_double_p, C.c_int]),
+    "lcg_hip_dense_solver_constrained_multi": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(LcgPara), c_int_p, c_int_p, c_int_p, c_double_p, C.c_int]),
+}
+
 _lib = None
 
 
@@ -259,7 +266,7 @@ def load():
     # the SAME runtime objects instead of mapping a second HIP runtime into the process.
     import torch  # noqa: F401
     lib = C.CDLL(SO_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in {**SIGNATURES, **STAGING_SIGNATURES, **STAGING_IC0_C64_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **STAGING_SIGNATURES, **STAGING_IC0_C64_SIGNATURES, **STAGING_BOX_MULTI_SIGNATURES}.items():
         fn = getattr(lib, name)     # AttributeError = header/library drift: fail loudly
         fn.restype = res
         fn.argtypes = args

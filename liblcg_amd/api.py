@@ -662,6 +662,43 @@ def dense_lpcg_multi(K, M, B, param, normal=True) -> list:
     return _multi("lcg_hip_dense_lpcg_multi", K, M, B, param, int(normal))
 
 
+@dataclass
+class BoxSolveInfo(SolveInfo):
+    products: int       # A.x calls the reference would have made for this column alone: 1 + its trial points
+
+
+def _box_multi(name, lead, M, B, low, hig, param, solver_id):
+    lib = L.load()
+    k = _block_k(M, B)
+    if tuple(M.shape) != tuple(B.shape):
+        raise ValueError("M and B must have the same shape")
+    (pm, mem), (pb, mem_b), (pl, mem_l), (ph, mem_h) = _ptr(M), _ptr(B), _ptr(low), _ptr(hig)
+    if not mem == mem_b == mem_l == mem_h:
+        raise ValueError("M, B, low and hig must live in the same memory space")
+    if int(low.shape[0]) != int(M.shape[0]) or int(hig.shape[0]) != int(M.shape[0]):
+        raise ValueError("low and hig are vectors of n = M.shape[0] elements")
+    ret = (C.c_int * k)(); its = (C.c_int * k)(); prods = (C.c_int * k)(); res = (C.c_double * k)()
+    rc = getattr(lib, name)(*lead, solver_id, pm, pb, pl, ph, C.byref(param) if param is not None else None, ret, its, prods, res, mem)
+    _chk(rc, name)
+    if rc:
+        raise LcgHipError(f"{name}: rc={rc}")
+    return [BoxSolveInfo(ret[j], its[j], res[j], prods[j]) for j in range(k)]
+
+
+def lcg_solver_constrained_multi(A, M, B, low, hig, param, solver_id=LCG_PG) -> list:
+    """Batched box-constrained solve (lcg_hip_solver_constrained_multi): LCG_PG / LCG_SPG per column as lcg_solver_constrained
+    runs them, for the k = 2, 4 or 8 columns of the (n, k) blocks M (in/out) and B; low, hig: one vector of n bounds each, shared by
+    all columns.  The matrix is read once per trial step for all columns and the line search runs on the device.  Returns one
+    BoxSolveInfo per column: ret, iterations, residual and products."""
+    return _box_multi("lcg_hip_solver_constrained_multi", (_instance(A), _block_k(M, B)), M, B, low, hig, param, solver_id)
+
+
+def dense_solver_constrained_multi(K, M, B, low, hig, param, solver_id=LCG_PG, normal=True) -> list:
+    """Batched box-constrained solve on a dense matrix (lcg_hip_dense_solver_constrained_multi): the operator is K^T.K (normal)
+    or K (square).  As lcg_solver_constrained_multi."""
+    return _box_multi("lcg_hip_dense_solver_constrained_multi", (_instance(K), _block_k(M, B), int(normal)), M, B, low, hig, param, solver_id)
+
+
 def lbicgstab_multi(A, M, B, param, precond=None) -> list:
     """Batched BiCGStab for a square real matrix, symmetric or not (lcg_hip_lbicgstab_multi).  precond None: plain; "jacobi",
     "ic0", "ilu0": right-preconditioned in x-space with the handle's diagonal or factor (built first) applied to all columns at

@@ -1,7 +1,7 @@
 // solvers_multi.hip -- batched CG and PCG over k = 2, 4, 8 right-hand sides: lcg_hip_lcg_multi, lcg_hip_lpcg_multi (the built-in
 // Jacobi), lcg_hip_lpcg_multi_m (Jacobi, or the handle's IC(0) / ILU(0) factor applied k wide: csr_tri_multi.hip), and the same loop
 // on a dense handle's K^T.K or K: lcg_hip_dense_lcg_multi, lcg_hip_dense_lpcg_multi (dense_multi.hip).  The loop reaches the matrix
-// through a small operator argument (CsrOp, DenseOp below).
+// through a small operator argument (CsrOp, DenseOp: multi_ops.hpp).
 //
 // Each column runs the reference's own recurrence as if it were alone (lcg.cpp:143-274, 293-434): its own alpha, beta, rho, its own
 // residual under the same stop rule, its own "already optimised" test, NaN scan, count and return code.  What the columns share is
@@ -27,9 +27,7 @@
 // change: their coefficients and stop words sit in registers, their sums are two accumulators per running sum.  A column's partial
 // sums are added in a fixed order (lane's own in index order, lanes of a wavefront by xor-butterfly, wavefronts in order, blocks in
 // order): the same bits whatever the other columns hold, from call to call.
-#include "multi_loop.hpp"
-#include "csr_tri.hpp"
-#include "dense.hpp"
+#include "multi_ops.hpp"
 
 namespace lcgh {
 namespace {
@@ -193,45 +191,7 @@ struct MOpPcgDir {      // d = z + b d                                     lcg.c
     __device__ void apply(long e, long, bool r0, bool r1, m2d *) { st2(d, e, ld2(z, e) + bk * ld2(d, e), r0, r1); }
 };
 
-// ---- the matrix, as the loop sees it ---------------------------------------------------------------------------------------------------
-// rows(), invdiag() (the Jacobi reciprocals), big_doubles(k) (what the product's carried sum needs on its way to the table) and
-// apply(): Y = A.X for the K columns and, with U, column j's (A.X)_j . U_j as *slots partial sums in `dots` (multi.hpp's table
-// format).  TREE: the passes add their sums as multi_loop.hpp's binary tree, so that a column's bits do not depend on K either.
-// factor(): a triangular factor as M (null: the built-in Jacobi).
-struct CsrOp {
-    static constexpr bool TREE = false;      // (the sums these entries have always computed)
-    lcg_hip_csr *A;
-    const TriFactor *F;
-    int rows() const { return A->n_rows; }
-    const double *invdiag() const { return A->invdiag; }
-    const TriFactor *factor() const { return F; }
-    size_t big_doubles(int k) const { return spmm_big_doubles(A->main, k); }
-    int apply(Ctx &c, int k, const double *X, double *Y, const int *done, const double *U = nullptr, double *big = nullptr,
-              double *dots = nullptr, int *slots = nullptr) const
-    {
-        c.cnt_ax++;
-        return spmm_launch(A->main, k, X, Y, c.stream, done, U, big, dots, slots);
-    }
-};
-// K^T.K or K of a dense handle (dense_multi.hip): the product is two to five launches, all counted as products
-struct DenseOp {
-    static constexpr bool TREE = true;
-    lcg_hip_dense *D;
-    int normal;
-    int rows() const { return D->N; }
-    const double *invdiag() const { return D->invdiag; }
-    const TriFactor *factor() const { return nullptr; }
-    size_t big_doubles(int) const { return 0; }
-    int apply(Ctx &c, int k, const double *X, double *Y, const int *done, const double *U = nullptr, double * = nullptr,
-              double *dots = nullptr, int *slots = nullptr) const
-    {
-        int launches = 0;
-        const int rc = dnm_op(D, k, normal, X, Y, c.stream, done, U, dots, slots, &launches);
-        c.cnt_ax += launches;
-        return rc;
-    }
-};
-
+// ---- the matrix, as the loop sees it: CsrOp, DenseOp (multi_ops.hpp) ------------------------------------------------------------------
 template <int K, bool PCG, class OpA>
 static int run_multi(const OpA &A, double *M, const double *B, const lcg_para &p, int *ret, int *iterations, double *residual, int mem)
 {   // A.factor(): the factor that is M (PCG only; its k-wide work vectors reserved by the caller), nullptr: the built-in Jacobi
