@@ -1,4 +1,4 @@
-"""ctypes view of the C ABI in ``include/lcg_hip.h``, ``include/lcg_hip_staging.h``, ``include/lcg_hip_staging_ic0_c64.h`` and ``include/lcg_hip_staging_box_multi.h`` (liblcg_amd/lib/liblcg_hip.so).
+"""ctypes view of the C ABI in ``include/lcg_hip.h``, ``include/lcg_hip_staging.h``, ``include/lcg_hip_staging_ic0_c64.h``, ``include/lcg_hip_staging_box_multi.h`` and ``include/lcg_hip_staging_dense_c64.h`` (liblcg_amd/lib/liblcg_hip.so).
 
 No compute happens in Python: every function here forwards to the HIP library.  If the
 shared object is missing the import fails loudly -- there is no fallback path.
@@ -238,6 +238,21 @@ STAGING_BOX_MULTI_SIGNATURES = {
     "lcg_hip_dense_solver_constrained_multi": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(LcgPara), c_int_p, c_int_p, c_int_p, c_double_p, C.c_int]),
 }
 
+# every symbol include/lcg_hip_staging_dense_c64.h declares: the complex64 dense entries (that header says why they have a file and
+# a dict of their own)
+STAGING_DENSE_C64_SIGNATURES = {
+    "lcg_hip_dense_create_c64": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, vp, C.c_int64, C.c_int]),
+    "clcg_hip_dense_matvec_c64": (C.c_int, [vp, vp, vp, C.c_int, C.c_int]),
+    "clcg_hip_dense_ax_c64": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
+    "clcg_hip_dense_jacobi_mx_c64": (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int]),
+    "lcg_hip_dense_build_jacobi_c64": (C.c_int, [vp, vp]),
+    "clcg_hip_dense_matmat_c64": (C.c_int, [vp, C.c_int, vp, vp, C.c_int]),
+    "clcg_hip_dense_op_multi_dot_c64": (C.c_int, [vp, C.c_int, vp, vp, vp, c_double_p]),
+    "clcg_hip_dense_lbicg_sym_multi_c64": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(ClcgPara), c_int_p, c_int_p, c_double_p, C.c_int]),
+    "clcg_hip_dense_lpcg_multi_c64": (C.c_int, [vp, C.c_int, vp, vp, C.POINTER(ClcgPara), c_int_p, c_int_p, c_double_p, C.c_int]),
+    "clcg_hip_dense_kernel_name_c64": (C.c_char_p, [C.c_int]),
+}
+
 _lib = None
 
 
@@ -266,7 +281,8 @@ def load():
     # the SAME runtime objects instead of mapping a second HIP runtime into the process.
     import torch  # noqa: F401
     lib = C.CDLL(SO_PATH, mode=C.RTLD_GLOBAL)
-    for name, (res, args) in {**SIGNATURES, **STAGING_SIGNATURES, **STAGING_IC0_C64_SIGNATURES, **STAGING_BOX_MULTI_SIGNATURES}.items():
+    for name, (res, args) in {**SIGNATURES, **STAGING_SIGNATURES, **STAGING_IC0_C64_SIGNATURES, **STAGING_BOX_MULTI_SIGNATURES,
+                              **STAGING_DENSE_C64_SIGNATURES}.items():
         fn = getattr(lib, name)     # AttributeError = header/library drift: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -382,6 +382,7 @@ class DenseMatrix:
     """An HBM-resident dense matrix (handle ``lcg_hip_dense_t``): K.x, K^T.x, K^T.K.x and the callbacks
     'lcg_hip_dense_ata_ax', 'lcg_hip_dense_ax', 'clcg_hip_dense_ax', 'lcg_hip_dense_jacobi_mx', 'clcg_hip_dense_jacobi_mx'."""
     KERNEL_AUTO, KERNEL_ROW, KERNEL_ROW_SPLIT, KERNEL_COL, KERNEL_ATA_TWO_PASS, KERNEL_ATA_ONE_PASS, KERNEL_ATA_SMALL = range(7)
+    is_c64 = False      # entries are complex64 (from_array_c64): the *_c64 methods and callbacks serve it, the others refuse it
 
     def __init__(self, handle: int, m: int, n: int, is_complex: bool):
         self.h = C.c_void_p(handle)
@@ -411,6 +412,72 @@ class DenseMatrix:
         h = C.c_void_p()
         _chk(lib.lcg_hip_dense_create(C.byref(h), m, n, ptr, ld, int(is_c), mem), "dense_create")
         return cls(h.value, m, n, is_c)
+
+    @classmethod
+    def from_array_c64(cls, K):
+        """A complex64 matrix (lcg_hip_dense_create_c64), 8 bytes per entry, nothing widened: K is a 2-d numpy complex64 array (host;
+        copied) or a torch.complex64 tensor (copied), row-major; the last axis may be a view of a wider array.  Products:
+        matvec_c64, cmatmat_c64, cop_multi_dot_c64; callbacks 'clcg_hip_dense_ax_c64', 'clcg_hip_dense_jacobi_mx_c64' for
+        clcg_solver_c64 / clcg_solver_preconditioned_c64; batched loops: dense_clbicg_sym_multi_c64, dense_clpcg_multi_c64."""
+        lib = L.load()
+        if isinstance(K, np.ndarray):
+            if K.dtype != np.complex64:
+                raise TypeError(f"from_array_c64 takes complex64 entries, not {K.dtype}")
+            if (K.ndim != 2 or K.strides[1] != K.itemsize or K.strides[0] % K.itemsize
+                    or (K.shape[0] > 1 and K.strides[0] < K.shape[1] * K.itemsize)):
+                K = np.ascontiguousarray(K)
+            ld, ptr, mem = K.strides[0] // K.itemsize, K.ctypes.data, MEM_HOST
+        else:
+            import torch
+            if K.dtype != torch.complex64:
+                raise TypeError(f"from_array_c64 takes complex64 entries, not {K.dtype}")
+            if K.dim() != 2 or K.stride(1) != 1:
+                raise ValueError("a 2-d tensor with unit stride along its rows is needed")
+            ld, ptr, mem = K.stride(0), K.data_ptr(), (MEM_DEVICE if K.is_cuda else MEM_HOST)
+        m, n = K.shape
+        if ld < n:
+            if m != 1:
+                raise ValueError(f"rows {ld} entries apart hold {n} entries: make the array contiguous first")
+            ld = n
+        h = C.c_void_p()
+        _chk(lib.lcg_hip_dense_create_c64(C.byref(h), m, n, ptr, ld, mem), "dense_create_c64")
+        D = cls(h.value, m, n, True)
+        D.is_c64 = True
+        return D
+
+    def matvec_c64(self, x, y, layout=0, conjugate=0):
+        """y = op(K).x for a complex64 matrix (clcg_hip_dense_matvec_c64): torch.complex64 CUDA tensors; layout 1: K^T, conjugate 1:
+        conj(K) / K^H."""
+        return _chk(L.load().clcg_hip_dense_matvec_c64(self.h, _ptr(x)[0], _ptr(y)[0], layout, conjugate), "dense_matvec_c64")
+
+    def build_jacobi_c64(self, diag_out=None):
+        """The complex64 reciprocals 1 / K(i,i) of a square complex64 matrix (lcg_hip_dense_build_jacobi_c64); diag_out (a
+        torch.complex64 CUDA tensor of n) receives the diagonal."""
+        p = None if diag_out is None else _ptr(diag_out)[0]
+        return _chk(L.load().lcg_hip_dense_build_jacobi_c64(self.h, p), "dense_build_jacobi_c64")
+
+    def cmatmat_c64(self, X, Y, conjugate=0):
+        """Y = K.X (conjugate 1: conj(K).X) for the k = 2, 4 or 8 complex64 columns of X with K read once for all of them, on the fp32
+        matrix instruction (clcg_hip_dense_matmat_c64): X (n, k), Y (m, k) C-contiguous complex64 CUDA tensors, 16-byte aligned."""
+        k = _block_k(X, Y, cplx="c64")
+        return _chk(L.load().clcg_hip_dense_matmat_c64(self.h, k, _ptr(X)[0], _ptr(Y)[0], conjugate), "dense_cmatmat_c64")
+
+    def cop_multi_dot_c64(self, X, Y, U):
+        """Y = K.X (square complex64 K) carrying one unconjugated sum per column (clcg_hip_dense_op_multi_dot_c64): returns a
+        complex128 array of k, [j] = sum_i Y_ij U_ij in fp64.  X, Y, U: (n, k) complex64 blocks."""
+        k = _block_k(X, Y, U, cplx="c64")
+        out = (C.c_double * (2 * k))()
+        _chk(L.load().clcg_hip_dense_op_multi_dot_c64(self.h, k, _ptr(X)[0], _ptr(Y)[0], _ptr(U)[0], out), "dense_cop_multi_dot_c64")
+        return np.array(out[:], dtype=np.float64).view(np.complex128)
+
+    @staticmethod
+    def kernel_names_c64():
+        lib, out, i = L.load(), [], 0
+        while True:
+            s = lib.clcg_hip_dense_kernel_name_c64(i)
+            if s is None:
+                return out
+            out.append(s.decode()); i += 1
 
     @classmethod
     def from_rows(cls, rows, is_complex=False):
@@ -760,6 +827,18 @@ def dense_clpcg_multi(K, M, B, param) -> list:
     """Batched complex PCG on a dense matrix with the reciprocals of K.build_jacobi(normal=False)
     (clcg_hip_dense_lpcg_multi).  As clpcg_multi."""
     return _multi("clcg_hip_dense_lpcg_multi", K, M, B, param, cplx=True)
+
+
+def dense_clbicg_sym_multi_c64(K, M, B, param) -> list:
+    """Batched BiCG on a square complex-symmetric complex64 dense matrix (clcg_hip_dense_lbicg_sym_multi_c64;
+    DenseMatrix.from_array_c64): K is read once per iteration for all k = 2, 4 or 8 columns.  As clbicg_sym_multi_c64."""
+    return _multi("clcg_hip_dense_lbicg_sym_multi_c64", K, M, B, param, cplx="c64")
+
+
+def dense_clpcg_multi_c64(K, M, B, param) -> list:
+    """Batched complex64 PCG on a dense matrix with the reciprocals of K.build_jacobi_c64() (clcg_hip_dense_lpcg_multi_c64).  As
+    clbicg_sym_multi_c64."""
+    return _multi("clcg_hip_dense_lpcg_multi_c64", K, M, B, param, cplx="c64")
 
 
 def lcgs(Afp, Pfp, m, B, n_size, param, instance, *workspaces) -> SolveInfo:

@@ -350,11 +350,18 @@ static int ata_product(lcg_hip_dense *K, const double *x, double *y, hipStream_t
     return rc;
 }
 
-static lcg_hip_dense *dense_of(const void *h, const char *entry)
+// any_type: the entry serves complex64 handles too (the queries, set_kernel, destroy); every other one refuses them
+static lcg_hip_dense *dense_of(const void *h, const char *entry, bool any_type = false)
 {
-    if (dense_handle(h)) return static_cast<lcg_hip_dense *>(const_cast<void *>(h));
-    arg_error("%s: the handle is not a dense matrix (lcg_hip_dense_create)", entry);
-    return nullptr;
+    if (!dense_handle(h)) { arg_error("%s: the handle is not a dense matrix (lcg_hip_dense_create)", entry); return nullptr; }
+    lcg_hip_dense *K = static_cast<lcg_hip_dense *>(const_cast<void *>(h));
+    if (K->c64 && !any_type) { refuse_c64_dense(entry); return nullptr; }
+    return K;
+}
+
+int refuse_c64_dense(const char *entry)
+{
+    return arg_error("%s: the matrix holds complex64 values (lcg_hip_dense_create_c64); its entries are the _c64 ones", entry);
 }
 
 static void dense_release(lcg_hip_dense *K)
@@ -437,16 +444,16 @@ int lcg_hip_dense_create_rows(lcg_hip_dense_t *K, int m_rows, int n_cols, const 
 
 int lcg_hip_dense_destroy(lcg_hip_dense_t K)
 {
-    if (!dense_of(K, "lcg_hip_dense_destroy")) return LCG_HIP_E_ARG;
+    if (!dense_of(K, "lcg_hip_dense_destroy", true)) return LCG_HIP_E_ARG;
     K->kind = 0;
     if (ctx().inited) (void)hipDeviceSynchronize();
     dense_release(K);
     return 0;
 }
 
-int lcg_hip_dense_rows(lcg_hip_dense_t K) { return dense_of(K, "lcg_hip_dense_rows") ? K->M : LCG_HIP_E_ARG; }
-int lcg_hip_dense_cols(lcg_hip_dense_t K) { return dense_of(K, "lcg_hip_dense_cols") ? K->N : LCG_HIP_E_ARG; }
-const char *lcg_hip_dense_last_kernel(lcg_hip_dense_t K) { return dense_of(K, "lcg_hip_dense_last_kernel") ? K->last_kernel : ""; }
+int lcg_hip_dense_rows(lcg_hip_dense_t K) { return dense_of(K, "lcg_hip_dense_rows", true) ? K->M : LCG_HIP_E_ARG; }
+int lcg_hip_dense_cols(lcg_hip_dense_t K) { return dense_of(K, "lcg_hip_dense_cols", true) ? K->N : LCG_HIP_E_ARG; }
+const char *lcg_hip_dense_last_kernel(lcg_hip_dense_t K) { return dense_of(K, "lcg_hip_dense_last_kernel", true) ? K->last_kernel : ""; }
 const char *lcg_hip_dense_kernel_name(int index)
 {
     return index >= 0 && index < (int)(sizeof DN_NAMES / sizeof *DN_NAMES) ? DN_NAMES[index] : nullptr;
@@ -454,8 +461,9 @@ const char *lcg_hip_dense_kernel_name(int index)
 
 int lcg_hip_dense_set_kernel(lcg_hip_dense_t K, int variant)
 {
-    if (!dense_of(K, "lcg_hip_dense_set_kernel")) return LCG_HIP_E_ARG;
+    if (!dense_of(K, "lcg_hip_dense_set_kernel", true)) return LCG_HIP_E_ARG;
     if (variant < DN_AUTO || variant > DN_ATA_SMALL) return arg_error("lcg_hip_dense_set_kernel: variant = %d (0 .. %d)", variant, (int)DN_ATA_SMALL);
+    if (K->c64 && variant > DN_COL) return arg_error("lcg_hip_dense_set_kernel: a complex64 matrix has no K^T.K.x forms (variant = %d)", variant);
     if ((variant == DN_ATA1 || variant == DN_ATA_SMALL) && (K->cplx || K->NP > 1024))
         return arg_error("lcg_hip_dense_set_kernel: the one-pass K^T.K.x serves real matrices of N <= 2048");
     if (variant == DN_ROW_SPLIT && row_plan(K->M, K->NP, true, true).S < 2)

@@ -1,7 +1,7 @@
 // dense.hpp -- what the dense units share (dense.hip: the single-vector products; dense_multi.hip: the k-wide kernels and their host
-// flow for real and complex128 handles; dense_multi_cplx.hip: the complex entries): the handle and the plans of the row and column
-// forms.  Not installed.
-// DESIGN.md sections 14, 19 and 20.
+// flow for real and complex128 handles; dense_multi_cplx.hip: the complex entries; dense_c64.hip: everything of a complex64 handle):
+// the handle and the plans of the row and column forms.  Not installed.
+// DESIGN.md sections 14, 19, 20 and 25.
 #pragma once
 
 #include <algorithm>
@@ -22,13 +22,15 @@ struct lcg_hip_dense {
     uint64_t kind = lcgh::KIND_DENSE;   // internal.hpp: the word both kinds of handle begin with
     int M = 0, N = 0;
     bool cplx = false;
+    bool c64 = false;           // the element type is complex64 (lcg_hip_dense_create_c64; cplx stays false): a pack is two (re, im) float pairs,
+                                // part and invdiag hold floats, t is not allocated.  Served by dense_c64.hip's entries and by no other
     int64_t ldp = 0;            // packs per stored row
     int NP = 0;                 // packs that hold a row's entries: N (c128) or ceil(N / 2)
     double2 *val = nullptr;     // M * ldp packs + slack
     double *t = nullptr;        // the M-vector between the two products of K^T.K.x
     double *part = nullptr;     // the partial-sum table
     int64_t part_doubles = 0;
-    double *invdiag = nullptr;  // N (or 2 N) doubles after lcg_hip_dense_build_jacobi
+    double *invdiag = nullptr;  // N (or 2 N) doubles after lcg_hip_dense_build_jacobi (c64: N float pairs after lcg_hip_dense_build_jacobi_c64)
     int invdiag_normal = -1;    // which operator the reciprocals belong to: 1 K^T.K, 0 K (-1: none built)
     int variant = 0;
     const char *last_kernel = "";
@@ -102,5 +104,18 @@ int dnm_op_dot_run(lcg_hip_dense *K, int k, int normal, const double *X, double 
 void dnm_fold_launch(const double *part, int S, int64_t n, double *y, hipStream_t s, const int *done);
 // entry `index` of the k-wide kernel names of real (cplx: complex128) handles, or nullptr
 const char *dnm_kernel_name(bool cplx, int index);
+// LCG_HIP_E_ARG with the text every entry for real or complex128 dense handles answers a complex64 one with (the two places a dense
+// handle's type is looked at: dense.hip's dense_of and dnm_handle)
+int refuse_c64_dense(const char *entry);
+
+// dense_c64.hip: the complex64 handle as the batched complex64 loops see it (solvers_multi_c64.hip)
+// a complex64 dense handle, or nullptr with the entry's name and the reason in lcg_hip_last_error()
+lcg_hip_dense *cdn_handle(const char *entry, const void *h);
+// the handle's fp32 k-wide slot table, as dnm_reserve
+int cdnm_reserve(lcg_hip_dense *K, int k);
+// Y = K.X for the k complex64 columns and, with U, column j's UNCONJUGATED sum Y_j . U_j as *slots <= MM_MG partial sums in
+// cspmm_c64_launch's table format (multi_c64.hpp).  *launches grows by the kernels enqueued.  Checked square handle, reserved k
+int cdnm_op(lcg_hip_dense *K, int k, const float *X, float *Y, hipStream_t s, const int *done, const float *U, double *dots, int *slots,
+            int *launches);
 
 } // namespace lcgh

@@ -531,6 +531,7 @@ lcg_hip_dense *dnm_handle(const char *entry, const void *h, bool cplx)
 {
     if (!dense_handle(h)) { arg_error("%s: the handle is not a dense matrix (lcg_hip_dense_create)", entry); return nullptr; }
     lcg_hip_dense *D = static_cast<lcg_hip_dense *>(const_cast<void *>(h));
+    if (D->c64) { refuse_c64_dense(entry); return nullptr; }
     if (D->cplx == cplx) return D;
     if (cplx) arg_error("%s: the matrix is real; the complex k-wide dense path serves complex128 matrices (real: lcg_hip_dense_matmat)", entry);
     else arg_error("%s: the matrix is complex; the k-wide dense path serves real fp64 matrices", entry);

@@ -1,6 +1,6 @@
 // solvers_multi_c64.hip -- batched complex64 loops over k = 2, 4, 8 right-hand sides against one complex-symmetric complex64 matrix:
 // clcg_hip_lbicg_sym_multi_c64 (clbicg_symmetric, clcg_cudaf.cu:254-401) and clcg_hip_lpcg_multi_c64 (clpcg with the handle's
-// reciprocal Jacobi diagonal, clcg_cudaf.cu:403-558).
+// reciprocal Jacobi diagonal, clcg_cudaf.cu:403-558), and the same loops on a dense complex64 handle (clcg_hip_dense_*_multi_c64).
 //
 // Each column runs solvers_c64.hip's recurrence as if it were alone: its own ak, bk and rho (r.r; PCG: r.s), both inner products
 // UNCONJUGATED (cublasCdotu), its own stop test, "already optimised" test, count and code.  What the columns share is the matrix: one
@@ -38,7 +38,9 @@
 #include "c64common.hpp"
 #include "multi_loop.hpp"
 #include "multi_c64.hpp"
+#include "dense.hpp"
 #include "lcg_hip_staging_ic0_c64.h"
+#include "lcg_hip_staging_dense_c64.h"
 
 namespace lcgh {
 namespace {
@@ -246,12 +248,46 @@ inline int c64m_code(int stop)
     }
 }
 
-// F: the complex64 IC(0) factor that is M (PCG only; its k-wide work vectors reserved by the caller), nullptr: the Jacobi reciprocals inv
-template <int K, bool PCG>
-static int run_c64m(lcg_hip_csr *A, const float *inv, const TriFactor *F, float *M, const float *B, const clcg_para &p, int *ret, int *iterations,
-                    double *residual, int mem)
+// The matrix as the loop sees it (multi_ops.hpp's operators in complex64): rows(), inv() (the complex64 Jacobi reciprocals, null without
+// Jacobi), factor() (the complex64 IC(0) factor that is M -- PCG only, its k-wide work vectors reserved by the caller -- or null),
+// big_doubles(k) and apply(): Y = A.X for the K columns and, with U, column j's unconjugated (A.X)_j . U_j as *slots partial sums in
+// `dots` (rows 2 j, 2 j + 1).
+struct C64CsrOp {
+    lcg_hip_csr *A;
+    const float *invdiag;
+    const TriFactor *F;
+    int rows() const { return A->n_rows; }
+    const float *inv() const { return invdiag; }
+    const TriFactor *factor() const { return F; }
+    size_t big_doubles(int k) const { return cspmm_c64_big_doubles(A->main, k); }
+    int apply(Ctx &c, int k, const float *X, float *Y, const int *done, const float *U, double *big, double *dots, int *slots) const
+    {
+        c.cnt_ax++;
+        return cspmm_c64_launch(A->main, k, X, Y, c.stream, done, U, big, dots, slots);
+    }
+};
+// a square complex64 dense handle (dense_c64.hip): the product is one to three launches, all counted as products
+struct C64DenseOp {
+    lcg_hip_dense *D;
+    int rows() const { return D->N; }
+    const float *inv() const { return reinterpret_cast<const float *>(D->invdiag); }
+    const TriFactor *factor() const { return nullptr; }
+    size_t big_doubles(int) const { return 0; }
+    int apply(Ctx &c, int k, const float *X, float *Y, const int *done, const float *U, double *, double *dots, int *slots) const
+    {
+        int launches = 0;
+        const int rc = cdnm_op(D, k, X, Y, c.stream, done, U, dots, slots, &launches);
+        c.cnt_ax += launches;
+        return rc;
+    }
+};
+
+template <int K, bool PCG, class Op>
+static int run_c64m(const Op &A, float *M, const float *B, const clcg_para &p, int *ret, int *iterations, double *residual, int mem)
 {
-    MultiFrame<C64MState, K, K / 2> f(A->n_rows);
+    const float *inv = A.inv();
+    const TriFactor *F = A.factor();
+    MultiFrame<C64MState, K, K / 2> f(A.rows());
     Ctx &c = f.c;
     {   // (the frame moves blocks as 16-byte pieces behind double pointers)
         double *Md = reinterpret_cast<double *>(M);
@@ -266,12 +302,11 @@ static int run_c64m(lcg_hip_csr *A, const float *inv, const TriFactor *F, float 
     TRY(vec(d));
     TRY(vec(Ad));
     if (PCG) TRY(vec(s));
-    const size_t nbig = cspmm_c64_big_doubles(A->main, K);
+    const size_t nbig = A.big_doubles(K);
     if (nbig) TRY(f.ws.get(big, nullptr, sizeof(double) * nbig));
     TRY(f.start(f.tree_grid(), p.epsilon, p.abs_diff));
     auto product = [&](const float *X, float *Y, const int *done, const float *U, double *dots, int *slots) -> int {
-        c.cnt_ax++;
-        return cspmm_c64_launch(A->main, K, X, Y, c.stream, done, U, big, dots, slots);
+        return A.apply(c, K, X, Y, done, U, big, dots, slots);
     };
 
     // setup: A.m for the guess, d = r (PCG: inv .* r), the verdict "already optimised"
@@ -316,7 +351,26 @@ static int c64m_entry(const char *entry, lcg_hip_csr *A, int k, float *M, const 
     const float *inv = PCG ? c64_builtin_invdiag((const void *)clcg_hip_jacobi_mx_c64, A, A->n_rows) : nullptr;
     if (PCG && inv == nullptr) return LCG_NULL_PRECONDITION_MATRIX;     // lcg_hip_csr_build_jacobi has not run
     TRY(ensure_init());
-    return multi_k(k, [&](auto K) { return run_c64m<decltype(K)::value, PCG>(A, inv, nullptr, M, B, p, ret, iterations, residual, mem); });
+    const C64CsrOp op{A, inv, nullptr};
+    return multi_k(k, [&](auto K) { return run_c64m<decltype(K)::value, PCG>(op, M, B, p, ret, iterations, residual, mem); });
+}
+
+// the dense entries: A = K, square; PCG with the reciprocals of lcg_hip_dense_build_jacobi_c64
+template <bool PCG>
+static int c64m_dense_entry(const char *entry, const void *Kh, int k, float *M, const float *B, const clcg_para *param, int *ret,
+                            int *iterations, double *residual, int mem)
+{
+    clcg_para p;
+    TRY(multi_args(entry, k, M, B));
+    lcg_hip_dense *D = cdn_handle(entry, Kh);
+    if (!D) return LCG_HIP_E_ARG;
+    TRY(multi_shape(entry, D->M == D->N, mem));
+    TRY(multi_para<true>(param, p, D->N));
+    if (PCG && D->invdiag == nullptr) return LCG_NULL_PRECONDITION_MATRIX;  // lcg_hip_dense_build_jacobi_c64 has not run
+    TRY(ensure_init());
+    TRY(cdnm_reserve(D, k));
+    const C64DenseOp op{D};
+    return multi_k(k, [&](auto K) { return run_c64m<decltype(K)::value, PCG>(op, M, B, p, ret, iterations, residual, mem); });
 }
 
 // precond: LCG_HIP_M_JACOBI (clcg_hip_lpcg_multi_c64 itself) or LCG_HIP_M_IC0 (the handle's complex64 factor)
@@ -335,7 +389,8 @@ static int c64m_entry_m(const char *entry, lcg_hip_csr *A, int k, int precond, f
     if (!F || !F->ok || !F->c64) return LCG_NULL_PRECONDITION_MATRIX;   // lcg_hip_csr_build_ic0_c64 has not run (or its pivot failed)
     TRY(ensure_init());
     TRY(tri_multi_reserve(F, k, 2));
-    return multi_k(k, [&](auto K) { return run_c64m<decltype(K)::value, true>(A, nullptr, F, M, B, p, ret, iterations, residual, mem); });
+    const C64CsrOp op{A, nullptr, F};
+    return multi_k(k, [&](auto K) { return run_c64m<decltype(K)::value, true>(op, M, B, p, ret, iterations, residual, mem); });
 }
 
 } // namespace
@@ -364,6 +419,18 @@ int clcg_hip_lpcg_multi_m_c64(lcg_hip_csr_t A, int k, int precond, float *M, con
 {
     NOT_DENSE(A, LCG_HIP_E_ARG);
     return c64m_entry_m("clcg_hip_lpcg_multi_m_c64", A, k, precond, M, B, param, ret, iterations, residual, mem);
+}
+
+int clcg_hip_dense_lbicg_sym_multi_c64(lcg_hip_dense_t K, int k, float *M, const float *B, const clcg_para *param, int *ret, int *iterations,
+                                       double *residual, int mem)
+{
+    return c64m_dense_entry<false>("clcg_hip_dense_lbicg_sym_multi_c64", K, k, M, B, param, ret, iterations, residual, mem);
+}
+
+int clcg_hip_dense_lpcg_multi_c64(lcg_hip_dense_t K, int k, float *M, const float *B, const clcg_para *param, int *ret, int *iterations,
+                                  double *residual, int mem)
+{
+    return c64m_dense_entry<true>("clcg_hip_dense_lpcg_multi_c64", K, k, M, B, param, ret, iterations, residual, mem);
 }
 
 } // extern "C"
