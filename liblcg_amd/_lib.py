@@ -1,4 +1,4 @@
-"""ctypes view of the C ABI in ``include/lcg_hip.h``, ``include/lcg_hip_staging.h``, ``include/lcg_hip_staging_ic0_c64.h``, ``include/lcg_hip_staging_box_multi.h`` and ``include/lcg_hip_staging_dense_c64.h`` (liblcg_amd/lib/liblcg_hip.so).
+"""ctypes view of the C ABI in ``include/lcg_hip.h``, ``include/lcg_hip_staging.h``, ``include/lcg_hip_staging_ic0_c64.h``, ``include/lcg_hip_staging_box_multi.h``, ``include/lcg_hip_staging_dense_c64.h`` and ``include/lcg_hip_staging_csr_normal.h`` (liblcg_amd/lib/liblcg_hip.so).
 
 No compute happens in Python: every function here forwards to the HIP library.  If the
 shared object is missing the import fails loudly -- there is no fallback path.
@@ -253,6 +253,27 @@ STAGING_DENSE_C64_SIGNATURES = {
     "clcg_hip_dense_kernel_name_c64": (C.c_char_p, [C.c_int]),
 }
 
+# every symbol include/lcg_hip_staging_csr_normal.h declares: K^T.x, K^T.K.x and the batched loops on K^T.K of a rectangular CSR
+# matrix (that header says why they have a file and a dict of their own)
+_MULTI = [vp, C.c_int, vp, vp, C.POINTER(LcgPara), c_int_p, c_int_p, c_double_p, C.c_int]
+STAGING_CSR_NORMAL_SIGNATURES = {
+    "lcg_hip_csr_cols": (C.c_int, [vp]),
+    "lcg_hip_csr_build_normal": (C.c_int, [vp]),
+    "lcg_hip_csr_normal_info": (C.c_int, [vp, c_int_p, C.POINTER(C.c_int64), c_double_p]),
+    "lcg_hip_csr_normal_arrays": (C.c_int, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
+    "lcg_hip_spmv_t": (C.c_int, [vp, vp, vp]),
+    "lcg_hip_csr_ata": (C.c_int, [vp, vp, vp]),
+    "lcg_hip_csr_ata_ax": (None, [vp, vp, vp, C.c_int]),
+    "lcg_hip_csr_build_jacobi_normal": (C.c_int, [vp, vp]),
+    "lcg_hip_csr_jacobi_normal_mx": (None, [vp, vp, vp, C.c_int]),
+    "lcg_hip_spmm_t": (C.c_int, [vp, C.c_int, vp, vp]),
+    "lcg_hip_csr_ata_multi": (C.c_int, [vp, C.c_int, vp, vp]),
+    "lcg_hip_csr_ata_multi_dot": (C.c_int, [vp, C.c_int, vp, vp, vp, c_double_p]),
+    "lcg_hip_csr_normal_lcg_multi": (C.c_int, list(_MULTI)),
+    "lcg_hip_csr_normal_lpcg_multi": (C.c_int, list(_MULTI)),
+    "lcg_hip_csr_normal_solver_constrained_multi": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(LcgPara), c_int_p, c_int_p, c_int_p, c_double_p, C.c_int]),
+}
+
 _lib = None
 
 
@@ -282,7 +303,7 @@ def load():
     import torch  # noqa: F401
     lib = C.CDLL(SO_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in {**SIGNATURES, **STAGING_SIGNATURES, **STAGING_IC0_C64_SIGNATURES, **STAGING_BOX_MULTI_SIGNATURES,
-                              **STAGING_DENSE_C64_SIGNATURES}.items():
+                              **STAGING_DENSE_C64_SIGNATURES, **STAGING_CSR_NORMAL_SIGNATURES}.items():
         fn = getattr(lib, name)     # AttributeError = header/library drift: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -363,6 +363,65 @@ class CsrMatrix:
         _chk(L.load().clcg_hip_spmm_dot_c64(self.h, k, _ptr(X)[0], _ptr(Y)[0], _ptr(U)[0], out), "cspmm_dot_c64")
         return np.array(out[:], dtype=np.float64).view(np.complex128)
 
+    # -- sparse least squares: K^T.x, K^T.K.x on a rectangular matrix (csr_normal.hip) ------------
+    @property
+    def n_cols(self) -> int:
+        return L.load().lcg_hip_csr_cols(self.h)
+
+    def build_normal(self):
+        """Materialise K^T and the work vectors beside the matrix (lcg_hip_csr_build_normal): what spmv_t, ata, the k-wide forms, the
+        callbacks 'lcg_hip_csr_ata_ax' / 'lcg_hip_csr_jacobi_normal_mx' and the csr_normal_* loops need.  Idempotent."""
+        _chk(L.load().lcg_hip_csr_build_normal(self.h), "build_normal")
+
+    def normal_info(self) -> dict:
+        lc, nb, ms = C.c_int(), C.c_int64(), C.c_double()
+        _chk(L.load().lcg_hip_csr_normal_info(self.h, C.byref(lc), C.byref(nb), C.byref(ms)), "normal_info")
+        return {"longest_column": lc.value, "extra_bytes": nb.value, "build_ms": ms.value}
+
+    def normal_to_host(self):
+        """(rowptr, col, val) of K^T copied to numpy: rows by source row, duplicates in K's own entry order."""
+        lib = L.load()
+        pr, pc, pv = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _chk(lib.lcg_hip_csr_normal_arrays(self.h, C.byref(pr), C.byref(pc), C.byref(pv)), "normal_arrays")
+        nnz = self.nnz
+        rowptr = np.empty(self.n_cols + 1, np.int32); col = np.empty(nnz, np.int32); val = np.empty(nnz, np.float64)
+        for dst, src in ((rowptr, pr), (col, pc), (val, pv)):
+            if dst.nbytes:
+                _chk(lib.lcg_hip_memcpy(dst.ctypes.data, src, dst.nbytes, 2), "memcpy d2h")
+        return rowptr, col, val
+
+    def spmv_t(self, x, y):
+        """y (n_cols) = K^T.x (n_rows) (lcg_hip_spmv_t): how b = K^T.d is formed."""
+        _chk(L.load().lcg_hip_spmv_t(self.h, _ptr(x)[0], _ptr(y)[0]), "spmv_t")
+
+    def ata(self, x, y):
+        """y = K^T.(K.x), both of n_cols elements (lcg_hip_csr_ata)."""
+        _chk(L.load().lcg_hip_csr_ata(self.h, _ptr(x)[0], _ptr(y)[0]), "csr_ata")
+
+    def spmm_t(self, X, Y):
+        """Y (n_cols, k) = K^T.X (n_rows, k) for k = 2, 4 or 8 columns (lcg_hip_spmm_t); blocks as spmm's."""
+        k = _block_k(X, Y)
+        _chk(L.load().lcg_hip_spmm_t(self.h, k, _ptr(X)[0], _ptr(Y)[0]), "spmm_t")
+
+    def ata_multi(self, X, Y):
+        """Y = K^T.(K.X) for the k columns of X, both matrices read once for all of them (lcg_hip_csr_ata_multi).  X, Y: (n_cols, k)."""
+        k = _block_k(X, Y)
+        _chk(L.load().lcg_hip_csr_ata_multi(self.h, k, _ptr(X)[0], _ptr(Y)[0]), "csr_ata_multi")
+
+    def ata_multi_dot(self, X, Y, U):
+        """ata_multi carrying the sum the batched loops take after it (lcg_hip_csr_ata_multi_dot): returns a float64 array of k,
+        [j] = Y_j . U_j.  X, Y, U: (n_cols, k) blocks."""
+        k = _block_k(X, Y, U)
+        out = (C.c_double * k)()
+        _chk(L.load().lcg_hip_csr_ata_multi_dot(self.h, k, _ptr(X)[0], _ptr(Y)[0], _ptr(U)[0], out), "csr_ata_multi_dot")
+        return np.array(out[:], dtype=np.float64)
+
+    def build_jacobi_normal(self, diag_out=None):
+        """The reciprocals of diag(K^T.K) = the columns' sums of squares (lcg_hip_csr_build_jacobi_normal), kept beside
+        build_jacobi()'s; diag_out (a float64 CUDA tensor of n_cols) receives the sums.  Mfp: 'lcg_hip_csr_jacobi_normal_mx'."""
+        p = None if diag_out is None else _ptr(diag_out)[0]
+        _chk(L.load().lcg_hip_csr_build_jacobi_normal(self.h, p), "build_jacobi_normal")
+
     def distribute(self, n_global: int, mode: int = 0):
         _chk(L.load().lcg_hip_csr_distribute(self.h, n_global, mode), "csr_distribute")
 
@@ -764,6 +823,24 @@ def dense_solver_constrained_multi(K, M, B, low, hig, param, solver_id=LCG_PG, n
     """Batched box-constrained solve on a dense matrix (lcg_hip_dense_solver_constrained_multi): the operator is K^T.K (normal)
     or K (square).  As lcg_solver_constrained_multi."""
     return _box_multi("lcg_hip_dense_solver_constrained_multi", (_instance(K), _block_k(M, B), int(normal)), M, B, low, hig, param, solver_id)
+
+
+def csr_normal_lcg_multi(K, M, B, param) -> list:
+    """Batched CG on K^T.K of a rectangular CSR matrix (lcg_hip_csr_normal_lcg_multi; K.build_normal() first): M (in/out) and B are
+    (n_cols, k) blocks of k = 2, 4 or 8 columns, every column solved as if it were alone while K and K^T are read once per iteration
+    for all of them.  Returns one SolveInfo per column, as dense_lcg_multi."""
+    return _multi("lcg_hip_csr_normal_lcg_multi", K, M, B, param)
+
+
+def csr_normal_lpcg_multi(K, M, B, param) -> list:
+    """Batched PCG on K^T.K with the reciprocals of K.build_jacobi_normal() (lcg_hip_csr_normal_lpcg_multi).  As csr_normal_lcg_multi."""
+    return _multi("lcg_hip_csr_normal_lpcg_multi", K, M, B, param)
+
+
+def csr_normal_solver_constrained_multi(K, M, B, low, hig, param, solver_id=LCG_PG) -> list:
+    """Batched box-constrained solve on K^T.K of a rectangular CSR matrix (lcg_hip_csr_normal_solver_constrained_multi).  As
+    lcg_solver_constrained_multi."""
+    return _box_multi("lcg_hip_csr_normal_solver_constrained_multi", (_instance(K), _block_k(M, B)), M, B, low, hig, param, solver_id)
 
 
 def lbicgstab_multi(A, M, B, param, precond=None) -> list:

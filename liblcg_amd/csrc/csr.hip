@@ -1887,6 +1887,7 @@ int lcg_hip_csr_destroy(lcg_hip_csr_t A)
     dist_free(A);
     free_part(A->main);
     for (int i = 1; i < 4; i++) free_part(A->op[i]);
+    normal_free(A);
     if (A->invdiag) hipFree(A->invdiag);
     tri_factor_free(A->ic0);
     tri_factor_free(A->ilu0);
@@ -1921,9 +1922,11 @@ int lcg_hip_csr_set_kernel(lcg_hip_csr_t A, int variant)
 // set_*(A, 0) is the first half of the rewrite protocol (lcg_hip.h): the transposed / conjugated copies (op_part) are made from the
 // arrays too, so they go with the plans and are rebuilt from the new arrays at their next use.  So is the half store of a symmetric
 // run stretch (csr_sym.hip), the one copy of VALUES the packed form keeps: it goes with ANY of the setters, and the plan it belongs
-// to is built -- and its values compared -- again at the next product.
+// to is built -- and its values compared -- again at the next product.  The normal state (csr_normal.hip) holds K^T and sums of
+// squared values: it stays, marked stale, and the next entry that needs it builds it again from the arrays as they are then.
 static void op_copies_free(lcg_hip_csr *A)
 {
+    normal_stale(A);
     if (A->main.pk_sym_H || std::strncmp(A->main.sym_why, "refused", 7) == 0) sym_runs_reset(A->main);      // (refused values may mirror each other now)
     if (!A->op[1].rowptr && !A->op[2].rowptr && !A->op[3].rowptr) return;
     if (ctx().inited) (void)hipDeviceSynchronize();

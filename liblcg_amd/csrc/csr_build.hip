@@ -362,11 +362,13 @@ __global__ void k_coo_place(long nnz, const int *row, const int *rowptr, int *ne
         perm[rowptr[r] + atomicAdd(&next[r], 1)] = (int)k;
     }
 }
-__global__ void k_perm_sort(int n, const int *rowptr, int *perm)
-{   // ascending input position inside each row = the order a stable sort by row would give
+__global__ void k_perm_sort(int n, const int *rowptr, int *perm, int longest)
+{   // ascending input position inside each row = the order a stable sort by row would give.  Rows of more than `longest` entries are
+    // left as they are (csr_normal.hip sorts those a workgroup at a time)
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int s = rowptr[i], e = rowptr[i + 1];
+    if (e - s > longest) return;
     for (int a = s + 1; a < e; a++) {
         const int v = perm[a];
         int b = a - 1;
@@ -381,6 +383,11 @@ __global__ void k_coo_gather(long nnz, const int *perm, const int *colin, const 
         const int src = perm[k];
         col[k] = colin[src]; val[k] = valin[src];
     }
+}
+
+void perm_sort_launch(int n, const int *rowptr, int *perm, int longest, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_perm_sort, dim3((unsigned)((n + VB - 1) / VB)), dim3(VB), 0, s, n, rowptr, perm, longest);
 }
 
 int alloc_part(CsrPart &P, int n_rows, long nnz, bool cplx)
@@ -597,7 +604,7 @@ int lcg_hip_csr_from_coo(lcg_hip_csr_t *out, int n, int64_t nnz, const int *row,
         e = hipMemsetAsync(cnt, 0, sizeof(int) * (size_t)n, c.stream);
         if (e != hipSuccess) return bail2(fail(e, "coo sort", __FILE__, __LINE__));
         hipLaunchKernelGGL(k_coo_place, dim3(1024), dim3(VB), 0, c.stream, (long)nnz, d_row, A->main.rowptr, cnt, perm);
-        hipLaunchKernelGGL(k_perm_sort, dim3((unsigned)((n + VB - 1) / VB)), dim3(VB), 0, c.stream, n, A->main.rowptr, perm);
+        perm_sort_launch(n, A->main.rowptr, perm, 0x7fffffff, c.stream);
         if (is_complex)
             hipLaunchKernelGGL((k_coo_gather<double2>), dim3(1024), dim3(VB), 0, c.stream, (long)nnz, perm, d_colin,
                                reinterpret_cast<const double2 *>(d_valin), A->main.col, reinterpret_cast<double2 *>(A->main.val));

@@ -336,6 +336,7 @@ inline int refuse_dense(const char *entry, bool park = false)
 #define NOT_DENSE_CB(h) do { if (::lcgh::dense_handle(h)) { ::lcgh::refuse_dense(__func__, true); return; } } while (0)
 
 namespace lcgh { struct TriFactor; }    // csr_tri.hpp
+namespace lcgh { struct CsrNormal; }    // csr_normal.hpp
 struct lcg_hip_csr {
     uint64_t kind = lcgh::KIND_CSR;
     int n_rows = 0;         // local rows
@@ -366,6 +367,8 @@ struct lcg_hip_csr {
     // --- complex64 values (csr_c64.hip) ---
     bool c64 = false;           // main.val holds n_nnz interleaved (re, im) floats (8 B per entry); is_complex stays false
     void *c64p = nullptr;       // the products' plans and the Jacobi reciprocals of such a matrix (csr_c64.hip: C64Data)
+    // --- the normal equations of a rectangular real matrix (csr_normal.hip) ---
+    lcgh::CsrNormal *normal = nullptr;  // K^T as a CSR of its own, the vectors between the two products, the reciprocals of diag(K^T.K): built by lcg_hip_csr_build_normal
 };
 
 namespace lcgh {
@@ -409,6 +412,10 @@ int device_exclusive_scan(int n, const int *counts, int *rowptr, hipStream_t s, 
 int transpose_launch(int n, int nt, long nnz, const int *rowptr, const int *col, const double *val, int *rpT, int *colT, double *valT,
                      bool cplx, int conj, int *cnt, hipStream_t s);
 void row_sort_launch(int n, const int *rowptr, int *col, double *val, bool cplx, hipStream_t s);    // k_row_sort: by (column, value)
+void perm_sort_launch(int n, const int *rowptr, int *perm, int longest, hipStream_t s);     // k_perm_sort: ascending, rows of at most `longest` entries
+// csr_normal.hip
+void normal_free(lcg_hip_csr *A);           // the normal state goes (lcg_hip_csr_destroy)
+void normal_stale(lcg_hip_csr *A);          // the arrays may be rewritten (the set_*(A, 0) protocol): the state is rebuilt from them at its next use
 // csr_tri.hip
 void tri_factor_free(TriFactor *&F);                                 // an IC(0) / ILU(0) factor and everything it holds; F = nullptr
 // csr.hip

@@ -1,9 +1,10 @@
 // multi_ops.hpp -- the matrix as the real batched loops see it (solvers_multi.hip: CG, PCG; solvers_multi_box.hip: PG, SPG): a small
-// operator argument over a CSR handle or a dense handle's K^T.K / K.  Host code only.  Not installed.
+// operator argument over a CSR handle, a rectangular CSR handle's K^T.K or a dense handle's K^T.K / K.  Host code only.  Not installed.
 #pragma once
 
 #include "multi_loop.hpp"
 #include "csr_tri.hpp"
+#include "csr_normal.hpp"
 #include "dense.hpp"
 
 namespace lcgh {
@@ -25,6 +26,24 @@ struct CsrOp {
     {
         c.cnt_ax++;
         return spmm_launch(A->main, k, X, Y, c.stream, done, U, big, dots, slots);
+    }
+};
+// K^T.K of a rectangular CSR handle with its normal state (csr_normal.hip): K.X into the state's M x k block, then K^T over the
+// materialised transpose, which carries the sum; two launches, both counted as products, both under the same stop flag.  The columns'
+// sums are the product kernel's (an order fixed by K^T alone) and the passes' are trees: a column's bits do not depend on k
+struct CsrNormalOp {
+    static constexpr bool TREE = true;
+    lcg_hip_csr *A;
+    int rows() const { return A->n_cols; }
+    const double *invdiag() const { return A->normal->invdiag; }
+    const TriFactor *factor() const { return nullptr; }
+    size_t big_doubles(int k) const { return spmm_big_doubles(A->normal->T, k); }
+    int apply(Ctx &c, int k, const double *X, double *Y, const int *done, const double *U = nullptr, double *big = nullptr,
+              double *dots = nullptr, int *slots = nullptr) const
+    {
+        c.cnt_ax += 2;
+        TRY(spmm_launch(A->main, k, X, A->normal->tk, c.stream, done));
+        return spmm_launch(A->normal->T, k, A->normal->tk, Y, c.stream, done, U, big, dots, slots);
     }
 };
 // K^T.K or K of a dense handle (dense_multi.hip): the product is two to five launches, all counted as products

@@ -1,7 +1,8 @@
 // solvers_multi.hip -- batched CG and PCG over k = 2, 4, 8 right-hand sides: lcg_hip_lcg_multi, lcg_hip_lpcg_multi (the built-in
 // Jacobi), lcg_hip_lpcg_multi_m (Jacobi, or the handle's IC(0) / ILU(0) factor applied k wide: csr_tri_multi.hip), and the same loop
-// on a dense handle's K^T.K or K: lcg_hip_dense_lcg_multi, lcg_hip_dense_lpcg_multi (dense_multi.hip).  The loop reaches the matrix
-// through a small operator argument (CsrOp, DenseOp: multi_ops.hpp).
+// on a dense handle's K^T.K or K: lcg_hip_dense_lcg_multi, lcg_hip_dense_lpcg_multi (dense_multi.hip), and on a rectangular CSR
+// handle's K^T.K: lcg_hip_csr_normal_lcg_multi, lcg_hip_csr_normal_lpcg_multi (csr_normal.hip).  The loop reaches the matrix
+// through a small operator argument (CsrOp, CsrNormalOp, DenseOp: multi_ops.hpp).
 //
 // Each column runs the reference's own recurrence as if it were alone (lcg.cpp:143-274, 293-434): its own alpha, beta, rho, its own
 // residual under the same stop rule, its own "already optimised" test, NaN scan, count and return code.  What the columns share is
@@ -281,6 +282,24 @@ static int solve_dense_multi(const char *entry, const void *Kh, int k, int norma
     return multi_k(k, [&](auto K) { return run_multi<decltype(K)::value, PCG>(op, M, B, p, ret, iterations, residual, mem); });
 }
 
+// the normal equations of a rectangular CSR handle: A = K^T.K through the handle's normal state (csr_normal.hip), PCG with the
+// reciprocals of lcg_hip_csr_build_jacobi_normal
+template <bool PCG>
+static int solve_normal_multi(const char *entry, lcg_hip_csr *K, int k, double *M, const double *B, const lcg_para *param, int *ret,
+                              int *iterations, double *residual, int mem)
+{
+    lcg_para p;
+    TRY(normal_kind(entry, K));
+    TRY(multi_args(entry, k, M, B));
+    TRY(multi_shape(entry, true, mem));
+    TRY(normal_ready(entry, K));
+    TRY(multi_para<false>(param, p, K->n_cols));
+    if (PCG && !K->normal->invdiag) return LCG_NULL_PRECONDITION_MATRIX;
+    TRY(normal_reserve(K, k));
+    const CsrNormalOp op{K};
+    return multi_k(k, [&](auto KK) { return run_multi<decltype(KK)::value, PCG>(op, M, B, p, ret, iterations, residual, mem); });
+}
+
 } // namespace
 } // namespace lcgh
 
@@ -319,6 +338,18 @@ int lcg_hip_dense_lpcg_multi(lcg_hip_dense_t K, int k, int normal, double *M, co
                              int *iterations, double *residual, int mem)
 {
     return solve_dense_multi<true>("lcg_hip_dense_lpcg_multi", K, k, normal, M, B, param, ret, iterations, residual, mem);
+}
+
+int lcg_hip_csr_normal_lcg_multi(lcg_hip_csr_t K, int k, double *M, const double *B, const lcg_para *param, int *ret, int *iterations,
+                                 double *residual, int mem)
+{
+    return solve_normal_multi<false>("lcg_hip_csr_normal_lcg_multi", K, k, M, B, param, ret, iterations, residual, mem);
+}
+
+int lcg_hip_csr_normal_lpcg_multi(lcg_hip_csr_t K, int k, double *M, const double *B, const lcg_para *param, int *ret, int *iterations,
+                                  double *residual, int mem)
+{
+    return solve_normal_multi<true>("lcg_hip_csr_normal_lpcg_multi", K, k, M, B, param, ret, iterations, residual, mem);
 }
 
 } // extern "C"

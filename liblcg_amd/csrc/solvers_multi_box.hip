@@ -1,5 +1,6 @@
 // solvers_multi_box.hip -- batched box-constrained solvers over k = 2, 4, 8 right-hand sides: lcg_hip_solver_constrained_multi (a CSR
-// handle) and lcg_hip_dense_solver_constrained_multi (a dense handle's K^T.K or K).  DESIGN.md section 24.
+// handle), lcg_hip_dense_solver_constrained_multi (a dense handle's K^T.K or K) and lcg_hip_csr_normal_solver_constrained_multi (a
+// rectangular CSR handle's K^T.K: csr_normal.hip).  DESIGN.md sections 24, 26.
 //
 // Each column runs the reference's lpg (lcg.cpp:1054-1204) or lspg (lcg.cpp:1224-1446) as if it were alone: the guess projected
 // into the box, g = A.m - b, both "already optimised" criteria in the reference's order, the stop rule and the cap at the loop
@@ -364,6 +365,24 @@ int lcg_hip_dense_solver_constrained_multi(lcg_hip_dense_t K, int k, int normal,
     TRY(ensure_init());
     TRY(dnm_reserve(D, k));
     return box_dispatch(DenseOp{D, normal}, k, spg, M, B, low, hig, xp, p, ret, iterations, products, residual, mem);
+}
+
+int lcg_hip_csr_normal_solver_constrained_multi(lcg_hip_csr_t K, int k, int solver_id, double *M, const double *B, const double *low,
+                                                const double *hig, const lcg_para *param, int *ret, int *iterations, int *products,
+                                                double *residual, int mem)
+{
+    static const char *entry = "lcg_hip_csr_normal_solver_constrained_multi";
+    const bool spg = solver_id == LCG_SPG;
+    lcg_para p;
+    XPara xp;
+    TRY(normal_kind(entry, K));
+    TRY(multi_args(entry, k, M, B));
+    TRY(box_bounds(entry, low, hig));
+    TRY(multi_shape(entry, true, mem));
+    TRY(normal_ready(entry, K));
+    TRY(box_para(entry, spg, param, p, xp));
+    TRY(normal_reserve(K, k));
+    return box_dispatch(CsrNormalOp{K}, k, spg, M, B, low, hig, xp, p, ret, iterations, products, residual, mem);
 }
 
 } // extern "C"
