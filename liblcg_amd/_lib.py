@@ -1,4 +1,4 @@
-"""ctypes view of the C ABI in ``include/lcg_hip.h``, ``include/lcg_hip_staging.h``, ``include/lcg_hip_staging_ic0_c64.h``, ``include/lcg_hip_staging_box_multi.h``, ``include/lcg_hip_staging_dense_c64.h`` and ``include/lcg_hip_staging_csr_normal.h`` (liblcg_amd/lib/liblcg_hip.so).
+"""ctypes view of the C ABI in ``include/lcg_hip.h``, ``include/lcg_hip_staging.h``, ``include/lcg_hip_staging_ic0_c64.h``, ``include/lcg_hip_staging_box_multi.h``, ``include/lcg_hip_staging_dense_c64.h``, ``include/lcg_hip_staging_csr_normal.h`` and ``include/lcg_hip_staging_dense_f32.h`` (liblcg_amd/lib/liblcg_hip.so).
 
 No compute happens in Python: every function here forwards to the HIP library.  If the
 shared object is missing the import fails loudly -- there is no fallback path.
@@ -274,6 +274,13 @@ STAGING_CSR_NORMAL_SIGNATURES = {
     "lcg_hip_csr_normal_solver_constrained_multi": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, C.POINTER(LcgPara), c_int_p, c_int_p, c_int_p, c_double_p, C.c_int]),
 }
 
+# every symbol include/lcg_hip_staging_dense_f32.h declares: the real dense handle stored in fp32 and the element-width query (that
+# header says why they have a file and a dict of their own)
+STAGING_DENSE_F32_SIGNATURES = {
+    "lcg_hip_dense_create_f32": (C.c_int, [C.POINTER(vp), C.c_int, C.c_int, vp, C.c_int64, C.c_int]),
+    "lcg_hip_dense_value_bytes": (C.c_int, [vp]),
+}
+
 _lib = None
 
 
@@ -303,7 +310,7 @@ def load():
     import torch  # noqa: F401
     lib = C.CDLL(SO_PATH, mode=C.RTLD_GLOBAL)
     for name, (res, args) in {**SIGNATURES, **STAGING_SIGNATURES, **STAGING_IC0_C64_SIGNATURES, **STAGING_BOX_MULTI_SIGNATURES,
-                              **STAGING_DENSE_C64_SIGNATURES, **STAGING_CSR_NORMAL_SIGNATURES}.items():
+                              **STAGING_DENSE_C64_SIGNATURES, **STAGING_CSR_NORMAL_SIGNATURES, **STAGING_DENSE_F32_SIGNATURES}.items():
         fn = getattr(lib, name)     # AttributeError = header/library drift: fail loudly
         fn.restype = res
         fn.argtypes = args

@@ -504,6 +504,41 @@ class DenseMatrix:
         D.is_c64 = True
         return D
 
+    @classmethod
+    def from_array_f32(cls, K):
+        """A real matrix kept as fp32 (lcg_hip_dense_create_f32), 4 bytes per entry: K is a 2-d numpy float32 array (host; copied) or a
+        torch.float32 tensor (copied), row-major; the last axis may be a view of a wider array.  Nothing is cast in either direction: a
+        float64 array is refused (from_array takes it), and from_array keeps widening a float32 one.  Vectors, sums and solver state stay
+        fp64 and every method and callback of a real fp64 matrix serves the handle, with the bits of from_array(K.astype(float64))."""
+        lib = L.load()
+        if isinstance(K, np.ndarray):
+            if K.dtype != np.float32:
+                raise TypeError(f"from_array_f32 takes float32 entries, not {K.dtype}")
+            if (K.ndim != 2 or K.strides[1] != K.itemsize or K.strides[0] % K.itemsize
+                    or (K.shape[0] > 1 and K.strides[0] < K.shape[1] * K.itemsize)):
+                K = np.ascontiguousarray(K)
+            ld, ptr, mem = K.strides[0] // K.itemsize, K.ctypes.data, MEM_HOST
+        else:
+            import torch
+            if K.dtype != torch.float32:
+                raise TypeError(f"from_array_f32 takes float32 entries, not {K.dtype}")
+            if K.dim() != 2 or K.stride(1) != 1:
+                raise ValueError("a 2-d tensor with unit stride along its rows is needed")
+            ld, ptr, mem = K.stride(0), K.data_ptr(), (MEM_DEVICE if K.is_cuda else MEM_HOST)
+        m, n = K.shape
+        if ld < n:
+            if m != 1:
+                raise ValueError(f"rows {ld} entries apart hold {n} entries: make the array contiguous first")
+            ld = n
+        h = C.c_void_p()
+        _chk(lib.lcg_hip_dense_create_f32(C.byref(h), m, n, ptr, ld, mem), "dense_create_f32")
+        return cls(h.value, m, n, False)
+
+    @property
+    def value_bytes(self) -> int:
+        """Bytes per stored entry of K (lcg_hip_dense_value_bytes): 4 (from_array_f32), 8 (float64, complex64) or 16 (complex128)."""
+        return _chk(L.load().lcg_hip_dense_value_bytes(self.h), "dense_value_bytes")
+
     def matvec_c64(self, x, y, layout=0, conjugate=0):
         """y = op(K).x for a complex64 matrix (clcg_hip_dense_matvec_c64): torch.complex64 CUDA tensors; layout 1: K^T, conjugate 1:
         conj(K) / K^H."""

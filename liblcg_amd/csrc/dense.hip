@@ -12,10 +12,15 @@
 //   k_dn_col         y_j = sum_i K(i,j) x_i      a lane owns one pack of columns and walks a strip of rows + k_dnm_fold
 //   k_dn_ata1        y = K^T.(K.x) in one pass   a workgroup keeps whole rows in registers between the two products
 //                                                (rows of <= 1024 packs); forced to one workgroup: k_dn_ata_small
+//
+// A handle made by lcg_hip_dense_create_f32 keeps K as fp32, packs of 8 bytes, and runs the *_f32 twin of each kernel: the same body
+// text behind ldpack's widening load, under the same plans, so its results are the bits of the fp64 handle of the widened matrix.  The
+// twins are copies, not one template over the pack's type: as one template the fp64 kernels compiled to other code.
 #include <cmath>
 #include <cstring>
 
 #include "dense.hpp"
+#include "lcg_hip_staging_dense_f32.h"
 
 namespace lcgh {
 
@@ -23,7 +28,7 @@ static const char *const DN_NAMES[] = {"k_dn_row", "k_dn_row_split", "k_dn_col",
                                        "k_dn_ata_small"};
 
 // ---- kernels ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double2 ldpack(const double2 *p) { return *p; }
+// (ldpack, how a pack arrives: dense.hpp)
 
 // one pack of a row times its entries of x, added to acc: real rows sum into acc.x; complex ones into (re, im)
 template <bool CX, bool CONJ>
@@ -70,6 +75,42 @@ __global__ __launch_bounds__(256) void k_dn_row(const double2 *__restrict__ K, i
         const int64_t at = (int64_t)blockIdx.y * M + i;
         if (CX) { out[2 * at] = acc.x; out[2 * at + 1] = acc.y; }
         else out[at] = acc.x;
+    }
+}
+
+// k_dn_row on fp32 packs (real): the same lanes, packs and order of additions behind the widening load, eight loads in flight
+template <int W>
+__global__ __launch_bounds__(256) void k_dn_row_f32(const float2 *__restrict__ K, int64_t ldp, int M, int N, int NP, int pps,
+                                                    const double *__restrict__ x, double *__restrict__ out)
+{
+    const int sub = threadIdx.x % W;
+    const int i = blockIdx.x * (256 / W) + threadIdx.x / W;
+    const int p0 = blockIdx.y * pps;
+    const int p1 = i < M ? min(NP, p0 + pps) : p0;        // (a row beyond M walks nothing but still joins the butterfly)
+    const float2 *row = K + (int64_t)min(i, M - 1) * ldp;
+    double2 acc = make_double2(0.0, 0.0);
+    int p = p0 + sub;
+    for (; p + 7 * W < p1; p += 8 * W) {
+        double2 k[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) k[u] = ldpack(row + p + u * W);
+#pragma unroll
+        for (int u = 0; u < 8; u++) row_term<false, false>(acc, k[u], x, p + u * W, N);
+    }
+    for (; p + 3 * W < p1; p += 4 * W) {
+        const double2 k0 = ldpack(row + p), k1 = ldpack(row + p + W), k2 = ldpack(row + p + 2 * W), k3 = ldpack(row + p + 3 * W);
+        row_term<false, false>(acc, k0, x, p, N);
+        row_term<false, false>(acc, k1, x, p + W, N);
+        row_term<false, false>(acc, k2, x, p + 2 * W, N);
+        row_term<false, false>(acc, k3, x, p + 3 * W, N);
+    }
+    for (; p < p1; p += W) row_term<false, false>(acc, ldpack(row + p), x, p, N);
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) {
+        acc.x += __shfl_xor(acc.x, o, W);
+    }
+    if (sub == 0 && i < M) {
+        out[(int64_t)blockIdx.y * M + i] = acc.x;
     }
 }
 
@@ -125,6 +166,45 @@ __global__ __launch_bounds__(256) void k_dn_col(const double2 *__restrict__ K, i
         const int64_t j = 2 * (int64_t)p;           // c128: the pack's (re, im); fp64: its two columns
         o[j] = acc.x;
         if (CX || j + 1 < N) o[j + 1] = acc.y;
+    }
+}
+
+// k_dn_col on fp32 packs (real): the same mapping and order behind the widening load, sixteen rows in flight
+template <bool SQ>
+__global__ __launch_bounds__(256) void k_dn_col_f32(const float2 *__restrict__ K, int64_t ldp, int M, int N, int NP, int CW, int rps,
+                                                    const double *__restrict__ x, double *__restrict__ out, int64_t n_out)
+{
+    constexpr int UN = 16;
+    __shared__ double2 sh[256];
+    const int RG = 256 / CW;
+    const int cp = threadIdx.x % CW, rg = threadIdx.x / CW;
+    const int p = blockIdx.x * CW + cp;
+    const bool live = p < NP;
+    const int r0 = blockIdx.y * rps, r1 = min(M, r0 + rps);
+    double2 acc = make_double2(0.0, 0.0);
+    if (live) {
+        const float2 *col = K + p;
+        int i = r0 + rg;
+        for (; i + (UN - 1) * RG < r1; i += UN * RG) {
+            double2 k[UN];
+#pragma unroll
+            for (int u = 0; u < UN; u++) k[u] = ldpack(col + (int64_t)(i + u * RG) * ldp);
+#pragma unroll
+            for (int u = 0; u < UN; u++) col_term<false, false, SQ>(acc, k[u], x, i + u * RG);
+        }
+        for (; i < r1; i += RG) col_term<false, false, SQ>(acc, ldpack(col + (int64_t)i * ldp), x, i);
+    }
+    if (RG > 1) {
+        sh[threadIdx.x] = acc;
+        __syncthreads();
+        if (rg == 0)
+            for (int g = 1; g < RG; g++) { const double2 v = sh[g * CW + cp]; acc.x += v.x; acc.y += v.y; }
+    }
+    if (rg == 0 && live) {
+        double *o = out + (int64_t)blockIdx.y * n_out;
+        const int64_t j = 2 * (int64_t)p;
+        o[j] = acc.x;
+        if (j + 1 < N) o[j + 1] = acc.y;
     }
 }
 
@@ -219,6 +299,94 @@ __global__ __launch_bounds__(BS) void k_dn_ata1(const double2 *__restrict__ K, i
     }
 }
 
+// k_dn_ata1 on fp32 packs: the rows stay floats in registers between the two products (half the registers) and are widened where
+// they are used; the same mapping and order
+template <int BS, int U, int RB>
+__global__ __launch_bounds__(BS) void k_dn_ata1_f32(const float2 *__restrict__ K, int64_t ldp, int M, int N, int NP, int CW,
+                                                     const double *__restrict__ x, double *__restrict__ out)
+{
+    __shared__ double2 sh[BS];
+    __shared__ double sw[RB][BS / 64];
+    const int RG = BS / CW;
+    const int cp = threadIdx.x % CW, rg = threadIdx.x / CW;
+    const int wave = threadIdx.x / 64;
+    double xa[U], xb[U];
+    double2 acc[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const int p = cp + u * CW, j = 2 * p;
+        xa[u] = p < NP ? x[j] : 0.0;
+        xb[u] = p < NP && j + 1 < N ? x[j + 1] : 0.0;
+        acc[u] = make_double2(0.0, 0.0);
+    }
+    const int step = RG * RB;
+    for (int64_t base = (int64_t)blockIdx.x * step; base < M; base += (int64_t)gridDim.x * step) {
+        float2 k[RB][U];
+        double s[RB];
+#pragma unroll
+        for (int r = 0; r < RB; r++) {
+            const int64_t i = base + r * RG + rg;
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int p = cp + u * CW;
+                k[r][u] = i < M && p < NP ? K[i * ldp + p] : make_float2(0.0f, 0.0f);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < RB; r++) {
+            s[r] = 0.0;
+#pragma unroll
+            for (int u = 0; u < U; u++) { const double2 kk = ldpack(&k[r][u]); s[r] += kk.x * xa[u] + kk.y * xb[u]; }
+        }
+        if (CW <= 64) {
+            for (int o = CW / 2; o > 0; o >>= 1) {
+#pragma unroll
+                for (int r = 0; r < RB; r++) s[r] += __shfl_xor(s[r], o, 64);
+            }
+        } else {
+            for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+                for (int r = 0; r < RB; r++) s[r] += __shfl_xor(s[r], o, 64);
+            }
+            if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+                for (int r = 0; r < RB; r++) sw[r][wave] = s[r];
+            }
+            __syncthreads();
+            const int wpr = CW / 64, w0 = rg * wpr;
+#pragma unroll
+            for (int r = 0; r < RB; r++) {
+                double t = sw[r][w0];
+                for (int w = 1; w < wpr; w++) t += sw[r][w0 + w];
+                s[r] = t;
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int r = 0; r < RB; r++) {
+#pragma unroll
+            for (int u = 0; u < U; u++) { const double2 kk = ldpack(&k[r][u]); acc[u].x += kk.x * s[r]; acc[u].y += kk.y * s[r]; }
+        }
+    }
+    double *o = out + (int64_t)blockIdx.x * N;
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        double2 a = acc[u];
+        if (RG > 1) {
+            __syncthreads();
+            sh[threadIdx.x] = a;
+            __syncthreads();
+            if (rg == 0)
+                for (int g = 1; g < RG; g++) { const double2 v = sh[g * CW + cp]; a.x += v.x; a.y += v.y; }
+        }
+        const int p = cp + u * CW, j = 2 * p;
+        if (rg == 0 && p < NP) {
+            o[j] = a.x;
+            if (j + 1 < N) o[j + 1] = a.y;
+        }
+    }
+}
+
 // z = x .* d (the reciprocal diagonal), n values
 template <bool CX>
 __global__ __launch_bounds__(256) void k_dn_scale(const double *__restrict__ d, const double *__restrict__ x, double *__restrict__ z, int n)
@@ -240,6 +408,25 @@ __global__ __launch_bounds__(256) void k_dn_diag(const double2 *__restrict__ K, 
     const double *row = reinterpret_cast<const double *>(K + (int64_t)i * ldp);
     if (CX) { d[2 * i] = row[2 * (int64_t)i]; d[2 * i + 1] = row[2 * (int64_t)i + 1]; }
     else d[i] = row[i];
+}
+__global__ __launch_bounds__(256) void k_dn_diag_f32(const float2 *__restrict__ K, int64_t ldp, int n, double *__restrict__ d)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    d[i] = (double)reinterpret_cast<const float *>(K + (int64_t)i * ldp)[i];
+}
+
+// Row i of an fp32 source, ld floats apart, into the handle's packs: thread (i, p) writes pack p of row i, the pad of an odd N as zero.
+// (the source is only 4-byte aligned: two scalar loads)
+__global__ __launch_bounds__(256) void k_dn_pack_f32(const float *__restrict__ src, int64_t ld, int rows, int N, int NP, float2 *__restrict__ dst,
+                                                     int64_t ldp)
+{
+    const int64_t at = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (at >= (int64_t)rows * NP) return;
+    const int64_t i = at / NP;
+    const int p = (int)(at - i * NP), j = 2 * p;
+    const float *row = src + i * ld;
+    dst[i * ldp + p] = make_float2(row[j], j + 1 < N ? row[j + 1] : 0.0f);
 }
 
 // ---- plans (pure functions of the shape: the table is sized from them when the handle is made; the row and column plans: dense.hpp)
@@ -283,6 +470,13 @@ static void row_dispatch(const lcg_hip_dense *K, const RowPlan &r, const double 
     switch (r.W) { DN_ROW_CASE(4) DN_ROW_CASE(8) DN_ROW_CASE(16) DN_ROW_CASE(32) default: DN_ROW_CASE(64) }
 #undef DN_ROW_CASE
 }
+static void row_dispatch_f32(const lcg_hip_dense *K, const RowPlan &r, const double *x, double *out, hipStream_t s)
+{
+    const dim3 grid((unsigned)cdiv(K->M, 256 / r.W), (unsigned)r.S);
+#define DN_ROW_CASE(w) case w: hipLaunchKernelGGL((k_dn_row_f32<w>), grid, dim3(256), 0, s, dn_val32(K), K->ldp, K->M, K->N, K->NP, r.pps, x, out); break;
+    switch (r.W) { DN_ROW_CASE(4) DN_ROW_CASE(8) DN_ROW_CASE(16) DN_ROW_CASE(32) default: DN_ROW_CASE(64) }
+#undef DN_ROW_CASE
+}
 
 // y[M] = K.x or conj(K).x
 static int row_product(lcg_hip_dense *K, const double *x, double *y, int conjugate, int variant, hipStream_t s)
@@ -291,7 +485,8 @@ static int row_product(lcg_hip_dense *K, const double *x, double *y, int conjuga
     const bool split = forced || (variant != DN_ROW && row_split_auto(K->M, K->NP));
     const RowPlan r = row_plan(K->M, K->NP, split, forced);
     double *out = r.S > 1 ? K->part : y;
-    if (!K->cplx) row_dispatch<false, false>(K, r, x, out, s);
+    if (K->f32) row_dispatch_f32(K, r, x, out, s);
+    else if (!K->cplx) row_dispatch<false, false>(K, r, x, out, s);
     else if (conjugate) row_dispatch<true, true>(K, r, x, out, s);
     else row_dispatch<true, false>(K, r, x, out, s);
     if (r.S > 1) fold_launch(K->part, r.S, (int64_t)K->M * (K->cplx ? 2 : 1), y, s);
@@ -307,11 +502,14 @@ static int col_product(lcg_hip_dense *K, const double *x, double *y, int conjuga
     double *out = c.RS > 1 ? K->part : y;
     const dim3 grid((unsigned)c.CT, (unsigned)c.RS);
 #define DN_COL(cx, cj, q) hipLaunchKernelGGL((k_dn_col<cx, cj, q>), grid, dim3(256), 0, s, K->val, K->ldp, K->M, K->N, K->NP, c.CW, c.rps, x, out, n_out)
-    if (sq) DN_COL(false, false, true);
+#define DN_COL32(q) hipLaunchKernelGGL((k_dn_col_f32<q>), grid, dim3(256), 0, s, dn_val32(K), K->ldp, K->M, K->N, K->NP, c.CW, c.rps, x, out, n_out)
+    if (K->f32) { if (sq) DN_COL32(true); else DN_COL32(false); }
+    else if (sq) DN_COL(false, false, true);
     else if (!K->cplx) DN_COL(false, false, false);
     else if (conjugate) DN_COL(true, true, false);
     else DN_COL(true, false, false);
 #undef DN_COL
+#undef DN_COL32
     if (c.RS > 1) fold_launch(K->part, c.RS, n_out, y, s);
     if (!sq) K->last_kernel = DN_NAMES[2];
     return launched("dense column product");
@@ -322,11 +520,19 @@ static int ata_one_pass(lcg_hip_dense *K, const double *x, double *y, bool small
     const AtaPlan a = ata_plan(K->M, K->NP, K->N, small);
     double *out = a.G > 1 ? K->part : y;
 #define DN_ATA(bs, u, rb) hipLaunchKernelGGL((k_dn_ata1<bs, u, rb>), dim3((unsigned)a.G), dim3(bs), 0, s, K->val, K->ldp, K->M, K->N, K->NP, a.CW, x, out)
-    if (small) DN_ATA(1024, 1, 2);
+#define DN_ATA32(bs, u, rb) hipLaunchKernelGGL((k_dn_ata1_f32<bs, u, rb>), dim3((unsigned)a.G), dim3(bs), 0, s, dn_val32(K), K->ldp, K->M, K->N, K->NP, a.CW, x, out)
+    if (K->f32) {
+        if (small) DN_ATA32(1024, 1, 2);
+        else if (a.U == 1) DN_ATA32(256, 1, 4);
+        else if (a.U == 2) DN_ATA32(256, 2, 4);
+        else DN_ATA32(256, 4, 2);
+    }
+    else if (small) DN_ATA(1024, 1, 2);
     else if (a.U == 1) DN_ATA(256, 1, 4);
     else if (a.U == 2) DN_ATA(256, 2, 4);
     else DN_ATA(256, 4, 2);
 #undef DN_ATA
+#undef DN_ATA32
     if (a.G > 1) fold_launch(K->part, a.G, K->N, y, s);
     K->last_kernel = small ? DN_NAMES[5] : DN_NAMES[4];
     return launched("dense K^T.K.x");
@@ -375,13 +581,13 @@ static void dense_release(lcg_hip_dense *K)
 }
 
 // the handle with its device arrays, K zeroed (pads and slack included)
-static int dense_alloc(lcg_hip_dense **out, int M, int N, bool cplx)
+static int dense_alloc(lcg_hip_dense **out, int M, int N, bool cplx, bool f32 = false)
 {
     lcg_hip_dense *K = new lcg_hip_dense;
-    K->M = M; K->N = N; K->cplx = cplx;
+    K->M = M; K->N = N; K->cplx = cplx; K->f32 = f32;
     K->NP = cplx ? N : (N + 1) / 2;
     K->ldp = K->NP;
-    const size_t bytes = (size_t)M * (size_t)K->ldp * 16 + 64;
+    const size_t bytes = (size_t)M * (size_t)K->ldp * (f32 ? 8 : 16) + 64;
     K->part_doubles = table_doubles(M, N, K->NP, cplx);
     hipError_t e = hipMalloc(&K->val, bytes);
     if (e == hipSuccess) e = hipMalloc(&K->t, sizeof(double) * (cplx ? 2 : 1) * (size_t)M);
@@ -423,6 +629,51 @@ int lcg_hip_dense_create(lcg_hip_dense_t *K, int m_rows, int n_cols, const doubl
     if (ld == n_cols && (size_t)ld * es == (size_t)D->ldp * 16) e = hipMemcpyAsync(D->val, val, (size_t)m_rows * (size_t)ld * es, kind, ctx().stream);
     else e = hipMemcpy2DAsync(D->val, (size_t)D->ldp * 16, val, (size_t)ld * es, (size_t)n_cols * es, (size_t)m_rows, kind, ctx().stream);
     return dense_publish(K, D, e);
+}
+
+// An fp32 source packed on the device.  A source on the host is staged through device memory a run of rows at a time (at most 256 MiB),
+// so the transient cost of the call is that buffer, not a second matrix.
+int lcg_hip_dense_create_f32(lcg_hip_dense_t *K, int m_rows, int n_cols, const float *val, int64_t ld, int mem)
+{
+    if (!K) return arg_error("lcg_hip_dense_create_f32: the handle pointer is NULL");
+    *K = nullptr;
+    if (!val) return arg_error("lcg_hip_dense_create_f32: val is NULL");
+    if (m_rows <= 0 || n_cols <= 0) return arg_error("lcg_hip_dense_create_f32: M = %d, N = %d (both must be positive)", m_rows, n_cols);
+    if (ld < n_cols) return arg_error("lcg_hip_dense_create_f32: ld = %lld < N = %d", (long long)ld, n_cols);
+    if (mem != LCG_HIP_MEM_HOST && mem != LCG_HIP_MEM_DEVICE) return arg_error("lcg_hip_dense_create_f32: mem = %d", mem);
+    int rc = ensure_init(); if (rc) return rc;
+    lcg_hip_dense *D = nullptr;
+    rc = dense_alloc(&D, m_rows, n_cols, false, true); if (rc) return rc;
+    hipStream_t s = ctx().stream;
+    float2 *dst = reinterpret_cast<float2 *>(D->val);
+    auto pack = [&](const float *src, int64_t lds, int i0, int rows) {
+        const int64_t work = (int64_t)rows * D->NP;
+        hipLaunchKernelGGL(k_dn_pack_f32, dim3((unsigned)cdiv(work, 256)), dim3(256), 0, s, src, lds, rows, n_cols, D->NP, dst + (int64_t)i0 * D->ldp, D->ldp);
+        return hipGetLastError();
+    };
+    hipError_t e = hipSuccess;
+    const int chunk = (int)std::min<int64_t>(m_rows, std::max<int64_t>(1, ((int64_t)64 << 20) / n_cols));      // rows per launch: <= 2^26 entries
+    if (mem == LCG_HIP_MEM_DEVICE) {
+        for (int i0 = 0; i0 < m_rows && e == hipSuccess; i0 += chunk) e = pack(val + (int64_t)i0 * ld, ld, i0, std::min(chunk, m_rows - i0));
+    } else {
+        float *stage = nullptr;
+        e = hipMalloc(&stage, sizeof(float) * (size_t)chunk * (size_t)n_cols);
+        for (int i0 = 0; i0 < m_rows && e == hipSuccess; i0 += chunk) {
+            const int rows = std::min(chunk, m_rows - i0);
+            e = hipMemcpy2DAsync(stage, sizeof(float) * (size_t)n_cols, val + (int64_t)i0 * ld, sizeof(float) * (size_t)ld, sizeof(float) * (size_t)n_cols,
+                                 (size_t)rows, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) e = pack(stage, n_cols, i0, rows);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (stage) (void)hipFree(stage);
+    }
+    return dense_publish(K, D, e);
+}
+
+int lcg_hip_dense_value_bytes(lcg_hip_dense_t K)
+{
+    if (!dense_of(K, "lcg_hip_dense_value_bytes", true)) return LCG_HIP_E_ARG;
+    return K->f32 ? 4 : K->cplx ? 16 : 8;       // (complex64: a float pair)
 }
 
 int lcg_hip_dense_create_rows(lcg_hip_dense_t *K, int m_rows, int n_cols, const double *const *rows, int is_complex)
@@ -552,7 +803,8 @@ int lcg_hip_dense_build_jacobi(lcg_hip_dense_t K, int normal, double *diag_out)
         HIPCHK(hipMemcpyAsync(d.data(), K->invdiag, bytes, hipMemcpyDeviceToHost, c.stream));
     } else {
         const dim3 grid((unsigned)cdiv(n, 256));
-        if (K->cplx) hipLaunchKernelGGL(k_dn_diag<true>, grid, dim3(256), 0, c.stream, K->val, K->ldp, n, K->invdiag);
+        if (K->f32) hipLaunchKernelGGL(k_dn_diag_f32, grid, dim3(256), 0, c.stream, dn_val32(K), K->ldp, n, K->invdiag);
+        else if (K->cplx) hipLaunchKernelGGL(k_dn_diag<true>, grid, dim3(256), 0, c.stream, K->val, K->ldp, n, K->invdiag);
         else hipLaunchKernelGGL(k_dn_diag<false>, grid, dim3(256), 0, c.stream, K->val, K->ldp, n, K->invdiag);
         int rc = launched("dense diagonal"); if (rc) return rc;
         HIPCHK(hipMemcpyAsync(d.data(), K->invdiag, bytes, hipMemcpyDeviceToHost, c.stream));

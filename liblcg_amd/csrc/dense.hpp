@@ -1,7 +1,7 @@
 // dense.hpp -- what the dense units share (dense.hip: the single-vector products; dense_multi.hip: the k-wide kernels and their host
 // flow for real and complex128 handles; dense_multi_cplx.hip: the complex entries; dense_c64.hip: everything of a complex64 handle):
 // the handle and the plans of the row and column forms.  Not installed.
-// DESIGN.md sections 14, 19, 20 and 25.
+// DESIGN.md sections 14, 19, 20, 25 and 27.
 #pragma once
 
 #include <algorithm>
@@ -24,9 +24,12 @@ struct lcg_hip_dense {
     bool cplx = false;
     bool c64 = false;           // the element type is complex64 (lcg_hip_dense_create_c64; cplx stays false): a pack is two (re, im) float pairs,
                                 // part and invdiag hold floats, t is not allocated.  Served by dense_c64.hip's entries and by no other
+    bool f32 = false;           // the entries are stored as fp32 (lcg_hip_dense_create_f32; cplx and c64 stay false): a pack is the 8 bytes of
+                                // columns 2p and 2p + 1 and val points at float2; everything else is a real fp64 handle's and every entry for
+                                // one serves it.  Looked at where a kernel is launched on val, nowhere else
     int64_t ldp = 0;            // packs per stored row
     int NP = 0;                 // packs that hold a row's entries: N (c128) or ceil(N / 2)
-    double2 *val = nullptr;     // M * ldp packs + slack
+    double2 *val = nullptr;     // M * ldp packs + slack (f32: float2 packs, dn_val32)
     double *t = nullptr;        // the M-vector between the two products of K^T.K.x
     double *part = nullptr;     // the partial-sum table
     int64_t part_doubles = 0;
@@ -76,6 +79,13 @@ static inline ColPlan col_plan(int M, int NP)
     c.RS = (int)cdiv(M, c.rps);
     return c;
 }
+
+// How a pack of K arrives: 16 bytes as they are, or (f32 handles) 8 bytes of two floats widened to the same double2 -- exactly, a
+// float is a double.  The one seam between the element widths: everything after the load is the fp64 code, so an fp32 handle gives
+// the bits of the fp64 handle of the widened matrix
+__device__ __forceinline__ double2 ldpack(const double2 *p) { return *p; }
+__device__ __forceinline__ double2 ldpack(const float2 *p) { const float2 v = *p; return make_double2((double)v.x, (double)v.y); }
+static inline const float2 *dn_val32(const lcg_hip_dense *K) { return reinterpret_cast<const float2 *>(K->val); }
 
 // doubles per element of K and of a block of vectors: the one place the complex factor 2 of the k-wide slot sizes comes from
 static inline int dn_words(const lcg_hip_dense *K) { return K->cplx ? 2 : 1; }

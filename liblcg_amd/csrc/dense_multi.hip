@@ -1,7 +1,8 @@
 // dense_multi.hip -- dense operators over k = 2, 4, 8 right-hand sides: K.X, K^T.X, K^T.(K.X) with K read ONCE for all k columns,
 // and the operator of the batched loops (solvers_multi.hip: lcg_hip_dense_lcg_multi, lcg_hip_dense_lpcg_multi; solvers_multi_cplx.hip:
 // the complex ones) with the sum they take after it.  One GPU.  The kernels and the host flow serve real fp64 and complex128 handles;
-// the real entries are here, the complex ones in dense_multi_cplx.hip.  DESIGN.md sections 19 and 20.
+// the real entries are here, the complex ones in dense_multi_cplx.hip.  A real handle that stores K as fp32 runs the
+// *_f32 twins of the real kernels under the same plans and gives the fp64 handle's bits.  DESIGN.md sections 19, 20 and 27.
 //
 // Blocks of vectors are multi.hpp's: X[i * k + j] is row i of column j, the base 16-byte aligned (complex: multi_cplx.hpp's, column j
 // of row i is the 16-byte piece i * k + j).  The kernels are the k-wide twins of dense.hip's, on the same storage (rows of 16-byte
@@ -85,6 +86,9 @@ struct DnCplx {
 // The row forms stay two kernels.  As one template over the element trait they compiled to the same registers, LDS and occupancy, but
 // not to the same code for the real K = 4 and K = 8 instantiations, and the real K = 8 product at 8192^2 measured 0.5 % below the parent in
 // three alternating runs out of three (profiles/multi_product_rates.txt).
+// The fp32 twins (k_dnm_row_f32, k_dnm_col_f32: a handle made by lcg_hip_dense_create_f32) are copies for the same reason: with one
+// body shared between the two pack types, 24 of this file's 61 kernels compiled to other instructions; beside the copies all are
+// identical to what they were.
 
 // one pack of row i (columns 2p, 2p + 1) times rows 2p and 2p + 1 of X.  Odd N: the last pack's pad entry never reads row N of X
 template <int K2>
@@ -143,6 +147,72 @@ __global__ __launch_bounds__(256) void k_dnm_row(const double2 *__restrict__ Kv,
 #pragma unroll
         for (int r = 0; r < RR; r++) {
             const double2 kk = row[r][p];
+            fma_row<K2>(acc[r], kk.x, xa); fma_row<K2>(acc[r], kk.y, xb);
+        }
+    }
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) {
+#pragma unroll
+        for (int r = 0; r < RR; r++)
+#pragma unroll
+            for (int h = 0; h < K2; h++) { acc[r][h].x += __shfl_xor(acc[r][h].x, o, W); acc[r][h].y += __shfl_xor(acc[r][h].y, o, W); }
+    }
+    if (sub == 0) {
+#pragma unroll
+        for (int r = 0; r < RR; r++) {
+            if (i0 + r < M) {
+                m2d *o = reinterpret_cast<m2d *>(out) + ((int64_t)blockIdx.y * M + i0 + r) * K2;
+#pragma unroll
+                for (int h = 0; h < K2; h++) o[h] = acc[r][h];
+            }
+        }
+    }
+}
+
+// k_dnm_row on fp32 packs (an fp32 handle): the same lanes, packs and order of additions behind ldpack's widening load.
+// A copy, not a shared template: see above.  fp32 packs are half the bytes, so a lane keeps twice as many in flight where the registers
+// allow it -- at K = 8 the rows of X in flight, not the packs, fill them
+template <int K, int W>
+__global__ __launch_bounds__(256) void k_dnm_row_f32(const float2 *__restrict__ Kv, int64_t ldp, int M, int N, int NP, int pps,
+                                                     const double *__restrict__ X, double *__restrict__ out, const int *done)
+{
+    constexpr int K2 = K / 2, RR = K / 2;
+    constexpr int UN = K == 2 ? 8 : K == 4 ? 4 : 2;
+    if (done && *done) return;
+    const int sub = threadIdx.x % W;
+    const int64_t i0 = ((int64_t)blockIdx.x * (256 / W) + threadIdx.x / W) * RR;
+    const int p0 = blockIdx.y * pps;
+    const int p1 = i0 < M ? min(NP, p0 + pps) : p0;       // (a group beyond M walks nothing but still joins the butterfly)
+    const float2 *row[RR];
+#pragma unroll
+    for (int r = 0; r < RR; r++) row[r] = Kv + min(i0 + r, (int64_t)M - 1) * ldp;     // (rows beyond M re-read the last one; never written)
+    const m2d *Xv = reinterpret_cast<const m2d *>(X);
+    m2d acc[RR][K2];
+#pragma unroll
+    for (int r = 0; r < RR; r++)
+#pragma unroll
+        for (int h = 0; h < K2; h++) acc[r][h] = (m2d)(0.0);
+    int p = p0 + sub;
+    for (; p + (UN - 1) * W < p1; p += UN * W) {
+        double2 kk[UN][RR];
+        m2d xa[UN][K2], xb[UN][K2];
+#pragma unroll
+        for (int u = 0; u < UN; u++)
+#pragma unroll
+            for (int r = 0; r < RR; r++) kk[u][r] = ldpack(row[r] + p + u * W);
+#pragma unroll
+        for (int u = 0; u < UN; u++) row_xload<K2>(xa[u], xb[u], Xv, p + u * W, N);
+#pragma unroll
+        for (int u = 0; u < UN; u++)
+#pragma unroll
+            for (int r = 0; r < RR; r++) { fma_row<K2>(acc[r], kk[u][r].x, xa[u]); fma_row<K2>(acc[r], kk[u][r].y, xb[u]); }
+    }
+    for (; p < p1; p += W) {
+        m2d xa[K2], xb[K2];
+        row_xload<K2>(xa, xb, Xv, p, N);
+#pragma unroll
+        for (int r = 0; r < RR; r++) {
+            const double2 kk = ldpack(row[r] + p);
             fma_row<K2>(acc[r], kk.x, xa); fma_row<K2>(acc[r], kk.y, xb);
         }
     }
@@ -342,6 +412,76 @@ __global__ __launch_bounds__(256) void k_dnm_col(const double2 *__restrict__ Kv,
     }
 }
 
+// k_dnm_col<DnReal<K>, K> on fp32 packs: the same mapping and order behind the widening load (a copy, as k_dnm_row_f32)
+template <int K>
+__global__ __launch_bounds__(256) void k_dnm_col_f32(const float2 *__restrict__ Kv, int64_t ldp, int M, int N, int NP, int CW, int rps,
+                                                     const double *__restrict__ X, double *__restrict__ out, int64_t n_out, const int *done)
+{
+    using E = DnReal<K>;
+    constexpr int A = E::A, UN = E::COL_UN;
+    static_assert(E::OR * A == K, "a pack's sums are K pieces");
+    __shared__ m2d sh[K][256];
+    if (done && *done) return;
+    const int RG = 256 / CW;
+    const int cp = threadIdx.x % CW, rg = threadIdx.x / CW;
+    const int p = blockIdx.x * CW + cp;
+    const bool live = p < NP;
+    const int r0 = blockIdx.y * rps, r1 = min(M, r0 + rps);
+    const m2d *Xv = reinterpret_cast<const m2d *>(X);
+    m2d acc[K];
+#pragma unroll
+    for (int h = 0; h < K; h++) acc[h] = (m2d)(0.0);
+    if (live) {
+        const float2 *col = Kv + p;
+        int i = r0 + rg;
+        for (; i + (UN - 1) * RG < r1; i += UN * RG) {
+            double2 kk[UN];
+            m2d xv[UN][A];
+#pragma unroll
+            for (int u = 0; u < UN; u++) kk[u] = ldpack(col + (int64_t)(i + u * RG) * ldp);
+#pragma unroll
+            for (int u = 0; u < UN; u++)
+#pragma unroll
+                for (int h = 0; h < A; h++) xv[u][h] = Xv[(int64_t)(i + u * RG) * A + h];
+#pragma unroll
+            for (int u = 0; u < UN; u++) E::col_term(acc, kk[u], xv[u]);
+        }
+        for (; i < r1; i += RG) {
+            const double2 kk = ldpack(col + (int64_t)i * ldp);
+            m2d xv[A];
+#pragma unroll
+            for (int h = 0; h < A; h++) xv[h] = Xv[(int64_t)i * A + h];
+            E::col_term(acc, kk, xv);
+        }
+    }
+    if (RG > 1) {       // (uniform over the workgroup)
+#pragma unroll
+        for (int h = 0; h < A; h++) {
+            sh[h][threadIdx.x] = acc[h];
+            if (E::OR == 2) sh[A + h][threadIdx.x] = acc[A + h];
+        }
+        __syncthreads();
+        if (rg == 0)
+            for (int g = 1; g < RG; g++) {
+#pragma unroll
+                for (int h = 0; h < A; h++) {
+                    acc[h] += sh[h][g * CW + cp];
+                    if (E::OR == 2) acc[A + h] += sh[A + h][g * CW + cp];
+                }
+            }
+    }
+    if (rg == 0 && live) {
+        const int64_t j = E::OR * (int64_t)p;           // the pack's first row of Y
+        m2d *o = reinterpret_cast<m2d *>(out + (int64_t)blockIdx.y * n_out) + j * A;
+#pragma unroll
+        for (int h = 0; h < A; h++) o[h] = acc[h];
+        if (E::OR == 2 && j + 1 < N) {
+#pragma unroll
+            for (int h = 0; h < A; h++) o[A + h] = acc[A + h];
+        }
+    }
+}
+
 // Column j's Y_j . U_j as one partial sum per workgroup and table row at part[row * MM_MG + blockIdx.x]: real, row j; complex (CX), the
 // UNCONJUGATED sum's re in row 2 j and im in row 2 j + 1 -- the table formats spmm_launch and cspmm_launch leave.  A workgroup of 64 * G
 // threads (G = the 16-byte pieces of a row: K / 2 real, K complex) owns rpb rows (a multiple of 64); its 64 row lanes r = tid / G add
@@ -436,6 +576,14 @@ static void row_dispatch(const lcg_hip_dense *D, const RowPlan &r, const double 
     switch (r.W) { DNM_ROW_CASE(4) DNM_ROW_CASE(8) DNM_ROW_CASE(16) DNM_ROW_CASE(32) default: DNM_ROW_CASE(64) }
 #undef DNM_ROW_CASE
 }
+template <int K>
+static void row_dispatch_f32(const lcg_hip_dense *D, const RowPlan &r, const double *X, double *out, hipStream_t s, const int *done)
+{
+    const dim3 grid((unsigned)cdiv(cdiv(D->M, K / 2), 256 / r.W), (unsigned)r.S);
+#define DNM_ROW_CASE(w) case w: hipLaunchKernelGGL((k_dnm_row_f32<K, w>), grid, dim3(256), 0, s, dn_val32(D), D->ldp, D->M, D->N, D->NP, r.pps, X, out, done); break;
+    switch (r.W) { DNM_ROW_CASE(4) DNM_ROW_CASE(8) DNM_ROW_CASE(16) DNM_ROW_CASE(32) default: DNM_ROW_CASE(64) }
+#undef DNM_ROW_CASE
+}
 template <int K, bool CONJ>
 static void zrow_dispatch(const lcg_hip_dense *D, const RowPlan &r, const double *X, double *out, hipStream_t s, const int *done)
 {
@@ -456,7 +604,8 @@ int dnm_row_product(lcg_hip_dense *D, int k, const double *X, double *Y, int con
     double *out = r.S > 1 ? D->multi->part : Y;
     multi_k(k, [&](auto K) {
         constexpr int KK = decltype(K)::value;
-        if (!D->cplx) row_dispatch<KK>(D, r, X, out, s, done);
+        if (D->f32) row_dispatch_f32<KK>(D, r, X, out, s, done);
+        else if (!D->cplx) row_dispatch<KK>(D, r, X, out, s, done);
         else if (conjugate) zrow_dispatch<KK, true>(D, r, X, out, s, done);
         else zrow_dispatch<KK, false>(D, r, X, out, s, done);
         return 0;
@@ -477,7 +626,8 @@ int dnm_col_product(lcg_hip_dense *D, int k, const double *X, double *Y, int con
 #define DNM_COL(...) hipLaunchKernelGGL((k_dnm_col<__VA_ARGS__, KK>), grid, dim3(256), 0, s, D->val, D->ldp, D->M, D->N, D->NP, c.CW, c.rps, X, out, n_out, done)
     multi_k(k, [&](auto K) {
         constexpr int KK = decltype(K)::value;
-        if (!D->cplx) DNM_COL(DnReal<KK>);
+        if (D->f32) hipLaunchKernelGGL((k_dnm_col_f32<KK>), grid, dim3(256), 0, s, dn_val32(D), D->ldp, D->M, D->N, D->NP, c.CW, c.rps, X, out, n_out, done);
+        else if (!D->cplx) DNM_COL(DnReal<KK>);
         else if (conjugate) DNM_COL(DnCplx<KK, true>);
         else DNM_COL(DnCplx<KK, false>);
         return 0;
