@@ -1,6 +1,6 @@
 // csr_sym.hip -- symmetric run stretches: half the value stream, a row slice per XCD.
 //
-// A run stretch (csr.hip: k_pk_stretch_flags) whose offset table is antisymmetric and whose values mirror each other BIT FOR BIT --
+// A run stretch (csr_packed.hip: k_pk_stretch_flags) whose offset table is antisymmetric and whose values mirror each other BIT FOR BIT --
 // val(i, k) == val(i + off[k], 2p - k) for the lower slots k < p -- needs only its diagonal and upper diagonals: a lower entry of row
 // i is the upper entry of its partner row.  k_sym_pack lays those out tile by tile (csr_sym.hpp: SymRun) in the order the product's
 // workgroups are dispatched, k_spmv_ldsp_sym multiplies the blocks of the stretch's sliced range from it -- values straight into
@@ -47,11 +47,21 @@ bool sym_runs_wanted(const CsrPart &P)
 
 void sym_runs_free(const CsrPart &P)
 {
-    if (P.pk_sym_H) (void)hipFree(P.pk_sym_H);
-    P.pk_sym_H = nullptr; P.pk_sym = SymRun(); P.pk_sym_tiles = 0; P.sym_why = "not tried";
+    if (PackedPlan *Kp = packed_plan(P)) {
+        PackedPlan &K = *Kp;
+        if (K.sym_H) (void)hipFree(K.sym_H);
+        K.sym_H = nullptr; K.sym = SymRun(); K.sym_tiles = 0;
+    }
+    P.sym_why = "not tried";
 }
 
-int64_t sym_runs_bytes(const CsrPart &P) { return P.pk_sym.NX > 0 ? 8 * P.pk_sym_tiles * (int64_t)(P.pk_sym.p + 1) * PK_R : 0; }
+int64_t sym_runs_bytes(const CsrPart &P)
+{
+    const PackedPlan *Kp = packed_plan(P);
+    if (!Kp) return 0;
+    const PackedPlan &K = *Kp;
+    return K.sym.NX > 0 ? 8 * K.sym_tiles * (int64_t)(K.sym.p + 1) * PK_R : 0;
+}
 
 // offset of slot k (uniform) from the stretch's table
 __device__ __forceinline__ int sym_off(const SymRun &sr, int k) { return sr.off[(k % 4) * sr.TQ + k / 4]; }
@@ -86,7 +96,7 @@ __global__ __launch_bounds__(VB) void k_sym_pack(SymRun sr, int b0, int s0, cons
 
 // Workgroup w of the sliced range: block sym_block_of(w), own tile Q + w (one slice: block sym_group_block_of(w), own tile
 // Q + block - inner0: see below).  Lane (row r, wavefront j0) takes slots k = j0, j0 + 4, ...
-// as in a run block (csr.hip: run_block).  A slot k >= p reads H[own tile][k - p][r]; a slot k < p reads the partner row's upper
+// as in a run block (csr_packed.hip: run_block).  A slot k >= p reads H[own tile][k - p][r]; a slot k < p reads the partner row's upper
 // entry, H[tile of row i + off[k]][p - k][(i + off[k]) & 63] -- the wavefront's 64 partner rows lie in two consecutive blocks, whose
 // tiles are scalar arithmetic; a lane only selects between the two bases.  Values and x gathers go out together; the additions run
 // in run_block's order, the carried dot's partial keeps the BLOCK's slot and its u comes from the gather of slot p.
@@ -173,13 +183,13 @@ int sym_group_in_use(const CsrPart &P)
 {
     static const int env = [] { const char *e = std::getenv("LCG_HIP_SYM_GROUP"); return e ? atoi(e) : 0; }();     // A/B runs: 1 / 2 / 4 / 8 for the whole process
     const auto ok = [](int v) { return v == 1 || v == 2 || v == 4 || v == 8; };
-    if (P.pk_sym.NX != 1) return 1;                     // (slices have their own placement)
+    if (packed_plan(P)->sym.NX != 1) return 1;                    // (slices have their own placement)
     return ok(env) ? env : SYM_GROUP_DEFAULT;
 }
 
 void sym_runs_launch(const CsrPart &P, bool dot, const double *x, double *y, hipStream_t s, const int *done, const DotPlan &dp)
 {
-    SymRun sr = P.pk_sym;
+    SymRun sr = packed_plan(P)->sym;
     sr.G = sym_group_in_use(P);
     const dim3 g((unsigned)(sr.NX * sr.S));
     const bool small = 2 * sr.p + 1 <= 24;
@@ -197,8 +207,9 @@ void sym_runs_launch(const CsrPart &P, bool dot, const double *x, double *y, hip
 void sym_runs_build(const CsrPart &P, hipStream_t s)
 {
     sym_runs_free(P);
+    PackedPlan &K = *packed_plan(P);        // (called by packed_build: the plan is there)
     const int NX = sym_nx_of(P);
-    const RunStretches &rs = P.pk_rs;
+    const RunStretches &rs = K.rs;
     int order[RS_MAX];
     for (int i = 0; i < RS_MAX; i++) order[i] = i;
     std::stable_sort(order, order + rs.n, [&](int a, int c) { return rs.s[a].b1 - rs.s[a].b0 > rs.s[c].b1 - rs.s[c].b0; });
@@ -224,13 +235,13 @@ void sym_runs_build(const CsrPart &P, hipStream_t s)
         (void)hipGetLastError();
         if (bad) { if (oi == 0) P.sym_why = "refused: the values do not mirror each other bit for bit"; continue; }
         const long tiles = (long)sr.Q + (long)NX * sr.S;
-        if (hipMalloc(&P.pk_sym_H, sizeof(double) * (size_t)tiles * (size_t)(p + 1) * PK_R) != hipSuccess) {
-            (void)hipGetLastError(); P.pk_sym_H = nullptr; if (oi == 0) P.sym_why = "refused: no memory for the half store"; break;
+        if (hipMalloc(&K.sym_H, sizeof(double) * (size_t)tiles * (size_t)(p + 1) * PK_R) != hipSuccess) {
+            (void)hipGetLastError(); K.sym_H = nullptr; if (oi == 0) P.sym_why = "refused: no memory for the half store"; break;
         }
-        hipLaunchKernelGGL(k_sym_pack, dim3((unsigned)tiles), dim3(VB), 0, s, sr, r.b0, r.s0, P.val, P.pk_sym_H);
-        if (hipGetLastError() != hipSuccess) { (void)hipFree(P.pk_sym_H); P.pk_sym_H = nullptr; if (oi == 0) P.sym_why = "refused: the half store could not be written"; break; }
-        sr.H = P.pk_sym_H;
-        P.pk_sym = sr; P.pk_sym_tiles = tiles;
+        hipLaunchKernelGGL(k_sym_pack, dim3((unsigned)tiles), dim3(VB), 0, s, sr, r.b0, r.s0, P.val, K.sym_H);
+        if (hipGetLastError() != hipSuccess) { (void)hipFree(K.sym_H); K.sym_H = nullptr; if (oi == 0) P.sym_why = "refused: the half store could not be written"; break; }
+        sr.H = K.sym_H;
+        K.sym = sr; K.sym_tiles = tiles;
         P.sym_why = "taken";
         break;
     }

@@ -10,7 +10,6 @@
 #include <vector>
 
 #include "lcg_hip.h"
-#include "csr_sym.hpp"
 
 namespace lcgh {
 
@@ -99,10 +98,10 @@ struct DotPlan {
     int yy = 0;
     int stride = AXP_CAP;   // distance of the y.y sums from the y.u sums in `part`
     int ux = 0;             // u is the product's own x (CG, PCG: d.Ad): a run block that holds its diagonal takes u from its gathers
-    int dof = 1;            // k_spmv_ldsp, long rows: a packed column field stands for `dof` consecutive columns (csr.hip: k_pk_dof)
+    int dof = 1;            // k_spmv_ldsp, long rows: a packed column field stands for `dof` consecutive columns (csr_packed.hip: k_pk_dof)
 };
 
-// Stretches of run blocks (csr.hip: k_pk_stretch / the stretch path of k_spmv_ldsp): consecutive full 64-row run blocks [b0, b1) with the
+// Stretches of run blocks (csr_packed.hip: k_pk_stretch / the stretch path of k_spmv_ldsp): consecutive full 64-row run blocks [b0, b1) with the
 // same L, the same offsets column(row 0, k) - first row and entries that follow each other without a gap.  A block of a stretch
 // derives everything it would load from the per-block plan from its number: it travels in the kernel arguments like the two plans above.
 constexpr int RS_MAX = 4;
@@ -264,29 +263,15 @@ struct CsrPart {
     bool padded = false;           // >= 64 readable bytes follow col[nnz] and val[nnz]
     mutable int slice_R = 0;       // rows per block the next field was computed for (0 = not yet)
     mutable int max_slice = 0;     // largest block slice, entries (csr.hip: k_max_slice)
-    // packed column indices for the one-window kernel (csr.hip: "packed columns"), built on first use
+    // packed column indices for the one-window kernel (csr_packed.hip), plan built on first use
     mutable int pk_mode = -1;      // -1 auto (large real matrices), 0 never, 1 whenever eligible
-    mutable int pk_state = 0;      // 0 not tried, 1 ready, -1 not eligible
-    mutable int *pk_base = nullptr, *pk_ofs = nullptr;     // per block of 64 rows: smallest column, first group
-    mutable void *pk_data = nullptr;                        // 16 bytes per group of 6 entries
-    mutable int pk_maxrow = 0;                              // longest row (chooses the gather batch of the kernel)
-    mutable int pk_bits = 21;                               // width of a packed column: 18 (seven per group) or 21 (six)
-    mutable int pk_R = 64;                                  // rows per block of the packed form (64; 32 / 16 for long rows)
-    mutable int pk_dof = 1;                                 // long rows: every row's entries come in groups of pk_dof consecutive columns (one packed field per group)
-    mutable int pk_runs = 0;                                // blocks stored as runs (row 0's columns only; csr.hip: k_pk_meta)
-    mutable int pk_tpls = 0;                                // blocks stored as templates (<= 32 diagonals + a mask per row)
-    mutable long pk_groups = 0;                             // 16-byte groups of the packed columns
+    mutable int pk_state = 0;      // 0 not tried, 1 ready, 2 ready for k_spmv_run1 only (run blocks' columns), -1 not eligible
+    mutable void *pk_plan = nullptr;                        // csr_plan.hpp: PackedPlan, owned (packed_free)
     mutable int rs_mode = 0;                                // run stretches: 0 (default: measured slower) every run block loads its per-block plan, 1 the blocks of a stretch do not
-    mutable RunStretches pk_rs;                             // the (up to four) longest stretches of run blocks, found with the packed form
-    mutable int *pk_rs_off = nullptr;                       // their offset tables
-    mutable long pk_rs_blocks = 0, pk_rs_groups = 0;        // blocks they cover; 16-byte groups of per-block columns those blocks no longer read
     // symmetric run stretch (csr_sym.hip): the longest stretch whose values mirror each other bit for bit reads a half store
     mutable int sym_mode = -1;                              // -1 automatic (what the automatic mode takes), 0 off, 1 forced
     mutable int sym_nx = 0;                                 // slices of the sliced range: 0 the process's default, 1, 2, 4, 8
     bool sym_whole = false;                                 // the main part of a real fp64 handle while it is not sharded (set where the handle is made, cleared by lcg_hip_csr_distribute): no shard, no op(A) copy, no range
-    mutable SymRun pk_sym;                                  // NX = 0: none
-    mutable double *pk_sym_H = nullptr;                     // the half store
-    mutable long pk_sym_tiles = 0;                          // its tiles
     mutable const char *sym_why = "not tried";              // why the stretch is (not) taken
     mutable double *dot_part = nullptr;                     // [2][dot_cap]: per-block (per-chunk) sums of a product that carries its dot (k_spmv_ldsp<DOT>, k_tile_spmv2<DOT>)
     mutable long dot_cap = 0;
@@ -379,7 +364,11 @@ int spmv_launch(const CsrPart &P, bool is_complex, int variant, double mean_row,
 // the same product with `pp.nblocks` pushing blocks in front of the grid (comm.hip, dist mode 2)
 int spmv_launch_push(const CsrPart &P, bool is_complex, int variant, double mean_row, const double *x, double *y,
                      hipStream_t s, const int *done_flag, const PushPlan &pp);
-void sym_runs_reset(CsrPart &P);            // csr.hip: the half store goes and, where the part's mode wants one, its packed plan is built again at the next product
+// csr_packed.hip: everything a part's packed plan holds goes (stretch tables and half store included) and the part is "not tried"
+// again -- the one place that releases it (the part's stream work must have ended).  part_goes: the part is being destroyed; otherwise
+// the released plan's numbers stay readable for the status queries, as they always did
+void packed_free(const CsrPart &P, bool part_goes = false);
+void sym_runs_reset(CsrPart &P);            // csr_packed.hip: the half store goes and, where the part's mode wants one, its packed plan is built again at the next product
 void sym_runs_free(const CsrPart &P);       // csr_sym.hip: the half store of a part's symmetric run stretch goes (the part's stream work must have ended)
 int jacobi_launch(const lcg_hip_csr *A, const double *x, double *z, int n, hipStream_t s);       // csr_build.hip
 // y = A.x with the sums y.u (and y.y) riding in the product: 1 = done, *slots partial sums wait in part[0 .. *slots) (and

@@ -1,4 +1,4 @@
-"""-m gpu: fuzz of the packed-column A.x (csr.hip: k_spmv_ldsp) against the plain kernel (bit-exact) and the
+"""-m gpu: fuzz of the packed-column A.x (csr_packed.hip: k_spmv_ldsp) against the plain kernel (bit-exact) and the
 oracle (1e-12): random ragged matrices whose 64-row blocks stay within one LDS window (<= 2240 entries), odd and
 even slice starts, empty rows, empty blocks, a full window, spans below and above the 2^21 limit (above it the
 plain kernel must answer), sizes that are not multiples of 64, more columns than rows."""
@@ -59,7 +59,7 @@ def test_packed_columns_fuzz(port):
 
 
 def test_run_blocks_fuzz(port):
-    """Mixtures of run blocks, near-runs and ragged blocks (csr.hip: k_pk_meta, the run paths of k_spmv_ldsp and k_spmv_run1):
+    """Mixtures of run blocks, near-runs and ragged blocks (csr_packed.hip: k_pk_meta, the run paths of k_spmv_ldsp and k_spmv_run1):
     every 64-row block of a matrix is drawn as (a) a run with its own L and offsets -- unsorted, with repeated columns now and
     then --, (b) the same with one entry moved, (c) rows of equal length but unrelated columns, or (d) ragged rows; L short
     (the one-wavefront-per-block kernel) or around 33 (the packed kernel).  The automatic choice must reproduce the plain

@@ -91,7 +91,7 @@ def test_packed_columns_are_bit_identical(api, port):
 
 
 def test_run_blocks_of_the_packed_form(api, port):
-    """Run blocks (csr.hip: k_pk_meta / the run path of k_spmv_ldsp): a block of 64 rows whose rows all hold L entries with
+    """Run blocks (csr_packed.hip: k_pk_meta / the run path of k_spmv_ldsp): a block of 64 rows whose rows all hold L entries with
     column(row r, slot k) = column(row 0, slot k) + r keeps row 0's columns only.  Against the plain row-block kernel the
     product must not change by a bit -- on pure stencils (L = 1 .. 40: one slot per lane, the 9-slot batch, the tail loop),
     on sizes that leave a partial last block, on matrices where ONE entry of one block breaks the pattern (that block must
@@ -172,7 +172,7 @@ def _stencil(dims, reach, faces=False):
 
 
 def test_template_blocks_of_the_packed_form(api, port):
-    """Template blocks (csr.hip: k_pk_meta / the template path of k_spmv_ldsp): a block of 64 rows whose entries all lie on the
+    """Template blocks (csr_packed.hip: k_pk_meta / the template path of k_spmv_ldsp): a block of 64 rows whose entries all lie on the
     <= 64 diagonals keeps those offsets and a 64-bit mask per row -- the blocks of a stencil that grid boundaries
     pass through.  27-point stencils on grids whose lines are shorter than, equal to, and no multiple of the 64-row block, a
     5 x 5 stencil in 2D: every block must be a run or a template, y must equal the plain row-block kernel's bit for bit, the

@@ -1,4 +1,4 @@
-"""-m gpu: stretches of run blocks (csr.hip: k_pk_stretch_flags / the stretch path of k_spmv_ldsp).  Consecutive full run blocks with the
+"""-m gpu: stretches of run blocks (csr_packed.hip: k_pk_stretch_flags / the stretch path of k_spmv_ldsp).  Consecutive full run blocks with the
 same row length, the same offsets column - row and their entries one behind the other form a stretch; the blocks of the four longest
 stretches derive their plan from their number instead of loading it.  Nothing of the result may change by a bit: every product here is
 compared with the same kernel's product with the stretches switched off, with the plain row-block kernel's, and with exact row sums,
