@@ -1081,7 +1081,7 @@ int lcg_hip_comm_init(int nranks, int rank, const void *id128)
     g_comm.force = std::getenv("LCG_HIP_FORCE_COMM") != nullptr;
     // Do two ranks of this job sit on one device?  (The real RCCL refuses that; a stand-in bound through LCG_HIP_RCCL_LIB does not.)  The
     // ranks' device UUIDs meet in the communicator's first all-gather; a rank that shares its device makes no placement walks
-    // (driver.hpp) -- what a walk holds, the rank next door cannot have.
+    // (placement.hip) -- what a walk holds, the rank next door cannot have.
     if (nranks > 1) {
         Ctx &c = ctx();
         hipUUID id;
@@ -1101,8 +1101,8 @@ int lcg_hip_comm_init(int nranks, int rank, const void *id128)
         hipFree(d);
         if (e != hipSuccess) return fail(e, "device identities", __FILE__, __LINE__);
         for (int q = 0; q < nranks; q++)
-            if (q != rank && std::memcmp(&all[16 * (size_t)q], &id, 16) == 0) c.ranks_share_device = true;
-        if (c.ranks_share_device && debug_on()) std::fprintf(stderr, "[lcg_hip] rank %d shares its device with another rank of the communicator\n", rank);
+            if (q != rank && std::memcmp(&all[16 * (size_t)q], &id, 16) == 0) c.place.ranks_share_device = true;
+        if (c.place.ranks_share_device && debug_on()) std::fprintf(stderr, "[lcg_hip] rank %d shares its device with another rank of the communicator\n", rank);
     }
     return 0;
 }
@@ -1414,7 +1414,7 @@ int lcg_hip_p2p_selftest(int rounds)
         g_xg.enabled = was;
         if (rc2) return rc2;
         for (int q = 0; q < P; q++)
-            if (q != me && all[2 * (size_t)q] == w[0] && all[2 * (size_t)q + 1] == w[1]) c.ranks_share_device = true;
+            if (q != me && all[2 * (size_t)q] == w[0] && all[2 * (size_t)q + 1] == w[1]) c.place.ranks_share_device = true;
     }
     return 0;
 }

@@ -637,8 +637,8 @@ int lcg_hip_csr_destroy(lcg_hip_csr_t A)
 {
     NOT_DENSE(A, LCG_HIP_E_ARG);
     if (!A) return 0;
-    ctx().forget_places();       // (driver.hpp: Placement remembers timings by the value array's address)
-    ctx().released_bytes += (size_t)A->main.nnz * (A->is_complex ? 20 : 12);     // (the plans beside it not counted: the walk's "fresh allocator" rule needs the order of magnitude)
+    ctx().place.forget_all();     // (placement.hip remembers timings by the value array's address)
+    ctx().place.gave_back((size_t)A->main.nnz * (A->is_complex ? 20 : 12));     // (site 5; the plans beside it not counted: the walk's "fresh allocator" rule needs the order of magnitude)
     dist_free(A);
     free_part(A->main);
     for (int i = 1; i < 4; i++) free_part(A->op[i]);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "lcg_hip.h"
+#include "pool.hpp"
 
 namespace lcgh {
 
@@ -185,54 +186,11 @@ struct Ctx {
     int last_ax_calls = 0;
     int prof_pending = 0;              // events of the finished solve not yet turned into last_ax_mean_us (done on demand)
     DevState *state_stage = nullptr;   // pinned: the initial state of a solve on its way to the device (no stream sync)
-    // scratch vectors of past solves, kept for the next one (hipMalloc + hipFree cost ~0.2 ms per solve, as much as ten
-    // iterations of a small system; lcg_hip_trim() gives them back)
-    struct Scratch { double *p; size_t bytes; bool busy; void *arena; };   // arena: the allocation this vector is a slot of (driver.hpp: Placement), or null
-    std::vector<Scratch> scratch;
-    // where the product's output lies (driver.hpp: Placement): what y = A.x took into a given vector against a given matrix
-    // (val = the matrix's value array; y == nullptr: "this matrix has had its walk, do not look again")
-    struct PlaceMemo { const void *val; const double *y; float us; };
-    std::vector<PlaceMemo> place_memo;
-    void forget_places() { place_memo.clear(); }
-    // one vector left the pool: its timings go, the per-matrix "has had its walk" markers (y == nullptr) stay
-    void forget_vector(const double *y)
-    {
-        if (!y) return;
-        for (size_t i = 0; i < place_memo.size();) if (place_memo[i].y == y) place_memo.erase(place_memo.begin() + (long)i); else i++;
-    }
-    // Bounds of the placement's walk (driver.hpp: Placement::run).  Production values; lcg_hip_placement_tune_for_test lowers them so
-    // that the walk, the arenas and their eviction run under -m gpu at a few million rows.
-    struct PlaceTune {
-        size_t stream_min = (size_t)768 << 20;     // a product that streams less shows one kind of place only: nothing is timed
-        size_t chunk = (size_t)1 << 30;            // the walk's step
-        int max_chunks = 128;
-        double wall_ms = 60.0;                     // looked at after EVERY allocation of the walk
-        size_t hold_max = (size_t)64 << 30;        // what a walk may hold at once: this many bytes ...
-        double hold_frac = 0.25;                   // ... and this fraction of the memory that was free when it started
-        size_t keep_free = (size_t)8 << 30;        // never into the last bytes of free memory
-        size_t shared_min = (size_t)4 << 30;       // others held more than this when the library was initialised: the device is shared, no walk
-        bool predict = true;                       // another chunk only while time used + the dearest allocation so far <= wall_ms
-        size_t released_max = (size_t)1 << 30;     // the library has given back more than this in the process's life: no walk (below)
-        int force_find_at = -1;                    // test hook: the k-th TIMED chunk is taken as the faster place whatever the clock says
-    } place_tune;
-    // What the library has handed back to the device in this process's life (matrices destroyed, pool vectors and arenas trimmed, the
-    // chunks of an earlier walk).  A 1 GiB hipMalloc costs 0.1-0.5 ms out of memory the process has never held and 30 ms .. 0.5 s ONE
-    // CALL once the allocator recycles what was released (bench.py's variants, LCG_HIP_DEBUG=1: walks of 74 / 381 / 528 ms against a
-    // bound of 60 that can only be looked at between calls) -- so the walk is made while the allocator is fresh: in practice once per
-    // process, for its first large system.
-    size_t released_bytes = 0;
-    bool ranks_share_device = false;               // two ranks of the communicator / of the mailboxes sit on this device (comm.hip: found at connect time)
-    size_t mem_total = 0, mem_free_at_init = 0;    // hipMemGetInfo at ensure_init: total - free = what others (and the host program) held
-    // the latest walk: chunks allocated, wall time, most bytes held at once, 1 = a faster place was kept, why it ended
+    Pool pool;                         // the work vectors kept between solves (pool.hpp)
+    PlaceState place;                  // where the product's output lies: memo, bounds, mode, reports (pool.hpp; the code: placement.hip)
     // what the latest solve enqueued: vector passes, scalar steps (a step that sums over ranks is one step, whatever it launches),
     // reductions over ranks (RCCL or mailboxes), products (lcg_hip_last_launches)
     int cnt_vec = 0, cnt_scal = 0, cnt_allreduce = 0, cnt_ax = 0;
-    int walks_made = 0;
-    int walk_chunks = 0, walk_found = 0; double walk_ms = 0.0; size_t walk_held = 0; const char *walk_end = "";
-    int place_mode = -1;               // lcg_hip_set_placement: -1 auto (large products on one GPU), 0 never, 1 whenever the callback is the built-in one
-    int place_timed = 0;               // candidates timed by the latest solve (0: answered from the memo, or not tried)
-    int place_moved = 0;               // roles the latest solve moved to another vector
-    double place_us_first = 0.0, place_us_chosen = 0.0;   // the latest solve's first output: as allocated / as placed
     unsigned shadow_seed = 1;
     std::vector<double> shadow_vec;    // explicit rbar0 for the next complex solve
     std::string err;

@@ -77,8 +77,8 @@ int ensure_init()
         HIPCHK(hipHostGetDevicePointer((void **)&c.snap_dev[i], c.snap[i], 0));
         HIPCHK(hipEventCreateWithFlags(&c.snap_ev[i], hipEventDisableTiming));
     }
-    if (hipMemGetInfo(&c.mem_free_at_init, &c.mem_total) != hipSuccess) { (void)hipGetLastError(); c.mem_free_at_init = c.mem_total = 0; }
-    if (const char *e = std::getenv("LCG_HIP_PLACE")) { const int v = atoi(e); if (v >= -1 && v <= 1 && c.place_mode == -1) c.place_mode = v; }
+    if (hipMemGetInfo(&c.place.mem_free_at_init, &c.place.mem_total) != hipSuccess) { (void)hipGetLastError(); c.place.mem_free_at_init = c.place.mem_total = 0; }
+    if (const char *e = std::getenv("LCG_HIP_PLACE")) { const int v = atoi(e); if (v >= -1 && v <= 1 && c.place.mode == -1) c.place.mode = v; }
     c.inited = true;
     return 0;
 }
@@ -261,84 +261,6 @@ double lcg_hip_last_ax_mean_us(void)
     return c.last_ax_mean_us;
 }
 
-int lcg_hip_trim(void)
-{
-    Ctx &c = ctx();
-    if (!c.inited) return 0;
-    (void)hipDeviceSynchronize();
-    // (slots of an arena go together: the arena is given back when none of its slots is in use)
-    auto arena_busy = [&](void *a) { for (auto &s : c.scratch) if (s.arena == a && s.busy) return true; return false; };
-    for (auto it = c.scratch.begin(); it != c.scratch.end();) {
-        if (it->busy || (it->arena && arena_busy(it->arena))) { ++it; continue; }
-        if (!it->arena || it->p == it->arena) (void)hipFree(it->p);
-        c.released_bytes += it->bytes;
-        it = c.scratch.erase(it);
-    }
-    c.forget_places();       // (addresses may come back as other memory)
-    return 0;
-}
-int lcg_hip_pool_info(int *vectors, int64_t *bytes, int *arena_slots)
-{
-    Ctx &c = ctx();
-    int64_t b = 0; int a = 0;
-    for (auto &s : c.scratch) { b += (int64_t)s.bytes; a += s.arena != nullptr; }
-    if (vectors) *vectors = (int)c.scratch.size();
-    if (bytes) *bytes = b;
-    if (arena_slots) *arena_slots = a;
-    return 0;
-}
-int lcg_hip_pool_add_arena_for_test(uint64_t slot_bytes, int slots)
-{
-    if (slot_bytes == 0 || slots <= 0) return LCG_HIP_E_ARG;
-    int rc = ensure_init(); if (rc) return rc;
-    Ctx &c = ctx();
-    const size_t slot = ((size_t)slot_bytes + 255) & ~(size_t)255;
-    void *base = nullptr;
-    HIPCHK(hipMalloc(&base, slot * (size_t)slots));
-    for (int i = 0; i < slots; i++) c.scratch.push_back({reinterpret_cast<double *>(static_cast<char *>(base) + (size_t)i * slot), slot, false, base});
-    return 0;
-}
-int lcg_hip_placement_tune_for_test(uint64_t stream_min_bytes, uint64_t chunk_bytes, int max_chunks, double wall_ms, uint64_t hold_max_bytes,
-                                    int force_find_at, int allow_shared)
-{
-    int rc = ensure_init(); if (rc) return rc;
-    Ctx::PlaceTune t;       // zeros / negatives: the production value
-    if (stream_min_bytes) t.stream_min = (size_t)stream_min_bytes;
-    if (chunk_bytes) t.chunk = ((size_t)chunk_bytes + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1);
-    if (max_chunks > 0) t.max_chunks = max_chunks;
-    if (wall_ms > 0.0) t.wall_ms = wall_ms;
-    if (hold_max_bytes) t.hold_max = (size_t)hold_max_bytes;
-    t.force_find_at = force_find_at;
-    if (allow_shared) t.shared_min = ~(size_t)0;
-    if (allow_shared == 1) { t.released_max = ~(size_t)0; t.predict = false; }    // (a test walks many times in one process; 2 keeps the fresh-allocator rule)
-    ctx().place_tune = t;
-    return 0;
-}
-int lcg_hip_last_placement_walk(int *chunks, double *wall_ms, int64_t *held_bytes, int *found, const char **ended)
-{
-    Ctx &c = ctx();
-    if (chunks) *chunks = c.walk_chunks;
-    if (wall_ms) *wall_ms = c.walk_ms;
-    if (held_bytes) *held_bytes = (int64_t)c.walk_held;
-    if (found) *found = c.walk_found;
-    if (ended) *ended = c.walk_end;
-    return c.walks_made;
-}
-int lcg_hip_set_placement(int mode)
-{
-    if (mode < -1 || mode > 1) return LCG_HIP_E_ARG;
-    ctx().place_mode = mode;
-    return 0;
-}
-int lcg_hip_last_placement(int *timed, int *moved, double *us_as_allocated, double *us_as_placed)
-{
-    Ctx &c = ctx();
-    if (timed) *timed = c.place_timed;
-    if (moved) *moved = c.place_moved;
-    if (us_as_allocated) *us_as_allocated = c.place_us_first;
-    if (us_as_placed) *us_as_placed = c.place_us_chosen;
-    return 0;
-}
 int lcg_hip_last_ax_calls(void) { return ctx().last_ax_calls; }
 int lcg_hip_last_launches(int *vector_passes, int *scalar_steps, int *rank_reductions, int *products)
 {

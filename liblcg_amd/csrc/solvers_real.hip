@@ -522,7 +522,7 @@ static int solve_cg(lcg_axfunc_ptr Afp, lcg_progress_ptr Pfp, double *m, const d
                                (c.cg_schedule == LCG_HIP_CG_AUTO && (comm_active() || (n < CG1_AUTO_ROWS && Afp == lcg_hip_csr_ax)));
     double *w = nullptr;
     if (one_reduction) TRY(k.get(w));
-    // roles by weight (driver.hpp: Placement): what the loop's product writes (A.d; w = A.g in the one-reduction arrangement), what it
+    // roles by weight (placement.hip: place_roles): what the loop's product writes (A.d; w = A.g in the one-reduction arrangement), what it
     // reads, the rest
     if (one_reduction) TRY(k.place(B, {&w, &g, &d, &Ad}, 1));
     else TRY(k.place(B, {&Ad, &d, &g}, 1));

@@ -1,4 +1,4 @@
-"""-m gpu: where the product's output lies (lcg_hip_set_placement, driver.hpp: Placement).
+"""-m gpu: where the product's output lies (lcg_hip_set_placement, placement.hip).
 Placement hands the solver's work vectors to other ROLES -- it must not change a bit of any iterate, must leave vectors the caller
 supplied where they are, must answer later solves from its memory, and must forget when vectors or matrices go away.
 The reference allocates its temporaries per call and knows no such thing (lcg.cpp:158-166); the oracle is the referee of the iterates."""
@@ -162,7 +162,7 @@ MB = 1 << 20
 
 
 def test_the_walk_its_arenas_and_its_bounds(api, lib, port):
-    """driver.hpp: Placement::run, the part automatic mode reaches only from 768 MB of stream: chunks allocated one after the other,
+    """placement.hip: place_roles, the part automatic mode reaches only from 768 MB of stream: chunks allocated one after the other,
     the product timed into every fourth, the chunk found kept as an arena and cut into work vectors, a second and a third matrix,
     the idle arena evicted, lcg_hip_trim.  The test hook lowers the thresholds (64 MB chunks, 256 MB of stream) and takes the second
     timed chunk as the faster place, so the whole path runs at 2M rows whatever this box's memory looks like.  Iterates: bit-identical
